@@ -11,8 +11,11 @@ windows, random reference-style weights with the zero-init trap removed, BASELIN
 round-robin to the ranks, each round's clip results are all-gathered over RCCL and every rank replays the
 tracker in global clip order while the next round computes (weak scaling: per-GPU frames fixed).
 
-Rank 0 prints ONE JSON line of at most LINE_LIMIT (4096) bytes -- the driver's contract keys and numbers only; the full objects go to
-gpurun_out/bench_extras.json (named by the line's `extras`), the sentences to DESIGN.md §5.  The default single-GPU invocation is an
+Rank 0 prints ONE JSON line of at most LINE_LIMIT (4096) bytes -- the driver's contract keys and numbers only.  A plain run does
+nothing but the headline: set-up, W warm-up steps, K timed steps, the outputs of the last timed step if --dump-outputs DIR is given
+(`dump_outputs`), the line.  Everything else the benchmark measures -- roofline and per-launch figures, the extra modes, the CPU baseline,
+the other configs, the root-load rehearsal, the multi-rank self-verification and halo-exchange A/B -- runs only with --full; there the
+full objects go to an extras file (named by the line's `extras`), the sentences to DESIGN.md §5, and the single-GPU invocation is an
 orchestrator that never touches the GPU: the headline leg runs FIRST in a child process, the N = 8 root-load rehearsal in a second child
 while the wall budget allows (`orchestrate`).
 """
@@ -450,6 +453,51 @@ def same_output(a, b):
     return True, ""
 
 
+DUMP_LIMIT = 64 << 20                 # bytes of every --dump-outputs array together
+DUMP_SAMPLE = 1 << 17                 # mask pixels sampled per instance (fixed positions: seed 0 over the video's frames x rows x columns)
+
+
+def dump_outputs(out, d):
+    """--dump-outputs DIR: what one `MDQE.forward` call returned, as DIR/<name>.npy in float32 / float64, so that two builds can be compared
+    output for output.  Scores and labels whole; the boolean masks [L, H, W] per instance (a 360p video of 120 frames: 28 MB each) as
+    per-frame, per-row and per-column pixel counts (exact in float) plus DUMP_SAMPLE pixels at seeded positions.  RLE strings
+    (--rle-output) are not arrays: only scores and labels are written then.  Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {"pred_scores": np.asarray(out["pred_scores"], dtype=np.float64),
+              "pred_labels": np.asarray(out["pred_labels"], dtype=np.float64),
+              "image_size": np.asarray(out["image_size"], dtype=np.float64)}
+    masks = out.get("pred_masks")
+    if masks:
+        n = len(masks)
+        L, H, W = (int(s) for s in masks[0].shape)
+        # (up to n_max_inst = 120 instances: the row / column counts only while they take at most half the limit, the sample the rest --
+        # always the first positions of the same seeded draw)
+        lines = 4 * n * L * (H + W) <= DUMP_LIMIT // 2
+        room = DUMP_LIMIT - 1024 - n * (8 * L + (4 * L * (H + W) if lines else 0))
+        s = max(1, min(DUMP_SAMPLE, L * H * W, room // (4 * n)))
+        pick = torch.randint(0, L * H * W, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))[:s].sort().values
+        area, rows, cols, sample = [], [], [], []
+        for m in masks:
+            m = m.to("cpu", torch.int32)
+            area.append(m.sum(dim=(1, 2)))
+            if lines:
+                rows.append(m.sum(dim=2))
+                cols.append(m.sum(dim=1))
+            sample.append(m.reshape(-1)[pick])
+        arrays["pred_masks_area"] = torch.stack(area).numpy().astype(np.float64)           # [n, L]
+        if lines:
+            arrays["pred_masks_rows"] = torch.stack(rows).numpy().astype(np.float32)       # [n, L, H]
+            arrays["pred_masks_cols"] = torch.stack(cols).numpy().astype(np.float32)       # [n, L, W]
+        arrays["pred_masks_sample"] = torch.stack(sample).numpy().astype(np.float32)       # [n, s]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise ValueError("--dump-outputs: %d bytes of arrays, more than the %d allowed" % (total, DUMP_LIMIT))
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return {name: a.shape for name, a in arrays.items()}
+
+
 def fail_hook(where, rank):
     """Test hooks for the failure paths of a multi-rank run: MDQE_BENCH_FAIL_RANK=r MDQE_BENCH_FAIL_AT=init|run makes rank r raise there,
     MDQE_BENCH_HANG_RANK=r makes it sleep instead (the others must time out, not wait for ever)."""
@@ -594,7 +642,8 @@ def orchestrate(args, argv):
     budget = float(os.environ.get("MDQE_BENCH_BUDGET_S", "118"))
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     want_cpu = not args.no_cpu_baseline and args.config == "R50_ovis_360"
-    full, rc = run_leg("main", {}, list(argv) + (["--no-cpu-baseline"] if want_cpu else []), float(os.environ.get("MDQE_BENCH_MAIN_S", "540")))
+    argv = list(argv) + ([] if "--full" in argv else ["--full"])          # (the main leg measures everything the --full line carries)
+    full, rc = run_leg("main", {}, argv + (["--no-cpu-baseline"] if want_cpu else []), float(os.environ.get("MDQE_BENCH_MAIN_S", "540")))
     if rc != 0 or "value" not in full:
         print("bench.py: %s" % full.get("error", "the main leg printed no headline"), file=sys.stderr)
         return rc or 1
@@ -616,7 +665,7 @@ def orchestrate(args, argv):
             halo = os.environ.get("MDQE_BENCH_ROOT_LOAD_HALO", "1") != "0"
             r, rc2 = run_leg("root_load", {"MDQE_BENCH_ROOT_LOAD": str(rl_w), "MDQE_BENCH_ROOT_LOAD_HALO": "1" if halo else "0",
                                            "MDQE_BENCH_LEG_DEADLINE_S": "%.1f" % (limit - 2)},
-                             ["--frames", str(args.frames), "--no-cpu-baseline", "--no-fast-mode"], limit + 20)
+                             ["--frames", str(args.frames), "--no-cpu-baseline", "--no-fast-mode", "--full"], limit + 20)
             if rc2 != 0:
                 full["root_load"] = r
             else:
@@ -663,6 +712,12 @@ def main():
     ap.add_argument("--config", choices=["R50_ovis_360", "R50_ovis_720", "swinl_ovis"], default="R50_ovis_360",
                     help="R50_ovis_360 is BASELINE.json's metric config; R50_ovis_720 = 640x1138 frames (configs[2]); "
                          "swinl_ovis = SwinV2-L, 480x853 frames, 2-frame clips (configs[3])")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: roofline / per-launch figures, the extra modes, the CPU baseline, the other configs, "
+                         "the root-load rehearsal, the multi-rank self-verification and halo-exchange A/B, the extras file.  Off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB; "
+                         "masks as per-frame / per-row / per-column pixel counts and a fixed seeded sample of pixels)")
     args = ap.parse_args()
     t_start = time.perf_counter()
     if args.gpus < 1:
@@ -701,7 +756,7 @@ def main():
     # is the top of an invocation and prints the compact line (MDQE_BENCH_LINE=full: the full object instead, for the tools/ scripts)
     leg = os.environ.get("MDQE_BENCH_LEG", "")
     full_line = bool(leg) or os.environ.get("MDQE_BENCH_LINE") == "full"
-    if not leg and world == 1 and not sharded and not probe:
+    if args.full and not leg and world == 1 and not sharded and not probe:
         sys.exit(orchestrate(args, sys.argv[1:]))
     if leg == "cpu":
         # the CPU baseline alone: BASELINE.json's configs[0] through the oracle on the host cores; no GPU call in this process
@@ -724,8 +779,8 @@ def main():
         os.write(json_fd, (line + "\n").encode())
 
     def emit_result(obj):
-        """Rank 0's one line: the full object from a leg, the compact line (+ the extras file) from the top of an invocation."""
-        emitted(json.dumps(obj) if full_line else compact_line(obj, write_extras(obj)))
+        """Rank 0's one line: the full object from a leg, the compact line (+ the extras file with --full) from the top of an invocation."""
+        emitted(json.dumps(obj) if full_line else compact_line(obj, write_extras(obj) if args.full else None))
 
     root_rest = os.environ.get("MDQE_BENCH_ROOT_REST", "1") != "0"       # N >= 3: rank 0 takes no chunk in the last round (sharding.rest_root_sizes)
     as_rank = int(os.environ.get("MDQE_BENCH_AS_RANK", "0")) if root_load > 0 else 0     # rehearsal: play THAT rank of the N-rank job (no replay)
@@ -784,7 +839,8 @@ def main():
     from mdqe_cvpr2023_amd import ops
 
     meter = Meter()
-    meter.install()
+    if args.full:
+        meter.install()                                    # (the roofline figures; a plain run's launches go to the library directly)
     phases = {}                                            # wall seconds since process start at the end of each phase (the extras file)
 
     def mark(name):
@@ -972,6 +1028,7 @@ def main():
     verified = None
     if sharded:
         fail_hook("run", rank)
+    if sharded and args.full:
         ok, vinfo = verify_sharded(args.halo_exchange)
         if not ok:
             dist.destroy_process_group()
@@ -1075,7 +1132,9 @@ def main():
     trk_timing = rank == 0 and (sharded or os.environ.get("MDQE_BENCH_TRK_TIMES") == "1")
     if trk_timing:
         _lib.load_library().mdqe_debug_trk_times(None, 1)          # host seconds inside the native tracker updates of the timed steps
-    dt, out = timed(args.precision, True, step_ms=steps_ms, **({"stats": st_main, "rest_until": rest_env} if sharded else {}))
+    dt, out = timed(args.precision, args.full, step_ms=steps_ms, **({"stats": st_main, "rest_until": rest_env} if sharded else {}))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
     if trk_timing:
         _lib.load_library().mdqe_debug_trk_times(trk_times, 0)
         if not sharded:
@@ -1115,7 +1174,7 @@ def main():
         return meter.summary(), meter.msda_summary()
 
     g_iso = m_iso = clip_stage = None
-    if not sharded:
+    if not sharded and args.full:
         g_iso, m_iso = isolated_pass(model)
         if not args.no_fast_mode:
             clip_stage = clip_stage_alone(model, cfg, torch.stack(host_frames).cuda(), meter, L, T)
@@ -1129,7 +1188,7 @@ def main():
         d, o = timed(precision, False, steps=xs, warmup=xw, **kw)
         return dict(rate(d, steps=xs), steps=xs), o
 
-    if not args.no_fast_mode and not vworld:
+    if args.full and not args.no_fast_mode and not vworld:
         extra["stream_mode"], _ = extra_leg(args.precision, stream=True)       # MDQE.forward_stream / run_round_robin_stream
         if args.precision == "f32":
             extra["fast_mode"], _ = extra_leg("f16x3")                         # f16x3 split precision, same parity bars
@@ -1266,7 +1325,7 @@ def main():
             line["clip_stage"] = clip_stage
         line.update(extra)
 
-    if rank == 0 and not sharded and not args.no_cpu_baseline:
+    if rank == 0 and not sharded and args.full and not args.no_cpu_baseline:
         # the CPU leg is BASELINE.json's configs[0] -- R50_ovis_360, 4 frames on the host cores -- and is quoted on the metric's config only
         line["cpu_baseline"] = cpu_baseline(cfg, sd, video[:4]) if args.config == "R50_ovis_360" else None
         mark("cpu_baseline")
@@ -1282,7 +1341,7 @@ def main():
 
     side = os.environ.get("MDQE_BENCH_SIDE_CONFIGS", "")            # "1": always, "0": never, unset: with the other extras of the headline config
     if (not sharded and rank == 0 and args.config == "R50_ovis_360" and args.precision == "f32"
-            and (side == "1" or (side != "0" and not args.no_fast_mode))):
+            and (side == "1" or (side != "0" and args.full and not args.no_fast_mode))):
         # BASELINE.json configs[2] and configs[3] as extra keys of the driver's line
         sf, ss = os.environ.get("MDQE_BENCH_SIDE_FRAMES"), int(os.environ.get("MDQE_BENCH_SIDE_STEPS", "4"))     # (tests: reduced sizes)
         for key, name, frames_, steps_ in (("config_R50_ovis_720", "R50_ovis_720", int(sf or 60), ss), ("config_swinl_ovis", "swinl_ovis", int(sf or 40), ss)):
@@ -1303,7 +1362,8 @@ def main():
     # It has never run over RCCL with more than one rank, so it runs LAST and under a soft deadline: if it has not finished in time,
     # rank 0 prints the line it already has (with `degraded`) and every rank leaves at once, without the process group's shutdown.
     halo_ab = os.environ.get("MDQE_BENCH_HALO_AB", "")             # "1": always, "0": never, unset: with the other extras of the line
-    if sharded and world > 1 and not vworld and not args.halo_exchange and (halo_ab == "1" or (halo_ab != "0" and not args.no_fast_mode)):
+    if (sharded and world > 1 and not vworld and not args.halo_exchange
+            and (halo_ab == "1" or (halo_ab != "0" and args.full and not args.no_fast_mode))):
         budget = float(os.environ.get("MDQE_BENCH_HALO_AB_S", "75"))
 
         def halo_gave_up():

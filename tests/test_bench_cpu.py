@@ -272,3 +272,28 @@ def test_orchestrator_runs_the_headline_first_and_skips_the_rehearsal_when_the_b
     # a failing main leg: no line, its exit code
     monkeypatch.setattr(bench, "run_leg", lambda *a: ({"error": "boom"}, 3))
     assert bench.orchestrate(args, []) == 3 and capsys.readouterr().out.strip() == ""
+
+
+def test_dump_outputs_writes_bounded_float_arrays_at_fixed_positions(tmp_path):
+    """--dump-outputs: scores / labels whole, masks as exact per-frame / row / column counts plus a seeded sample at the same positions
+    every run; float32 / float64 only and at most 64 MB together, also at n_max_inst = 120 instances of a 120-frame 360p video."""
+    import numpy as np
+    from bench import DUMP_LIMIT, dump_outputs
+    g = torch.Generator().manual_seed(5)
+    masks = [torch.rand(6, 36, 64, generator=g) > 0.5 for _ in range(3)]
+    out = {"image_size": (36, 64), "pred_scores": [0.9, 0.5, 0.25], "pred_labels": [3, 1, 4], "pred_masks": masks}
+    shapes = dump_outputs(out, str(tmp_path / "a"))
+    dump_outputs(out, str(tmp_path / "b"))
+    for name in shapes:
+        a, b = (np.load(str(tmp_path / d / (name + ".npy"))) for d in ("a", "b"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    area = np.load(str(tmp_path / "a" / "pred_masks_area.npy"))
+    assert np.array_equal(area, torch.stack(masks).sum(dim=(2, 3)).numpy())
+    assert np.array_equal(np.load(str(tmp_path / "a" / "pred_labels.npy")), [3.0, 1.0, 4.0])
+    assert np.array_equal(np.load(str(tmp_path / "a" / "pred_masks_rows.npy")), torch.stack(masks).sum(dim=3).numpy())
+    # the largest output the shipped config can return stays within the limit
+    big = torch.zeros(120, 360, 640, dtype=torch.bool)
+    shapes = dump_outputs({"image_size": (360, 640), "pred_scores": [0.5] * 120, "pred_labels": [0] * 120, "pred_masks": [big] * 120},
+                          str(tmp_path / "c"))
+    total = sum(os.path.getsize(str(tmp_path / "c" / f)) for f in os.listdir(str(tmp_path / "c")))
+    assert total <= DUMP_LIMIT + 4096 * len(shapes) and shapes["pred_masks_sample"][0] == 120

@@ -34,7 +34,8 @@ def _contract(d, frames, steps, warmup):
 
 
 def test_bench_line_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "24", "--no-cpu-baseline", "--no-fast-mode"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "24", "--no-cpu-baseline", "--no-fast-mode",
+                        "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     c, text, d = _line_and_full(r.stdout)
@@ -65,12 +66,12 @@ def test_bench_line_contract():
 
 
 def test_bench_default_invocation_every_leg_on_fits_the_line():
-    """The DEFAULT invocation (every leg on: extra modes, CPU baseline, configs[2] / configs[3], the N = 8 root-load rehearsal in both forms) at
+    """The --full invocation (every leg on: extra modes, CPU baseline, configs[2] / configs[3], the N = 8 root-load rehearsal in both forms) at
     reduced size: ONE line of at most 4096 bytes that keeps the driver's contract and carries the extras as numbers; the headline is timed
     FIRST (the rehearsal's child starts after the main leg has left); the full objects are in the extras file."""
     env = dict(os.environ, MDQE_BENCH_SIDE_FRAMES="12", MDQE_BENCH_SIDE_STEPS="1", MDQE_BENCH_SIDE_S="300", MDQE_BENCH_ROOT_LOAD_LEG="8",
                MDQE_BENCH_ROOT_LOAD_S="400")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "36"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "36", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     c, text, d = _line_and_full(r.stdout)
@@ -113,6 +114,33 @@ def test_bench_default_invocation_every_leg_on_fits_the_line():
     assert rh["tracker_native_ms_per_step"]["updates_per_step"] >= 8 * 30
 
 
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times the headline and nothing else: the contract keys, no roofline / extra modes / CPU baseline / extras
+    file; --dump-outputs writes the last timed step's result (float32 / float64 arrays, <= 64 MB) that agrees with the line."""
+    import numpy as np
+    d_out = str(tmp_path / "out")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", "24",
+                        "--dump-outputs", d_out], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[:2000]
+    c = json.loads(lines[0])
+    for k, t in (("metric", str), ("value", float), ("unit", str), ("ms_per_step", float), ("higher_is_better", bool), ("dtype", str)):
+        assert isinstance(c[k], t), (k, c[k])
+    assert c["steps"] == 2 and c["warmup"] == 1 and c["unit"] == "frames/s" and c["dtype"] == "f32" and c["higher_is_better"] is True
+    assert abs(c["value"] - 24 * 1e3 / c["ms_per_step"]) < 2e-3 * c["value"]
+    for k in ("roofline", "roofline_msda", "cpu_baseline", "clip_stage", "fast_mode", "config_R50_ovis_720", "root_load"):
+        assert k not in c, k
+    assert c["extras"] is None
+    files = sorted(os.listdir(d_out))
+    assert {"pred_scores.npy", "pred_labels.npy", "pred_masks_area.npy", "pred_masks_sample.npy"} <= set(files), files
+    arrays = {f: np.load(os.path.join(d_out, f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    n = c["config"]["instances_out"]
+    assert arrays["pred_scores.npy"].shape == (n,) and arrays["pred_masks_area.npy"].shape == (n, 24)
+
+
 def test_bench_gpus_2_runs_two_ranks_without_torchrun():
     """`python bench.py --gpus 2` spawns its own ranks (rehearsal hooks: both on this box's one GPU, gloo instead of RCCL) and prints a
     line for TWO ranks."""
@@ -122,7 +150,8 @@ def test_bench_gpus_2_runs_two_ranks_without_torchrun():
     # process group; the recompute form of the same schedule is held to the single-GPU result in tests/test_sharded_gpu.py)
     # MDQE_BENCH_HALO_AB=1: the halo-exchange form runs as the extra key `halo_exchange` of the same line (its own process group, its own
     # bit-exact verification); the recompute form is the headline
-    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--frames", "24", "--no-cpu-baseline", "--no-fast-mode"]
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--frames", "24", "--no-cpu-baseline", "--no-fast-mode",
+            "--full"]
     env["MDQE_BENCH_HALO_AB"] = "1"
     if torch.cuda.device_count() < 2:
         # (that the same command WITHOUT the rehearsal hooks fails loudly on a box with fewer GPUs than ranks is held by

@@ -14,7 +14,7 @@ CFG = (("base", {}), ("dec24", {"MDQE_MSDA_DEC_STAGE_KB": "24"}), ("dec24_tp0", 
        ("pad12", {"MDQE_GEMM_LDS_PAD": "12288"}), ("pad12_dec24", {"MDQE_GEMM_LDS_PAD": "12288", "MDQE_MSDA_DEC_STAGE_KB": "24"}))
 for r in range(reps):
     for name, env in CFG:
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "3", "--no-fast-mode", "--no-cpu-baseline"],
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", steps, "--warmup", "3", "--no-fast-mode", "--no-cpu-baseline"],
                            capture_output=True, text=True, env=dict(os.environ, **env), cwd=ROOT)
         lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
         if p.returncode or not lines:

@@ -3,7 +3,7 @@
 VAR=$1; VALS=$2; ROUNDS=${3:-2}; shift 3
 for i in $(seq 1 $ROUNDS); do
   for v in $VALS; do
-    env $VAR=$v python bench.py --steps 4 --warmup 1 --no-fast-mode "$@" 2>/dev/null | tail -1 > /tmp/_ab_line.json
+    env $VAR=$v python bench.py --full --steps 4 --warmup 1 --no-fast-mode "$@" 2>/dev/null | tail -1 > /tmp/_ab_line.json
     python - "$VAR" "$v" <<'PY'
 import json, sys
 d = json.load(open("/tmp/_ab_line.json"))

@@ -13,7 +13,7 @@ for r in range(reps):
             e = dict(os.environ, **env)
             if sharded:
                 e["MDQE_BENCH_FORCE_SHARDED"] = "1"
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "3", "--no-fast-mode", "--no-cpu-baseline"],
+            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", steps, "--warmup", "3", "--no-fast-mode", "--no-cpu-baseline"],
                                capture_output=True, text=True, env=e, cwd=ROOT)
             lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
             if p.returncode or not lines:
