@@ -122,6 +122,14 @@ int mdqe_gemm_nt_cat2_f32(const float* A1, long lda1, int K1, const float* A2, l
                           int H2, int W2, int stride, const float* W, const float* bias, float* C, long ldc, int N, int act,
                           void* stream);
 
+/* The strided 1x1 conv1 of an MSRA bottleneck (detectron2 BottleneckBlock with STRIDE_IN_1X1 True, the downsampling block of
+ * res3..res5, folded FrozenBN; configs/R101_coco.yaml, R101_ytvis19.yaml; the reference reaches it through cuDNN):
+ * C[(img, oh, ow), :] = act(A[img, oh*stride, ow*stride, :] W^T + bias).  A NHWC [NI, H, W, lda >= K]; C [M = NI*OH*OW, ldc];
+ * W [N, K].  (OH - 1)*stride < H and (OW - 1)*stride < W (a 1x1 conv without padding: OH = (H - 1)/stride + 1).  K a multiple
+ * of 16, any H, W.  Exact fp32 MFMA; the row addressing of mdqe_gemm_nt_cat2_f32's second operand. */
+int mdqe_gemm_nt_pix_f32(const float* A, long lda, int K, int NI, int H, int W, int OH, int OW, int stride, const float* Wt,
+                         const float* bias, float* C, long ldc, int N, int act, void* stream);
+
 /* Linear + residual + LayerNorm in one kernel, for the encoder / decoder pattern  x = norm(x + dropout(linear(..)))
  * (transformer_enc.py:100-110, transformer_dec.py:352-358,404-409; nn.LayerNorm over d_model = 256):
  * C = LN(A W^T + bias + residual) * gamma + beta, N must be 256; C may alias the residual.  Exact fp32 MFMA. */

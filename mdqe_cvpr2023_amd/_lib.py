@@ -92,6 +92,7 @@ SIGNATURES = {
     "mdqe_gemm_ln2_f32": [p, l, p, p, p, l, i, i, i, p, l, p, p, p, p, p, l, f, p],
     "mdqe_gemm_nt_side_f32": [p, l, p, p, p, l, i, i, i, p, p, i, p, p],
     "mdqe_gemm_nt_cat2_f32": [p, l, i, p, l, i, i, i, i, i, i, i, p, p, p, l, i, i, p],
+    "mdqe_gemm_nt_pix_f32": [p, l, i, i, i, i, i, i, i, p, p, p, l, i, i, p],
     "mdqe_groupnorm_nhwc_f32": [p, l, l, p, l, l, i, i, i, i, p, p, f, i, p, p],
     "mdqe_resize_pil_bilinear_u8": [p, l, i, i, i, i, i, i, p, p, p, i, p, p, p, i, p, p],
     "mdqe_stem_im2col_f32": [p, i, l, i, i, i, i, i, p, p, p, p],

@@ -13,6 +13,7 @@ from typing import Tuple
 @dataclass
 class MDQEConfig:
     backbone: str = "R50"                     # "R50" | "R101" | "SwinV2" | "custom"
+    stride_in_1x1: bool = False               # MODEL.RESNETS.STRIDE_IN_1X1: a downsampling block's stride on conv1 (MSRA) instead of conv2
     swin_embed_dim: int = 192                 # MODEL.SWIN.* (mdqe/backbone/config.py:60-75, configs/swinl_coco.yaml)
     swin_depths: Tuple[int, ...] = (2, 2, 18, 2)
     swin_heads: Tuple[int, ...] = (6, 12, 24, 48)
@@ -72,21 +73,45 @@ R50_OVIS_360 = MDQEConfig()
 R50_OVIS_720 = replace(R50_OVIS_360, n_frames_window_test=20, merge_on_cpu=True, apply_cls_thres=0.2, min_size_test=640)
 SWINL_OVIS = MDQEConfig(backbone="SwinV2", backbone_channels=(384, 768, 1536), hidden_dim=192, n_frames=2, n_frames_test=2,
                         n_frames_window_test=20, merge_on_cpu=True, apply_cls_thres=0.1, min_size_test=480)
-PRESETS = {"R50_ovis_360": R50_OVIS_360, "R50_ovis_720": R50_OVIS_720, "swinl_ovis": SWINL_OVIS}
+# configs/R101_ytvis19.yaml -> R50_ytvis19.yaml -> R50_ytvis21.yaml -> R50_coco.yaml
+R101_YTVIS19 = MDQEConfig(backbone="R101", stride_in_1x1=True, num_classes=40, window_inter_frame_asso=7, n_max_inst=70,
+                          n_frames_test=4, n_frames_window_test=30, apply_cls_thres=0.1, min_size_test=360, detections_per_image=10)
+PRESETS = {"R50_ovis_360": R50_OVIS_360, "R50_ovis_720": R50_OVIS_720, "swinl_ovis": SWINL_OVIS, "R101_ytvis19": R101_YTVIS19}
+
+# detectron2 ResNet options (MODEL.RESNETS.*) the backbone implements only at these values: anything else is refused, never ignored
+_RESNET_FIXED = (("NUM_GROUPS", 1), ("WIDTH_PER_GROUP", 64), ("RES5_DILATION", 1), ("NORM", "FrozenBN"), ("STEM_OUT_CHANNELS", 64),
+                 ("RES2_OUT_CHANNELS", 256))
+
+
+def _resnet_options(rn):
+    """MODEL.RESNETS -> (depth, stride_in_1x1); ValueError on an option the backbone does not implement.  Absent keys take the
+    values the product has always assumed (STRIDE_IN_1X1 False: an attribute tree without the key keeps its old meaning)."""
+    depth = getattr(rn, "DEPTH", 50)
+    if depth not in (50, 101):
+        raise ValueError("MODEL.RESNETS.DEPTH = %r is not supported (50 or 101)" % (depth,))
+    for key, want in _RESNET_FIXED:
+        v = getattr(rn, key, want)
+        if v != want:
+            raise ValueError("MODEL.RESNETS.%s = %r is not supported (only %r)" % (key, v, want))
+    deform = getattr(rn, "DEFORM_ON_PER_STAGE", ())
+    if any(bool(d) for d in deform):
+        raise ValueError("MODEL.RESNETS.DEFORM_ON_PER_STAGE = %r is not supported (deformable convolutions)" % (list(deform),))
+    return depth, bool(getattr(rn, "STRIDE_IN_1X1", False))
 
 
 def from_d2_cfg(cfg) -> MDQEConfig:
     m = cfg.MODEL.MDQE
-    depth = getattr(getattr(cfg.MODEL, "RESNETS", None), "DEPTH", 50)
     name = getattr(getattr(cfg.MODEL, "BACKBONE", None), "NAME", "build_resnet_backbone")
     swin = {}
-    if "swinv2" in name:
+    if "swinv2" not in name:
+        depth, s1 = _resnet_options(getattr(cfg.MODEL, "RESNETS", None))
+    else:
         sw = cfg.MODEL.SWIN
         swin = dict(backbone="SwinV2", swin_embed_dim=sw.EMBED_DIM, swin_depths=tuple(sw.DEPTHS), swin_heads=tuple(sw.NUM_HEADS),
                     swin_window=sw.WINDOW_SIZE, swin_mlp_ratio=sw.MLP_RATIO,
                     backbone_channels=tuple(sw.EMBED_DIM * 2 ** i for i in (1, 2, 3)))
     return MDQEConfig(
-        **({"backbone": "R%d" % depth} if not swin else swin),
+        **({"backbone": "R%d" % depth, "stride_in_1x1": s1} if not swin else swin),
         hidden_dim=m.HIDDEN_DIM, nheads=m.NHEADS, enc_layers=m.ENC_LAYERS, dec_layers=m.DEC_LAYERS,
         n_levels=m.NUM_FEATURE_LEVELS, enc_points=m.ENC_NUM_POINTS, dec_points=m.DEC_NUM_POINTS,
         n_frames=cfg.INPUT.SAMPLING_FRAME_NUM, num_classes=m.NUM_CLASSES, num_queries=m.NUM_OBJECT_QUERIES,

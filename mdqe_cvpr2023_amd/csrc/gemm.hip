@@ -605,6 +605,18 @@ extern "C" int mdqe_gemm_nt_side_f32(const float* A, long lda, const float* W, c
   return mdqe_launch_status();
 }
 
+// Cat-mode launch (the K-step-16 kernel with a second, pixel-addressed A operand) on the plain GEMM's tile rule (dispatch_gemm).
+static int launch_cat_k16(GemmParams& p, hipStream_t st) {
+  p.vec_ok = ((((uintptr_t)p.C | (uintptr_t)p.bias) & 15) == 0) && (p.ldc % 4 == 0);
+  const long b128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
+  int tile = 3;
+  if (p.N <= 64) tile = (p.M >= 4096) ? 2 : 3;
+  else if (b128 >= 2000 && (p.N >= 1024 || p.K >= 1024)) tile = 1;
+  else if (b128 >= 2000 && (p.N > 256 || p.K > 256)) tile = 2;
+  mdqe_clear_error();
+  return mdqe_launch_gemm_k16(p, tile, st);
+}
+
 // C = act([A1 | A2'] W^T + bias): the last 1x1 conv of a ResNet bottleneck and its projection shortcut as ONE product -- W = [W3 | Ws]
 // along K, bias = b3 + bs -- so the shortcut's output (as wide as the block's output) is never written and read back.  A1: [M, K1]
 // rows (pitch lda1); A2: the block's input, NHWC [NI, H2, W2, lda2 >= K2], read at pixel (oh*stride, ow*stride) for output row
@@ -628,14 +640,29 @@ extern "C" int mdqe_gemm_nt_cat2_f32(const float* A1, long lda1, int K1, const f
   p.A2 = A2; p.lda2 = lda2; p.K1 = K1; p.a2_bytes = (unsigned)a2b; p.OH = OH; p.OW = OW; p.H = H2; p.Wd = W2; p.stride = stride;
   p.bias = bias; p.act = act; p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb; p.ksplit = 1; p.kchunk = K;
   p.stamps = g_gemm_stamps;
-  p.vec_ok = ((((uintptr_t)C | (uintptr_t)bias) & 15) == 0) && (ldc % 4 == 0);
-  const long b128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-  int tile = 3;                                          // the plain GEMM's rule (dispatch_gemm)
-  if (N <= 64) tile = (M >= 4096) ? 2 : 3;
-  else if (b128 >= 2000 && (N >= 1024 || K >= 1024)) tile = 1;
-  else if (b128 >= 2000 && (N > 256 || K > 256)) tile = 2;
-  mdqe_clear_error();
-  return mdqe_launch_gemm_k16(p, tile, (hipStream_t)stream);
+  return launch_cat_k16(p, (hipStream_t)stream);
+}
+
+// The cat kernel with an empty first operand (K1 = 0): every K-step reads the row (img, oh*stride, ow*stride) of A.
+extern "C" int mdqe_gemm_nt_pix_f32(const float* A, long lda, int K, int NI, int H, int Wd, int OH, int OW, int stride,
+                                    const float* W, const float* bias, float* C, long ldc, int N, int act, void* stream) {
+  MDQE_REQUIRE(NI >= 0 && H > 0 && Wd > 0 && OH > 0 && OW > 0 && stride > 0 && N > 0 && K > 0);
+  MDQE_REQUIRE(K % 16 == 0 && lda % 4 == 0 && lda >= K && ldc >= N);
+  MDQE_REQUIRE((long)(OH - 1) * stride < H && (long)(OW - 1) * stride < Wd);
+  const long Ml = (long)NI * OH * OW;
+  MDQE_REQUIRE(Ml < 0x7FFFFFFFL);
+  if (Ml == 0) return MDQE_OK;
+  MDQE_CHECK_PTR(A); MDQE_CHECK_PTR(W); MDQE_CHECK_PTR(C);
+  MDQE_REQUIRE((((uintptr_t)A | (uintptr_t)W) & 15) == 0);
+  const int M = (int)Ml;
+  const long ab = (((long)NI * H * Wd - 1) * lda + K) * 4, wb = (long)N * K * 4;
+  MDQE_REQUIRE(ab < 0xFFFFFFF0L && wb < 0xFFFFFFF0L);
+  GemmParams p = {};
+  p.A = A; p.W = W; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldc = ldc; p.conv = 0;
+  p.A2 = A; p.lda2 = lda; p.K1 = 0; p.a2_bytes = (unsigned)ab; p.OH = OH; p.OW = OW; p.H = H; p.Wd = Wd; p.stride = stride;
+  p.bias = bias; p.act = act; p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb; p.ksplit = 1; p.kchunk = K;
+  p.stamps = g_gemm_stamps;
+  return launch_cat_k16(p, (hipStream_t)stream);
 }
 
 extern "C" int mdqe_conv2d_nhwc_f32(const float* X, long x_img_stride, const float* Wt, const float* bias, float* Y, long ldy,

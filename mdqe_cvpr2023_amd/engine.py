@@ -109,6 +109,8 @@ class Packed:
                 for bi in range(nb):
                     q = f"{bp}.res{si + 2}.{bi}"
                     blk = NS(stride=2 if (bi == 0 and si > 0) else 1, shortcut=None)
+                    # where the stride sits: conv1 (MSRA, STRIDE_IN_1X1 True) or conv2; the shortcut always carries it
+                    blk.s1, blk.s3 = (blk.stride, 1) if cfg.stride_in_1x1 else (1, blk.stride)
                     if (q + ".shortcut.weight") in sd:
                         w, b = _fold_bn(sd, q + ".shortcut")
                         blk.shortcut = (up(_krsc(w)), up(b))
@@ -419,8 +421,9 @@ class Engine:
 
     # ---- a1, a2, a4: normalise + pad + ResNet ------------------------------------------------------
     def backbone(self, frames, geo):
-        """frames [NI,3,h,w] uint8/fp32 CUDA -> [res3,res4,res5] NHWC.  ResNet-50 as built by detectron2
-        (STRIDE_IN_1X1 False, FrozenBN folded; configs/R50_coco.yaml:7-10)."""
+        """frames [NI,3,h,w] uint8/fp32 CUDA -> [res3,res4,res5] NHWC.  ResNet-50/101 as built by detectron2, FrozenBN folded:
+        STRIDE_IN_1X1 False puts a downsampling block's stride on the 3x3 conv2 (configs/R50_coco.yaml:7-10), True on the 1x1
+        conv1 (MSRA; configs/R101_coco.yaml, R101_ytvis19.yaml)."""
         if self.backbone_fn is not None:
             return self.backbone_fn(frames, geo)
         with self.amp():
@@ -439,16 +442,19 @@ class Engine:
         outs = []
         for si, blocks in enumerate(bb.stages):
             for blk in blocks:
-                s = blk.stride
+                s, s1, s3 = blk.stride, blk.s1, blk.s3
                 if blk.cat is not None and RESNET_CAT and ops.get_gemm_precision() == "f32" and x.is_contiguous():
                     # relu(conv3(y) + shortcut(x)) in one launch: the shortcut's output (as wide as the block's) is never written
-                    y = self._conv(x, blk.conv1, 1, 1, 0, "relu")
-                    y = self._conv(y, blk.conv2, 3, s, 1, "relu")
+                    if s1 == 1:
+                        y = self._conv(x, blk.conv1, 1, 1, 0, "relu")
+                    else:                                          # MSRA conv1: a 1x1 product on every s1-th pixel of x
+                        y = ops.linear_pix(x, s1, blk.conv1[0].view(blk.conv1[0].shape[0], -1), blk.conv1[1], act="relu")
+                    y = self._conv(y, blk.conv2, 3, s3, 1, "relu")
                     x = ops.linear_cat2(y, x, s, *blk.cat, act="relu")
                     continue
                 sc = x if blk.shortcut is None else self._conv(x, blk.shortcut, 1, s, 0, None)
-                y = self._conv(x, blk.conv1, 1, 1, 0, "relu")
-                y = self._conv(y, blk.conv2, 3, s, 1, "relu")
+                y = self._conv(x, blk.conv1, 1, s1, 0, "relu")
+                y = self._conv(y, blk.conv2, 3, s3, 1, "relu")
                 x = self._conv(y, blk.conv3, 1, 1, 0, "relu", residual=sc)
             if si >= 1:
                 outs.append(x)

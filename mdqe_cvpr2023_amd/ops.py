@@ -267,6 +267,23 @@ def linear_cat2(y, x_nhwc, stride, weight, bias, act=None, out=None):
     return out
 
 
+def linear_pix(x_nhwc, stride, weight, bias, act=None, out=None):
+    """act(x[:, ::stride, ::stride] @ weight^T + bias): a 1x1 convolution with stride and no padding, the strided pixels read in place
+    (mdqe_gemm_nt_pix_f32; exact fp32 whatever the GEMM precision mode).  x_nhwc [NI, H, W, K] contiguous, weight [N, K] ->
+    [NI, (H - 1) // stride + 1, (W - 1) // stride + 1, N]."""
+    _chk(x_nhwc, "x"); _chk(weight, "weight"); _chk(bias, "bias")
+    NI, H, W, K = x_nhwc.shape
+    N = weight.shape[0]
+    if weight.dim() != 2 or weight.shape[1] != K:
+        raise RuntimeError("linear_pix: a [N, K] weight required")
+    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if out is None:
+        out = torch.empty((NI, OH, OW, N), dtype=torch.float32, device=x_nhwc.device)
+    check(lib.mdqe_gemm_nt_pix_f32(ptr(x_nhwc), K, K, NI, H, W, OH, OW, stride, ptr(weight), ptr(bias), ptr(out), N, N, ACT[act],
+                                   cur_stream()), "gemm_nt_pix")
+    return out
+
+
 def layernorm(x, gamma, beta, res=None, eps=1e-5, out=None):
     _chk(x, "x"); _chk(res, "res"); _chk(gamma, "gamma"); _chk(beta, "beta")
     C = x.shape[-1]

@@ -25,6 +25,8 @@ ALIASES = {
 
 
 def resnet_manifest(kind="R50", p="detr.backbone.0.backbone"):
+    """detectron2 ResNet-50/101 parameters.  Both stride placements (STRIDE_IN_1X1 False: on the 3x3 conv2; True, MSRA: on the
+    1x1 conv1) have exactly these names and shapes, so a checkpoint does not tell them apart: MDQEConfig.stride_in_1x1 does."""
     m = OrderedDict()
 
     def conv(name, cout, cin, k):
