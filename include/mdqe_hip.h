@@ -213,6 +213,19 @@ int mdqe_conv2d_nhwc_f32(const float* X, long x_img_stride, const float* Wt, con
                          int act, const float* residual, long ldr, int res_first, int tile, const void* w_split,
                          int ksplit, float* splitk_ws, void* stream);
 
+/* ---- stride-1, pad-1 3x3 convolution as fp32 Winograd F(2x2,3x3) (csrc/winograd.hip) ------------
+ * The same product as mdqe_conv2d_nhwc_f32(..., KH = KW = 3, stride = 1, pad = 1, no residual) in the exact fp32 mode, with 2.25x
+ * fewer matrix multiplies; max-abs error about 1.8x the direct kernel's.  Weights are transformed once:
+ * mdqe_winograd_weight_f32 turns the packed [Cout,3,3,Cin] weight into U [16][Cout][Cin] (computed in double, rounded once).
+ * mdqe_conv3x3_winograd_f32: X [NI,H,W,Cin] (Cin % 32 == 0; images x_img_stride floats apart, <= 0: dense), Y [NI*H*W, ldy]
+ * (Cout % 4 == 0, ldy % 4 == 0), fused bias and activation; workspace >= mdqe_winograd_workspace_bytes(NI, H, W, Cin, Cout) bytes,
+ * one per stream.  MDQE_EINVAL outside the exact fp32 GEMM mode (mdqe_set_gemm_precision). */
+int mdqe_winograd_weight_f32(const float* Wt, int Cout, int Cin, float* U, void* stream);
+long mdqe_winograd_workspace_bytes(int NI, int H, int W, int Cin, int Cout);
+int mdqe_conv3x3_winograd_f32(const float* X, long x_img_stride, const float* U, const float* bias, float* Y, long ldy,
+                              int NI, int H, int W, int Cin, int Cout, int act, void* workspace, long ws_bytes, void* stream);
+int mdqe_debug_winograd_tile(int tile);   /* tools/ A/B: K-step-16 tile code of the plane products (0 = by shape) */
+
 /* ---- eval-time frame resize (ResizeShortestEdgeClip -> ResizeTransform -> PIL Image.resize(BILINEAR) on uint8 frames,
  * mdqe/data/augmentation.py:364-389, dataset_mapper.py:252-258), Pillow's two-pass fixed-point resampling bit for bit.
  * in: NI images [C,H,W] u8, in_img_stride bytes apart; out [NI,C,oh,ow] u8.  Coefficient tables (DEVICE int32), built on the

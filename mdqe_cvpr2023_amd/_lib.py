@@ -87,6 +87,9 @@ SIGNATURES = {
     "mdqe_debug_msda_variant": [i],
     "mdqe_mask_row_stats_f32": [p, i, i, i, i, i, p, p, p, p],
     "mdqe_conv2d_nhwc_f32": [p, l, p, p, p, l, i, i, i, i, i, i, i, i, i, i, p, l, i, i, p, i, p, p],
+    "mdqe_winograd_weight_f32": [p, i, i, p, p],
+    "mdqe_conv3x3_winograd_f32": [p, l, p, p, p, l, i, i, i, i, i, i, p, l, p],
+    "mdqe_debug_winograd_tile": [i],
     "mdqe_layernorm_f32": [p, p, p, p, p, l, i, f, p],
     "mdqe_gemm_ln_f32": [p, l, p, p, p, l, i, i, i, p, l, p, p, f, p],
     "mdqe_gemm_ln2_f32": [p, l, p, p, p, l, i, i, i, p, l, p, p, p, p, p, l, f, p],
@@ -148,6 +151,8 @@ def load_library(path=None):
     h.mdqe_dyn_mask_workspace_floats.argtypes = [c_int, c_int, c_int, c_int]
     h.mdqe_groupnorm_workspace_bytes.restype = c_long
     h.mdqe_groupnorm_workspace_bytes.argtypes = [c_int, c_int]
+    h.mdqe_winograd_workspace_bytes.restype = c_long
+    h.mdqe_winograd_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
     for name, args in SIGNATURES.items():
         fn = getattr(h, name)          # AttributeError if the symbol is missing: loud by design
         fn.argtypes = args

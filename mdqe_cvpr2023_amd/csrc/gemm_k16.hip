@@ -59,19 +59,27 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
     while (wall_clock64() < until) __builtin_amdgcn_s_sleep(32);
   }
 
-  // XCD-aware tile order: blocks that share an A row-panel run on the same XCD (same L2).
+  // XCD-aware tile order: blocks that share an A row-panel run on the same XCD (same L2).  A plane batch orders all planes' tiles as
+  // one list (plane-major), so an XCD's contiguous range covers whole row panels of one plane and that plane's W.
   const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
   const int nblk = nbm * nbn;
+  const int nall = p.planes > 1 ? nblk * p.planes : nblk;
   int bid = blockIdx.x;
   {
-    const int q = nblk / 8, r = nblk % 8, xcd = bid % 8, i = bid / 8;
+    const int q = nall / 8, r = nall % 8, xcd = bid % 8, i = bid / 8;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
   }
+  const int plane = bid / nblk;
+  bid -= plane * nblk;
   const int bm = bid / nbn, bn = bid % nbn;
   const int m0 = bm * BM, n0 = bn * BN;
+  // this block's product: the plane's own bases (each plane's buffer range starts at its base -- 32-bit offsets never span planes)
+  const float* const pA = p.A + (long)plane * p.plane_a;
+  const float* const pW = p.W + (long)plane * p.plane_w;
+  float* const pC = p.C + (long)plane * p.plane_c;
 
-  const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, p.a_bytes, 0x00020000);
-  const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, p.w_bytes, 0x00020000);
+  const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)pA, 0, p.a_bytes, 0x00020000);
+  const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)pW, 0, p.w_bytes, 0x00020000);
   const auto rsA2 = __builtin_amdgcn_make_buffer_rsrc((void*)(CAT ? p.A2 : p.A), 0, CAT ? p.a2_bytes : p.a_bytes, 0x00020000);
 
   // instruction j of this wave covers image rows (wave*IPW + j)*16 .. +15; lane -> row += lane>>2, LDS chunk lane&3,
@@ -465,8 +473,8 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
     }
     if (fast) {
       const int c4 = lane & 7, r8 = lane >> 3;
-      const auto rsC = __builtin_amdgcn_make_buffer_rsrc((void*)p.C, 0, (int)(unsigned)c_bytes, 0x00020000);
-      const auto rsR = __builtin_amdgcn_make_buffer_rsrc((void*)(p.residual != nullptr ? p.residual : p.C), 0, (int)(unsigned)(p.residual != nullptr ? r_bytes : c_bytes), 0x00020000);
+      const auto rsC = __builtin_amdgcn_make_buffer_rsrc((void*)pC, 0, (int)(unsigned)c_bytes, 0x00020000);
+      const auto rsR = __builtin_amdgcn_make_buffer_rsrc((void*)(p.residual != nullptr ? p.residual : pC), 0, (int)(unsigned)(p.residual != nullptr ? r_bytes : c_bytes), 0x00020000);
       const int row0 = m0 + wm * (BM / WM), col0 = n0 + wn * (BN / WN);
       const unsigned vC = (unsigned)((r8 * p.ldc + c4 * 4) * 4), vR = (unsigned)((r8 * p.ldr + c4 * 4) * 4);
       const bool has_res = p.residual != nullptr, has_bias = p.bias != nullptr;
@@ -626,7 +634,7 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
             for (int e = 0; e < 4; ++e)
               if (n + e < p.mask_cols) v[e] = 0.f;
           }
-          *reinterpret_cast<f32x4*>(p.C + (long)m * p.ldc + n) = v;
+          *reinterpret_cast<f32x4*>(pC + (long)m * p.ldc + n) = v;
         } else {
           // ragged edge / unaligned operands: element by element, ROLLED (the vector rotates through the loop so that no register is
           // indexed dynamically) -- the generic activation switch, tanhf included, appears once here instead of four times
@@ -645,7 +653,7 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
             if (p.act != MDQE_ACT_NONE && (p.act_cols <= 0 || n + e < p.act_cols)) x = mdqe_act(x, p.act);
             if (!p.res_first) x += rv;
             if (masked && n + e < p.mask_cols) x = 0.f;
-            p.C[(long)m * p.ldc + n + e] = x;
+            pC[(long)m * p.ldc + n + e] = x;
           }
         }
       }
@@ -686,7 +694,7 @@ static int launch_k16_ns_(const GemmParams& p_in, hipStream_t st) {
     smem += (size_t)g_k16_lds_pad;
     if (smem > 64 * 1024 && mdqe_allow_lds(reinterpret_cast<const void*>(kern), 160 * 1024 - 256) != hipSuccess) return MDQE_ELAUNCH;
   }
-  hipLaunchKernelGGL(kern, dim3(nbm * nbn, p.ksplit > 1 ? p.ksplit : 1), dim3(64 * WM * WN), smem, st, p);
+  hipLaunchKernelGGL(kern, dim3(nbm * nbn * (p.planes > 1 ? p.planes : 1), p.ksplit > 1 ? p.ksplit : 1), dim3(64 * WM * WN), smem, st, p);
   return mdqe_launch_status();
 }
 
@@ -710,6 +718,8 @@ static int launch_k16_(const GemmParams& p, hipStream_t st) {
 
 // tile: 1 128x128, 2 128x64, 3 64x64 (as gemm.hip), 7 32x64, 8 32x128, 9 64x128; the split-K reduce pass is launched by the caller
 int mdqe_launch_gemm_k16(const GemmParams& p, int tile, hipStream_t st) {
+  if (p.planes > 1 && (p.conv || p.ksplit > 1 || tile == 6 || p.A2 != nullptr || p.swin_ws > 0 || p.residual != nullptr || p.rowmask != nullptr ||
+                       p.side != nullptr)) return MDQE_EINVAL;                   // plane batch: plain products, plain epilogue only
   if (p.side != nullptr && (p.conv || p.ksplit > 1 || tile == 6 || p.A2 != nullptr)) return MDQE_EINVAL;   // side term: plain tiles only
   if (p.swin_ws > 0 && (p.conv || p.ksplit > 1 || tile == 6 || p.A2 != nullptr)) return MDQE_EINVAL;        // window gather: plain tiles only
   if (p.A2 != nullptr) {                                // cat mode: two A operands side by side along K

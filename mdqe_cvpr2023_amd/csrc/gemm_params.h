@@ -37,6 +37,9 @@ struct GemmParams {
   int swin_ws, swin_shift, swin_H, swin_W;
   int fast_epi;             // K-step-16 kernel: 1 (default) = interior tiles of plain products take the few-instruction epilogue
   int stagger;              // K-step-16 kernel: the first resident round of blocks starts (slot on the CU) x stagger 10-ns ticks late (0: off)
+  // plane batch (K-step-16 kernel, plain products; planes > 1): `planes` independent products of one shape in ONE launch, product z on
+  // A + z*plane_a, W + z*plane_w, C + z*plane_c (floats); a_bytes / w_bytes cover ONE plane (buffer ranges are 32-bit).  winograd.hip
+  int planes; long plane_a, plane_w, plane_c;
 };
 
 #define OOB_OFF 0xFFFFFFF0u

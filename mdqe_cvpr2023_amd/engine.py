@@ -117,6 +117,8 @@ class Packed:
                     for cn in ("conv1", "conv2", "conv3"):
                         w, b = _fold_bn(sd, f"{q}.{cn}")
                         setattr(blk, cn, (up(_krsc(w)), up(b)))
+                    if blk.s3 == 1:                                # stride-1 3x3: Winograd transform of the weight (ops.conv2d_nhwc)
+                        ops.winograd_weight(blk.conv2[0])
                     blk.cat = None
                     if blk.shortcut is not None:                   # conv3 + projection shortcut as one product: W = [W3 | Ws] along K
                         w3, b3 = blk.conv3
@@ -200,7 +202,7 @@ class Packed:
         h = "detr.transformer_dec.mask_head"
         mh = NS()
         for i in (1, 2, 3):
-            setattr(mh, f"lay{i}", (up(_krsc(sd[f"{h}.lay{i}.weight"])), up(sd[f"{h}.lay{i}.bias"])))
+            setattr(mh, f"lay{i}", (ops.winograd_weight(up(_krsc(sd[f"{h}.lay{i}.weight"]))), up(sd[f"{h}.lay{i}.bias"])))
             setattr(mh, f"gn{i}", (up(sd[f"{h}.gn{i}.weight"]), up(sd[f"{h}.gn{i}.bias"])))
         for i in (1, 2):
             setattr(mh, f"ad{i}", (up(_krsc(sd[f"{h}.adapter{i}.weight"])), up(sd[f"{h}.adapter{i}.bias"])))

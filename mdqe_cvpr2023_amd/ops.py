@@ -30,6 +30,8 @@ if os.environ.get("MDQE_MSDA_TP_STAGED"):              # tools/ A/B: 0 = the dec
     check(lib.mdqe_debug_msda_tp_staged(int(os.environ["MDQE_MSDA_TP_STAGED"])), "msda_tp_staged")
 if os.environ.get("MDQE_GEMM_LDS_PAD"):                # tools/ A/B: extra LDS bytes per K-step-16 GEMM block (caps the GEMM blocks per CU)
     check(lib.mdqe_debug_gemm_lds_pad(int(os.environ["MDQE_GEMM_LDS_PAD"])), "gemm_lds_pad")
+if os.environ.get("MDQE_WINOGRAD_TILE"):               # tools/ A/B: K-step-16 tile code of the Winograd plane products (csrc/winograd.hip)
+    check(lib.mdqe_debug_winograd_tile(int(os.environ["MDQE_WINOGRAD_TILE"])), "winograd_tile")
 
 _ws = {}
 
@@ -108,6 +110,50 @@ def _wsplit(w):
     return planes                                    # w is the registered tensor or a full reshaped view of it
 
 
+# ---- constant 3x3 weights: Winograd F(2x2,3x3) transforms for the stride-1 convs (csrc/winograd.hip) ----------
+WINOGRAD = os.environ.get("MDQE_WINOGRAD", "1") != "0"     # 0: every 3x3 conv on the direct implicit GEMM (A/B in one process: set ops.WINOGRAD)
+_wino = {}           # data_ptr -> (weakref to the packed weight, its _version, U [16, Cout, Cin])
+
+
+def winograd_weight(w):
+    """Declare `w` (packed [Cout, 3, 3, Cin] CUDA fp32, contiguous) a constant weight of stride-1 3x3 convs: its Winograd
+    transform U = G g G^T is computed once, and `conv2d_nhwc` then runs the exact-fp32 mode's stride-1, pad-1 launches of it as
+    F(2x2,3x3).  Returns w.  Weights the Winograd path cannot take (Cin < 128, Cin % 32, Cout % 4, Cout > 1024) are left alone."""
+    import weakref
+    if not (torch.is_tensor(w) and w.is_cuda and w.dtype == torch.float32 and w.dim() == 4 and w.is_contiguous()):
+        return w
+    Cout, KH, KW, Cin = w.shape
+    if KH != 3 or KW != 3 or Cin < 128 or Cin % 32 != 0 or Cout % 4 != 0 or Cout > 1024:
+        return w
+    U = torch.empty((16, Cout, Cin), dtype=torch.float32, device=w.device)
+    check(lib.mdqe_winograd_weight_f32(ptr(w), Cout, Cin, ptr(U), cur_stream()), "winograd_weight_f32")
+    key = w.data_ptr()
+    _wino[key] = (weakref.ref(w), w._version, U)
+    weakref.finalize(w, _drop_wino, key)                # U goes when the weight tensor goes
+    return w
+
+
+def _drop_wino(key):
+    ent = _wino.get(key)
+    if ent is not None and ent[0]() is None:
+        del _wino[key]
+
+
+def _wino_u(w):
+    """U of a registered weight (None: not registered, freed, modified in place, or another tensor at the same address)."""
+    ent = _wino.get(w.data_ptr())
+    if ent is None:
+        return None
+    ref, ver, U = ent
+    base = ref()
+    if base is None or base._version != ver:
+        del _wino[w.data_ptr()]
+        return None
+    if w.shape != base.shape or w._version != ver or not w.is_contiguous():
+        return None
+    return U
+
+
 def _workspace(nbytes, device):
     """Scratch buffer (split-K partials, GroupNorm statistics), one per (device, stream): the per-frame stages and the
     per-clip stages run on different streams and must not share it."""
@@ -181,6 +227,18 @@ def conv2d_nhwc(x, w_packed, bias=None, stride=1, pad=0, act=None, residual=None
     ldy = out.stride(-2)
     ldr = residual.stride(-2) if residual is not None else 0
     M, K = NI * OH * OW, KH * KW * Cin
+    if (WINOGRAD and KH == 3 and KW == 3 and stride == 1 and pad == 1 and residual is None and tile == 0 and ksplit == 0
+            and Cin >= 128 and Cin % 32 == 0 and lib.mdqe_get_gemm_precision() == 0):
+        U = _wino_u(w_packed)
+        # (the Winograd entry point takes 16-byte aligned operands and row pitches only; anything else keeps the direct kernel, which
+        # handles unaligned ones)
+        aligned = ((x.data_ptr() | out.data_ptr() | (bias.data_ptr() if bias is not None else 0)) & 15) == 0 and ldy % 4 == 0 and xis % 4 == 0
+        if U is not None and aligned:                    # F(2x2,3x3): 2.25x fewer matrix multiplies (csrc/winograd.hip)
+            nb = lib.mdqe_winograd_workspace_bytes(NI, H, W, Cin, Cout)
+            ws = _workspace(nb, x.device)
+            check(lib.mdqe_conv3x3_winograd_f32(ptr(x), xis, ptr(U), ptr(bias), ptr(out), ldy, NI, H, W, Cin, Cout, ACT[act],
+                                                ptr(ws), ws.numel(), cur_stream()), "conv3x3_winograd_f32")
+            return out
     ws = None
     if ksplit == 0 and K >= 4096 and ((OH * OW + 63) // 64) * ((Cout + 63) // 64) <= 16:
         # few output pixels PER IMAGE, very deep K (input_proj's 3x3/s2 on res5: 60 pixels, K = 18432): spread K over the CUs.  Decided

@@ -20,7 +20,7 @@ rec = []
 L = _lib.load_library()
 if os.environ.get("GEMM_VARIANT"):                       # tools/ A/B: 1 = the K-step-16 kernel for every shape
     L.mdqe_debug_gemm_variant(int(os.environ["GEMM_VARIANT"]))
-raw = {n: getattr(L, n) for n in ("mdqe_gemm_nt_f32", "mdqe_gemm_ln_f32", "mdqe_conv2d_nhwc_f32", "mdqe_gemm_nt_cat2_f32")}
+raw = {n: getattr(L, n) for n in ("mdqe_gemm_nt_f32", "mdqe_gemm_ln_f32", "mdqe_conv2d_nhwc_f32", "mdqe_gemm_nt_cat2_f32", "mdqe_conv3x3_winograd_f32")}
 
 
 class Wrapped:
@@ -50,6 +50,11 @@ class Wrapped:
         NI, H, W, Cin, Cout, KH, KW, stride, pad = a[6:15]
         M = NI * ((H + 2 * pad - KH) // stride + 1) * ((W + 2 * pad - KW) // stride + 1)
         return self._timed("mdqe_conv2d_nhwc_f32", "conv %dx%d/%d M=%7d N=%5d K=%5d" % (KH, KW, stride, M, Cout, KH * KW * Cin), 2.0 * M * Cout * KH * KW * Cin, a)
+
+    def mdqe_conv3x3_winograd_f32(self, *a):         # (TF: the direct convolution's FLOPs over the Winograd launches' time -- effective rate)
+        NI, H, W, Cin, Cout = a[6:11]
+        M = NI * H * W
+        return self._timed("mdqe_conv3x3_winograd_f32", "wino 3x3/1 M=%7d N=%5d K=%5d" % (M, Cout, 9 * Cin), 2.0 * M * Cout * 9 * Cin, a)
 
 
 with torch.no_grad():
