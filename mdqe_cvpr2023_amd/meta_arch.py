@@ -409,9 +409,14 @@ class MDQE(nn.Module):
     CACHE_GB = float(os.environ.get("MDQE_CACHE_GB", "24"))       # HBM budget of ONE frame-cache buffer (a long video uses two)
 
     def iter_clip_results(self, frames_dev, clips, frame_offset=0, trace=None, primed=False, on_frames_queued=None, h2d=None,
-                          halo=None, side_streams=True, prime_all=True, split_small=False):
+                          halo=None, side_streams=True, prime_all=True, split_small=False, carry=None):
         """Per-frame features (computed once, streamed in passes of `frame_batch` frames) + decoder + inference_clip for
         `clips` (global frame indices; frames_dev[0] is global frame `frame_offset`).  Yields (start, end, last, res).
+
+        carry (online video, online._Carry): the cache rows of the `carry.rows` frames in front of this chunk, computed by earlier
+        calls, go into the rows in front of its first frame (`carry.head`), so a clip may start anywhere in them -- a 1-frame push
+        owns only such straddling clips.  The chunk's frames from global frame `carry.tail_from` on (what later calls' clips read)
+        go through the per-frame stages even if no clip here reads them, and their rows are handed to `carry.on_tail`.
 
         Two HIP streams: the per-frame stages (backbone .. decoder value cache: large GEMMs) of the next passes run on a frame
         stream while the decoder + inference_clip of group k (small kernels and two host syncs) run on the caller's
@@ -440,6 +445,10 @@ class MDQE(nn.Module):
             if any(c[1] - c[0] != Tn or c[0] < frame_offset - (Tn - 1) for c in strad) or not clips:
                 raise RuntimeError("halo exchange: a chunk must hold at least one whole clip and its straddling clips T frames")
             lead = Tn - 1 if strad else 0
+        elif carry is not None:
+            lead = carry.rows
+            if any(c[0] < frame_offset - lead or c[1] > frame_offset + n_local for c in clips):
+                raise RuntimeError("online carry: a clip reads frames outside the carried rows and the chunk")
         bounds = self.pass_bounds(n_local, fbatch, self.taper_passes, self.taper_tail, split_small=split_small)
         cuda = frames_dev.is_cuda
         clip_stream = torch.cuda.current_stream(frames_dev.device) if cuda else None
@@ -463,7 +472,15 @@ class MDQE(nn.Module):
             capf = -(-capf // 8) * 8              # (rounded: videos of similar length reuse the allocator's blocks)
         elif halo is not None:
             raise RuntimeError("halo exchange: a chunk (%d frames) must fit one frame-cache buffer (%d frames; MDQE_CACHE_GB)" % (n_local, capf))
+        elif carry is not None:
+            raise RuntimeError("online carry: a chunk (%d frames) must fit one frame-cache buffer (%d frames; MDQE_CACHE_GB)" % (n_local, capf))
         bufs = [self.alloc_cache(capf, geo, keep_enc=halo is not None), None]
+        carry_ev = []                             # (online carry) the event behind the hand-over of the chunk's tail rows
+        if carry is not None and lead:
+            with fctx():
+                if cuda and fstream is not clip_stream:
+                    fstream.wait_stream(clip_stream)
+                carry.head(bufs[0], 0)            # in front of every pass and every `ready` event of this chunk
         readers = [[], []]                        # buffer -> group states that read it
         seg = {"b": 0, "base": 0, "lead": lead}   # row of local frame f in buffer b: f - base + lead
         nxt = 0                                   # local frames [0, nxt) have been through the per-frame stages
@@ -554,6 +571,23 @@ class MDQE(nn.Module):
             for v in tail_state["views"]:
                 v.record_stream(hs)
 
+        def carry_tail():
+            """(online carry) Once every clip is planned: the frames from `carry.tail_from` on through the per-frame stages, their cache
+            rows -- carried rows in front of the chunk included -- to `carry.on_tail` on the frame stream."""
+            nonlocal nxt
+            if carry is None or carry.tail_sent:
+                return
+            t0 = min(max(carry.tail_from - frame_offset, -lead), n_local)
+            if nxt < t0:
+                nxt = t0                          # frames no clip reads (CLIP_STRIDE > clip length)
+            while nxt < n_local:
+                queue_pass()
+            with fctx():
+                carry.on_tail({k_: v[t0 + lead:nxt + lead] for k_, v in bufs[0].items()})
+                if cuda:
+                    carry_ev.append(torch.cuda.Event())
+                    carry_ev[-1].record(fstream)
+
         from collections import deque
         states = deque()                          # prepared (their frames queued on the frame stream) and not yet decoded, in clip order
         plan = {"ci": 0}
@@ -566,6 +600,7 @@ class MDQE(nn.Module):
             nonlocal nxt
             ci = plan["ci"]
             if ci >= len(clips):
+                carry_tail()
                 return False
             off = frame_offset
             T = clips[ci][1] - clips[ci][0]
@@ -686,6 +721,9 @@ class MDQE(nn.Module):
                 res["ready"] = ready
                 res["batch_end"] = gi == len(group) - 1
                 yield start, end, last, res
+        if carry_ev:
+            # the tail passes no group waited for: the chunk's frames and cache are released on the caller's stream after them
+            clip_stream.wait_event(carry_ev[-1])
         if strad:
             raise RuntimeError("halo exchange: the chunk has no full-length group for its straddling clips (chunk_plan(..., halo_exchange=True) "
                                "merges a short last chunk into its neighbour)")
@@ -859,6 +897,14 @@ class MDQE(nn.Module):
         while state["cur"] is not None:
             yield guarded(step)
 
+    def online_video(self, height=None, width=None, emit="masks", keep=False):
+        """An online session over ONE video whose frames arrive in pushes (a camera, a stream, a video too long to hold): push()
+        returns each tracker window as soon as it is final, close() the rest, result() the video-level scores / labels / tracks.
+        height / width: output mask size (default: the frame size); emit: "masks" (bool [n, F, H, W] per window) or "rle"; keep:
+        result() also carries forward()'s "pred_masks" / "pred_rles", bit-identical.  See online.py."""
+        from .online import OnlineVideo
+        return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep)
+
     def inference_image(self, batched_inputs):
         """COCO single-image branch: MDQE.forward :213-236 -> mdqe.forward (models/mdqe.py:62-70) -> decoder
         eval branch `is_coco` (transformer_dec.py:247-255) -> MDQE.inference_image (mdqe/mdqe.py:486-556).  The pseudo clip
@@ -919,12 +965,9 @@ class MDQE(nn.Module):
         res.scores, res.pred_classes, res.pred_masks, res.pred_boxes = sc, label, pm, Boxes(boxes)
         return [{"instances": res}]
 
-    def inference_video(self, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True):
-        """mdqe/mdqe.py:430-471.  The x4 aligned-bilinear up-sampling, sigmoid, crop (:357-358), nearest resize to the
-        original size and the 0.5 threshold (:458-462) run as ONE kernel per window; windows in which an instance did not
-        exist yet stay zero (:442).  `early` (ClipMerger, CUDA): the masks of every tracked instance were already produced
-        and copied to pinned host memory window by window, under the later windows' compute; only the selection is left."""
-        from . import ops
+    def select_tracks(self, cls_clips):
+        """mdqe/mdqe.py:431-454 without the masks: the video-level class scores of every track from its per-window class rows
+        (`cls_clips`, [tracks so far, K] per window) and their top-k -> (scores [k] host tensor, labels, track index of each output)."""
         K = self.cfg.num_classes
         total = cls_clips[-1].shape[0]
         self.last_num_tracks = int(total)                      # tracks of the video just merged (diagnostics; bench.py reports it)
@@ -934,6 +977,15 @@ class MDQE(nn.Module):
         sc, ti = out_cls.topk(k, sorted=False)
         labels = (ti % K).tolist()
         inst = torch.div(ti, K, rounding_mode="floor").tolist()
+        return sc, labels, inst
+
+    def inference_video(self, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True):
+        """mdqe/mdqe.py:430-471.  The x4 aligned-bilinear up-sampling, sigmoid, crop (:357-358), nearest resize to the
+        original size and the 0.5 threshold (:458-462) run as ONE kernel per window; windows in which an instance did not
+        exist yet stay zero (:442).  `early` (ClipMerger, CUDA): the masks of every tracked instance were already produced
+        and copied to pinned host memory window by window, under the later windows' compute; only the selection is left."""
+        from . import ops
+        sc, labels, inst = self.select_tracks(cls_clips)
         sel = sorted(set(inst))
         Ho, Wo = int(image_size[0]), int(image_size[1])
         if not emit_masks:
@@ -986,9 +1038,13 @@ class ClipMerger:
     tracker_cls = OverTracker               # (tests without a GPU substitute a stand-in bank, tests/_standins.py)
     EARLY_TRACKS = 48                       # tracks per video the early-mask path budgets pinned memory for
 
-    def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True):
+    def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True, online=None):
         self.model, self.frame_hw, self.out_size, self.mask_hw = model, frame_hw, out_size, mask_hw
         self.emit_masks = emit_masks                # False: scores / labels only (ranks > 0 of a sharded video)
+        # online ("masks" | "rle"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their RLE -- of every
+        # current track are built and appended to `emitted`; neither the logits nor a host buffer stay here (n_frames is unknown)
+        self.online = online
+        self.emitted = []
         self.n_frames = n_frames                    # total frames of the video when known: enables the early mask path
         self.early = None
         # MODEL.MDQE.MERGE_ON_CPU (mdqe/mdqe.py:185-186,337,354-355; True in R50_ovis_720 / swinl_ovis): the device the window results
@@ -1067,6 +1123,9 @@ class ClipMerger:
                 m = m.contiguous()
                 if not self.emit_masks:
                     self.windows.append((self.f_off, None))
+                elif self.online:
+                    self.emitted.append(self._online_window(c, m))
+                    self.windows.append((self.f_off, None))
                 elif self.use_side and self.n_frames is not None and (self.early_on or self.model.rle_output):
                     self._early_masks(m)
                     # inference_video returns from its `early` branch and never reads `windows` then: the stride-4 logits of a flushed
@@ -1122,6 +1181,51 @@ class ClipMerger:
                 dev.record_stream(cs)
                 self.early["done"].record(cs)
         self.early["windows"].append((self.f_off, nf, n))
+
+    def _online_window(self, c, m):
+        """Online mode: the window just flushed (c: class rows [n, K] on the host, m: mean logits [n, F, Hm, Wm]) as a record --
+        frames, class rows, and the final masks of tracks 0..n-1 by the kernels of the early path: dense masks copied to a pinned host
+        buffer on the copy stream (`ready` fires when they are there), or the RLE strings of `inference_video`'s early branch."""
+        from . import ops
+        model = self.model
+        n, nf = int(m.shape[0]), int(m.shape[1])
+        Ho, Wo = int(self.out_size[0]), int(self.out_size[1])
+        ms, (fh, fw) = model.cfg.match_stride, self.frame_hw
+        rec = {"frames": (self.f_off, self.f_off + nf), "cls_probs": c, "ready": None}
+        idx = torch.arange(n, dtype=torch.int32, device=self.dev)
+        if self.online == "rle":
+            from . import rle as R
+            rles = []
+            if n:
+                cap = 4 * (Ho + Wo) + 64
+                while True:
+                    pos, n_pos = ops.final_masks_rle(m, idx, ms, fh, fw, Ho, Wo, cap)
+                    mx = int(n_pos.max())
+                    if mx <= cap:
+                        break
+                    cap = mx
+                counts, lengths = R.positions_to_counts(pos[:, :max(mx, 1)].cpu().numpy(), n_pos.cpu().numpy(), Ho * Wo)
+                strs = R.counts_to_strings(counts, lengths)
+                rles = [[{"size": [Ho, Wo], "counts": strs[i * nf + f].decode("utf-8")} for f in range(nf)] for i in range(n)]
+            rec["rles"] = rles
+            return rec
+        if not n:
+            rec["masks"] = torch.zeros((0, nf, Ho, Wo), dtype=torch.bool)
+            return rec
+        if model._copy_stream is None:
+            model._copy_stream = torch.cuda.Stream(self.dev)
+        cs = model._copy_stream
+        dev = torch.empty(n, nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
+        ops.final_masks(m, idx, ms, fh, fw, Ho, Wo, dev, 0)
+        host = model.pinned_mask_buffer((n, nf, Ho, Wo))
+        cs.wait_stream(self.side)
+        with torch.cuda.stream(cs):
+            host.copy_(dev, non_blocking=True)
+            dev.record_stream(cs)
+            rec["ready"] = torch.cuda.Event()
+            rec["ready"].record(cs)
+        rec["masks"] = host.view(torch.bool)
+        return rec
 
     def finish(self):
         if self.use_side:

@@ -1,0 +1,261 @@
+"""Online video inference: frames arrive in pushes of any size, tracker windows come back as soon as they are final.
+
+    ov = model.online_video(height=H, width=W, emit="masks", keep=False)
+    for chunk in source:                   # [n, 3, h, w] uint8 / float32, host or device, n >= 1 (n == 0: no-op)
+        for win in ov.push(chunk):         # the windows this push completed, in order
+            win.frames, win.track_ids, win.cls_probs, win.masks   # (or win.rles with emit="rle")
+    for win in ov.close():                 # the clamped last clip and the final flush
+        ...
+    res = ov.result()                      # {"image_size", "pred_scores", "pred_labels", "pred_track_ids"} (+ "pred_masks" / "pred_rles" if keep)
+
+Same clips in the same order and the same window flushes as `MDQE.forward` on the whole video (mdqe/mdqe.py:308-366), so with
+keep=True the result equals forward()'s bit for bit.  A push runs every clip whose frames are all present (the schedule's last clip,
+`end > L`, can only run at close(), when L is known); each frame goes through the per-frame stages once -- a clip that straddles two
+pushes reads the carried cache rows of the earlier frames (`_Carry`, at most T-1 frames).  What stays on the device between pushes is
+the tracker bank and the carry; the masks of a window leave for the host when it is flushed.  MERGE_ON_CPU has no meaning here (it
+only places the window results the offline merge waits on).  One GPU, one video per session.
+"""
+import contextlib
+import dataclasses
+import os
+
+import numpy as np
+import torch
+
+
+# ---- the schedule, as pure functions (tests/test_online_cpu.py drives them without a GPU) --------------------------------------------
+def push_clips(next_start, received, T, stride):
+    """The clips a push runs once `received` frames are in: every (s, s+T, False) with s = next_start, next_start + stride, ...
+    and s + T <= received.  Returns (clips, the start of the next clip)."""
+    clips, s = [], int(next_start)
+    while s + T <= received:
+        clips.append((s, s + T, False))
+        s += stride
+    return clips, s
+
+
+def close_clips(n_run, L, T, stride):
+    """The clips close() runs: those of the offline schedule (`MDQE.clip_schedule(L, T, stride)`) that no push ran -- at most the
+    clamped last one, because a push runs every clip with s + T <= frames received and `last` means s + T > L."""
+    from .meta_arch import MDQE
+    sched = MDQE.clip_schedule(L, T, stride)
+    return sched[n_run:]
+
+
+def is_flush(start, last, saved, stride, win):
+    """ClipMerger.feed_many's rule: the clip at `start` flushes tracker window `saved` (0-based)."""
+    return bool(last) or start + stride >= win * (saved + 1)
+
+
+def carry_from(next_start, received):
+    """First frame whose cache rows a later clip reads: the start of the next clip, or nothing (`received`) if it starts later."""
+    return min(int(next_start), int(received))
+
+
+def plan(push_sizes, T, stride, win):
+    """The whole online schedule of a video pushed in `push_sizes` (a final 0 stands for close()): per call, the clips it runs and the
+    windows (0-based indices) whose flush clip is among them.  Pure bookkeeping; `OnlineVideo` follows the same steps."""
+    out, nxt, received, n_run, saved = [], 0, 0, 0, 0
+    sizes = list(push_sizes)
+    for i, n in enumerate(sizes + [None]):
+        if n is None:
+            clips = close_clips(n_run, received, T, stride)
+        else:
+            received += int(n)
+            clips, nxt = push_clips(nxt, received, T, stride)
+        n_run += len(clips)
+        wins = []
+        for s, _, last in clips:
+            if is_flush(s, last, saved, stride, win):
+                wins.append(saved)
+                saved += 1
+        out.append({"clips": clips, "windows": wins, "received": received})
+    return out
+
+
+# ---- the session -----------------------------------------------------------------------------------------------------------------
+class _Carry:
+    """The cache rows (every kind of `MDQE.alloc_cache`) of the frames a later push's clips read -- at most T-1 -- kept on the device
+    between pushes: the same-process counterpart of sharding._Halo.  `head` writes them in front of the next chunk, `on_tail`
+    takes the new ones (a copy: the chunk's cache is released behind it), `tail_sent` marks that hand-over done for the chunk."""
+
+    def __init__(self):
+        self.rows, self.store, self.tail_from, self.tail_sent = 0, {}, 0, False
+
+    def head(self, ring, at):
+        for k, v in self.store.items():
+            ring[k][at:at + self.rows].copy_(v)
+
+    def on_tail(self, views):
+        self.tail_sent = True
+        self.store = {k: v.clone() for k, v in views.items()}
+        self.rows = int(next(iter(views.values())).shape[0]) if views else 0
+
+
+@dataclasses.dataclass
+class Window:
+    """One tracker window: frames [f0, f1), tracker instance index of each row, this window's class probabilities per track
+    (provisional: the video-level class is decided at close), and the final masks -- bool [n, f1-f0, H, W] on the host -- or,
+    with emit="rle", per track per frame {"size", "counts"}."""
+    frames: tuple
+    track_ids: list
+    cls_probs: torch.Tensor
+    masks: torch.Tensor = None
+    rles: list = None
+
+
+class OnlineVideo:
+    def __init__(self, model, height=None, width=None, emit="masks", keep=False):
+        if emit not in ("masks", "rle"):
+            raise ValueError("online_video: emit must be 'masks' or 'rle'")
+        if model.cfg.is_coco:
+            raise RuntimeError("online_video: a COCO image config takes the single-image branch; online inference is for videos")
+        if model.device.type != "cuda":
+            raise RuntimeError("online_video: the model must be on a HIP device (the product has no CPU path)")
+        self.model, self.emit, self.keep = model, emit, bool(keep)
+        self.height, self.width = height, width
+        cfg = model.cfg
+        self.T, self.stride, self.win = cfg.n_frames_test, cfg.clip_stride, cfg.n_frames_window_test
+        self.received, self.next_start, self.n_run = 0, 0, 0
+        self.carry = _Carry()
+        self.merger = None
+        self.in_hw = None                         # (h0, w0) of the first push: every push must match it
+        self.kept = []
+        self.closed = False
+        self._result = None
+
+    @contextlib.contextmanager
+    def _ctx(self):
+        m = self.model
+        with m._on_device(), torch.autocast(device_type="cuda", enabled=False), torch.no_grad(), m.work_stream():
+            yield
+
+    @staticmethod
+    def _hw(frames):
+        f = frames if torch.is_tensor(frames) else frames[0]
+        return int(f.shape[-2]), int(f.shape[-1])
+
+    def _start(self, frames_dev, h0, w0):
+        from .meta_arch import ClipMerger
+        model, cfg = self.model, self.model.cfg
+        h, w = int(frames_dev.shape[-2]), int(frames_dev.shape[-1])
+        self.hw = (h, w)
+        self.geo = model.engine.geometry(h, w)
+        self.out_size = (int(self.height if self.height is not None else h0), int(self.width if self.width is not None else w0))
+        self.mask_hw = (self.geo.Hp // cfg.match_stride, self.geo.Wp // cfg.match_stride)
+        self.merger = ClipMerger(model, self.hw, self.out_size, self.mask_hw, n_frames=None, online=self.emit)
+        shapes = model.engine.cache_shapes(self.geo)
+        per_frame = 4 * sum(int(np.prod(sh)) for sh in shapes.values())
+        forced = int(os.environ.get("MDQE_CACHE_FRAMES", "0"))
+        budget = forced if forced > 0 else int(model.CACHE_GB * 2 ** 30 // max(per_frame, 1))
+        self.chunk = max(1, budget - (self.T - 1))   # frames of one iter_clip_results call: chunk + carry fit one cache buffer
+
+    def _run(self, frames_dev, h2d, clips, offset):
+        """The clips of one chunk (frames_dev[0] = global frame `offset`) through iter_clip_results with the carry, fed to the
+        tracker per decoder batch as merge_clips does.  Returns the windows flushed."""
+        model, m = self.model, self.merger
+        self.carry.tail_sent = False
+        self.carry.tail_from = carry_from(self.next_start, offset + int(frames_dev.shape[0]))
+        buf, n0 = [], len(m.emitted)
+        for item in model.iter_clip_results(frames_dev, clips, offset, h2d=h2d, carry=self.carry):
+            buf.append(item)
+            if item[3].get("batch_end", True):
+                m.feed_many(buf)
+                buf = []
+        if buf:
+            m.feed_many(buf)
+        m.main.wait_stream(m.side)
+        self.n_run += len(clips)
+        return m.emitted[n0:]
+
+    def _windows(self, recs):
+        out = []
+        for r in recs:
+            if r["ready"] is not None:
+                r["ready"].synchronize()
+            n = int(r["cls_probs"].shape[0])
+            out.append(Window(frames=r["frames"], track_ids=list(range(n)), cls_probs=r["cls_probs"],
+                              masks=r.get("masks"), rles=r.get("rles")))
+        del self.merger.emitted[:]
+        if self.keep:
+            self.kept.extend(out)
+        return out
+
+    def push(self, frames):
+        """Frames [n, 3, h, w] (uint8 or float32, host or device) of the video, in order.  Runs every clip whose frames are all
+        present now and returns the windows that completed, in order."""
+        if self.closed:
+            raise RuntimeError("online_video: push() after close()")
+        n = int(frames.shape[0]) if torch.is_tensor(frames) else len(frames)
+        if n == 0:
+            return []
+        hw0 = self._hw(frames)
+        if self.in_hw is not None and hw0 != self.in_hw:
+            raise RuntimeError("online_video: frame size %s differs from the first push's %s" % (hw0, self.in_hw))
+        with self._ctx():
+            model = self.model
+            frames_dev, h2d, h0, w0 = model._frames_for({"image": frames})
+            if self.merger is None:
+                self.in_hw = hw0
+                self._start(frames_dev, h0, w0)
+            recs, r0 = [], self.received
+            if n > self.chunk and h2d:
+                torch.cuda.current_stream(model.device).wait_event(h2d[-1][1])   # (sub-chunks: the whole upload first)
+                h2d = None
+            for a in range(0, n, self.chunk):
+                b = min(n, a + self.chunk)
+                self.received = r0 + b
+                clips, self.next_start = push_clips(self.next_start, self.received, self.T, self.stride)
+                recs += self._run(frames_dev[a:b], h2d, clips, r0 + a)
+            return self._windows(recs)
+
+    def close(self):
+        """The end of the video: the clips of the offline schedule no push could run (the clamped last clip) and the final flush.
+        Returns the remaining windows."""
+        if self.closed:
+            raise RuntimeError("online_video: close() after close()")
+        if self.received == 0:
+            raise RuntimeError("online_video: close() without frames")
+        self.closed = True
+        L = self.received
+        clips = close_clips(self.n_run, L, self.T, self.stride)
+        if not clips:
+            return []
+        self.next_start = L
+        with self._ctx():
+            h, w = self.hw
+            empty = torch.empty((0, 3, h, w), dtype=torch.float32, device=self.model.device)
+            return self._windows(self._run(empty, None, clips, L))
+
+    def result(self):
+        """After close(): {"image_size", "pred_scores", "pred_labels", "pred_track_ids"} -- the video-level top-k of
+        `inference_video`; pred_track_ids[j] is the track behind output j.  keep=True adds "pred_masks" (or "pred_rles"),
+        assembled from the windows handed out, equal to forward()'s."""
+        if not self.closed:
+            raise RuntimeError("online_video: result() before close()")
+        if self._result is not None:
+            return self._result
+        if not self.merger.cls_clips:
+            raise RuntimeError("online_video: no tracker window was flushed (the schedule of this length has no last clip)")
+        sc, labels, inst = self.model.select_tracks(self.merger.cls_clips)
+        Ho, Wo = self.out_size
+        res = {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels, "pred_track_ids": list(inst)}
+        if self.keep:
+            sel = sorted(set(inst))
+            if self.emit == "rle":
+                from . import rle as R
+                empty = {"size": [Ho, Wo], "counts": R.counts_to_strings([Ho * Wo], [1])[0].decode("utf-8")}
+                per = {i: [] for i in sel}
+                for w in self.kept:
+                    nf = w.frames[1] - w.frames[0]
+                    for i in sel:            # before a track's first window: empty masks (mdqe/mdqe.py:442)
+                        per[i] += w.rles[i] if i < len(w.rles) else [dict(empty) for _ in range(nf)]
+                res["pred_rles"] = [per[i] for i in inst]
+            else:
+                per = {}
+                for i in sel:
+                    per[i] = torch.cat([w.masks[i] if i < w.masks.shape[0] else
+                                        torch.zeros((w.frames[1] - w.frames[0], Ho, Wo), dtype=torch.bool) for w in self.kept])
+                res["pred_masks"] = [per[i] for i in inst]
+        self._result = res
+        return res
