@@ -258,7 +258,7 @@ extern "C" int mdqe_time_fuse_f32(const float* w, const float* x, int Bc, int T,
 // box_head_refine: the LAST layer of the box head (Linear(C -> 4), transformer_dec.py:492-493 `bbox_embed`) + the iterative
 // refinement sigmoid(delta + inverse_sigmoid(prev)) of every frame of a (clip, query) + the clip-circumscribed box (:473-480,
 // :496-503) in ONE kernel: one wave per (clip, query) walks its T rows of the head's hidden activation; a lane takes 4 consecutive k
-// of a row, the four weight rows come from L1, xor-shuffle sums -- the arithmetic of rows_dot_kernel<4> (gemm.hip) followed by the
+// of a row, the four weight rows come from L1, xor-shuffle sums -- the arithmetic of rows_dot_kernel<4> (gemm_api.hip) followed by the
 // arithmetic of box_refine_kernel, bit for bit, so the fused and the two-kernel forms are interchangeable.
 __global__ void __launch_bounds__(256)
 box_head_refine_kernel(const float* __restrict__ h, long ldh, const float* __restrict__ W, const float* __restrict__ bias,

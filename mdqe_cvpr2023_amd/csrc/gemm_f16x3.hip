@@ -12,8 +12,7 @@
 // zero fill for padding/K tail) -> split in registers (VALU, overlapped with the MFMAs of the previous
 // K-step) -> LDS as two f16 planes (64-B rows, 16-B chunks XOR-swizzled by (row>>2)&3: conflict-free
 // ds_read_b128) -> MFMA.  Same tile order, epilogue and conv addressing as gemm.hip.
-#include "common.h"
-#include "gemm_params.h"
+#include "gemm_device.h"
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -42,11 +41,7 @@ gemm_nt_f16x3_kernel(const GemmParams p) {
 
   const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
   const int nblk = nbm * nbn;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk / 8, r = nblk % 8, xcd = bid % 8, i = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
+  const int bid = gemm_xcd_tile(blockIdx.x, nblk);
   const int bm = bid / nbn, bn = bid % nbn;
   const int m0 = bm * BM, n0 = bn * BN;
 
@@ -63,9 +58,7 @@ gemm_nt_f16x3_kernel(const GemmParams p) {
     if (irow < BM) {
       int m = m0 + irow; if (m > p.M - 1) m = p.M - 1;
       if (p.conv) {
-        const int ow = m % p.OW; const int t = m / p.OW; const int oh = t % p.OH; const int img = t / p.OH;
-        ih0[j] = oh * p.stride - p.pad; iw0[j] = ow * p.stride - p.pad;
-        rowoff[j] = (unsigned)(((long)img * p.img_stride + ((long)ih0[j] * p.Wd + iw0[j]) * p.Cin) * 4);
+        rowoff[j] = gemm_conv_row(p, m, ih0[j], iw0[j]);
       } else {
         rowoff[j] = (unsigned)((long)m * p.lda * 4);
       }
@@ -78,20 +71,15 @@ gemm_nt_f16x3_kernel(const GemmParams p) {
   f32x4 stg[NLD];
   auto load_regs = [&](int kt) {
     const int k0 = kt * BK;
-    int tap_off = 0, kh = 0, kw = 0;
-    if (p.conv) {
-      const int tap = k0 / p.Cin; const int cin0 = k0 - tap * p.Cin; kh = tap / p.KW; kw = tap - kh * p.KW;
-      tap_off = ((kh * p.Wd + kw) * p.Cin + cin0) * 4;
-    }
+    int tap_off = 0, kh = 0, kw = 0, cin0 = 0;
+    if (p.conv) { gemm_tap_seek(p, k0, kh, kw, cin0); tap_off = gemm_tap_bytes(p, kh, kw, cin0); }
     const int kk = k0 + q8 * 4;
 #pragma unroll
     for (int j = 0; j < NLD; ++j) {
       const bool isA = (j * RPP) < BM;          // compile-time per j (RPP divides BM)
       unsigned off;
       if (isA && p.conv) {
-        const int ih = ih0[j] + kh, iw = iw0[j] + kw;
-        const bool ok = (ih >= 0) && (ih < p.H) && (iw >= 0) && (iw < p.Wd);
-        off = ok ? rowoff[j] + (unsigned)tap_off + (unsigned)(q8 * 16) : OOB_OFF;
+        off = gemm_tap_addr(p, ih0[j] + kh, iw0[j] + kw, rowoff[j] + (unsigned)(q8 * 16), tap_off);
       } else {
         off = kk < p.K ? rowoff[j] + (unsigned)(kk * 4) : OOB_OFF;
       }
@@ -166,7 +154,7 @@ gemm_nt_f16x3_kernel(const GemmParams p) {
     __syncthreads();
   }
 
-  // ---- epilogue (as gemm.hip): restage the fp32 tile through LDS, float4 per lane -----------------
+  // ---- epilogue (as gemm.hip): restage the fp32 tile through LDS for gemm_tile_out --------------------
   float* sC = lds_f;
 #pragma unroll
   for (int i = 0; i < MT; ++i)
@@ -174,67 +162,12 @@ gemm_nt_f16x3_kernel(const GemmParams p) {
     for (int j = 0; j < NT; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = wm * (BM / WM) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int row = wm * (BM / WM) + i * 32 + gemm_acc_row(r, lh);
         const int col = wn * (BN / WN) + j * 32 + lr;
         sC[row * BN + col] = acc[i][j][r] + acx[i][j][r] * (1.0f / 2048.f);
       }
   __syncthreads();
-  constexpr int C4 = BN / 4;
-  constexpr int NV = BM * C4 / NT_;
-  if (p.ksplit > 1) {
-    float* w = p.ws + (long)blockIdx.y * p.M * p.N;
-    for (int it = 0; it < NV; ++it) {
-      const int idx = it * NT_ + tid;
-      const int row = idx / C4, c4 = idx - row * C4;
-      const int m = m0 + row, n = n0 + c4 * 4;
-      if (m >= p.M) continue;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (n + e < p.N) w[(long)m * p.N + n + e] = sC[row * BN + c4 * 4 + e];
-    }
-    return;
-  }
-  const bool vec = p.vec_ok;
-  int rr0 = 0;
-  if (p.residual != nullptr && p.res_mod > 0) rr0 = m0 % p.res_mod;
-#pragma unroll 4
-  for (int it = 0; it < NV; ++it) {
-    const int idx = it * NT_ + tid;
-    const int row = idx / C4, c4 = idx - row * C4;
-    const int m = m0 + row, n = n0 + c4 * 4;
-    if (m >= p.M || n >= p.N) continue;
-    f32x4 v = *reinterpret_cast<const f32x4*>(sC + row * BN + c4 * 4);
-    const bool full = vec && (n + 3 < p.N);
-    long rrow = m;
-    if (p.res_mod > 0) { int t = rr0 + row; while (t >= p.res_mod) t -= p.res_mod; rrow = t; }
-    const bool masked = p.rowmask != nullptr && p.rowmask[m];
-    if (full) {
-      if (p.bias != nullptr) v += *reinterpret_cast<const f32x4*>(p.bias + n);
-      f32x4 rv = {0.f, 0.f, 0.f, 0.f};
-      if (p.residual != nullptr) rv = *reinterpret_cast<const f32x4*>(p.residual + rrow * p.ldr + n);
-      if (p.res_first) v += rv;
-      mdqe_act4(v, p.act, [&](int e) { return p.act_cols <= 0 || n + e < p.act_cols; });
-      if (!p.res_first) v += rv;
-      if (masked) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (n + e < p.mask_cols) v[e] = 0.f;
-      }
-      *reinterpret_cast<f32x4*>(p.C + (long)m * p.ldc + n) = v;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (n + e >= p.N) break;
-        float x = v[e] + (p.bias != nullptr ? p.bias[n + e] : 0.f);
-        const float rv = p.residual != nullptr ? p.residual[rrow * p.ldr + n + e] : 0.f;
-        if (p.res_first) x += rv;
-        if (p.act != MDQE_ACT_NONE && (p.act_cols <= 0 || n + e < p.act_cols)) x = mdqe_act(x, p.act);
-        if (!p.res_first) x += rv;
-        if (masked && n + e < p.mask_cols) x = 0.f;
-        p.C[(long)m * p.ldc + n + e] = x;
-      }
-    }
-  }
+  gemm_tile_out<BM, BN, NT_, 4>(p, sC, m0, n0, tid);
 }
 
 template <int BM, int BN>
@@ -243,11 +176,7 @@ static int launch_f16x3(const GemmParams& p, hipStream_t st) {
   size_t smem = (size_t)2 * 2 * (BM + BN) * 32 * sizeof(_Float16);     // 2 stages x (hi, lo) planes
   if (smem < (size_t)BM * BN * sizeof(float)) smem = (size_t)BM * BN * sizeof(float);
   auto kern = gemm_nt_f16x3_kernel<BM, BN, 2, 2>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
+  if (smem > 64 * 1024 && mdqe_allow_lds(reinterpret_cast<const void*>(kern), (int)smem) != hipSuccess) return MDQE_ELAUNCH;
   hipLaunchKernelGGL(kern, dim3(nbm * nbn, p.ksplit > 1 ? p.ksplit : 1), dim3(256), smem, st, p);
   return mdqe_launch_status();
 }

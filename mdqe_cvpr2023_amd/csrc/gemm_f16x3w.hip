@@ -17,8 +17,7 @@
 //   * the epilogue restages each wave's 32 x (BN/4) half tile through its OWN LDS slice (no block
 //     barrier), then bias / residual / activation / mask and 16-B stores as in gemm.hip.
 // Tile order, conv addressing, split-K and the epilogue semantics are those of gemm.hip.  K % 32 == 0.
-#include "common.h"
-#include "gemm_params.h"
+#include "gemm_device.h"
 #include <type_traits>
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -88,11 +87,8 @@ gemm_nt_f16x3w_kernel(const GemmParams p) {
   const int G = gridDim.x;
   const int my_tiles = (ntiles - (int)blockIdx.x + G - 1) / G;        // >= 1 (G <= ntiles)
   const int total = my_tiles * nk;
-  const int xq = ntiles / 8, xr = ntiles % 8;
-  auto tile_mn = [&](int it, int& m0, int& n0) __attribute__((always_inline)) {                       // XCD-aware order: an XCD owns a contiguous tile range
-    int v = (int)blockIdx.x + it * G;
-    const int xcd = v % 8, i = v / 8;
-    v = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + i;
+  auto tile_mn = [&](int it, int& m0, int& n0) __attribute__((always_inline)) {
+    const int v = gemm_xcd_tile((int)blockIdx.x + it * G, ntiles);
     const int bm = v / nbn;
     m0 = bm * BM; n0 = (v - bm * nbn) * BN;
   };
@@ -115,9 +111,7 @@ gemm_nt_f16x3w_kernel(const GemmParams p) {
       int m = m0 + j * 64 + (tid >> 3); if (m > p.M - 1) m = p.M - 1;
       ih0[j] = 0; iw0[j] = 0;
       if (CONV) {
-        const int ow = m % p.OW; const int t = m / p.OW; const int oh = t % p.OH; const int img = t / p.OH;
-        ih0[j] = oh * p.stride - p.pad; iw0[j] = ow * p.stride - p.pad;
-        arow[j] = (unsigned)(((long)img * p.img_stride + ((long)ih0[j] * p.Wd + iw0[j]) * p.Cin) * 4) + (unsigned)(q8 * 16);
+        arow[j] = gemm_conv_row(p, m, ih0[j], iw0[j]) + (unsigned)(q8 * 16);
       } else {
         arow[j] = (unsigned)((long)m * p.lda * 4) + (unsigned)(q8 * 16);
       }
@@ -141,9 +135,10 @@ gemm_nt_f16x3w_kernel(const GemmParams p) {
   auto load_a = [&](auto slot_) __attribute__((always_inline)) {        // loads the K-step under the A cursor, then advances it (parks on the last one at the end)
     constexpr int slot = decltype(slot_)::value;
     if (CONV) {
-      const int tap_off = ((t_kh * p.Wd + t_kw) * p.Cin + t_c) * 4;
+      const int tap_off = gemm_tap_bytes(p, t_kh, t_kw, t_c);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
+        // (gemm_tap_addr's test written out: through the helper this kernel's register allocation comes out 4 VGPRs wider)
         const int ih = ih0[j] + t_kh, iw = iw0[j] + t_kw;
         const bool ok = (ih >= 0) && (ih < p.H) && (iw >= 0) && (iw < p.Wd);
         const unsigned off = ok ? arow[j] + (unsigned)tap_off : OOB_OFF;
@@ -159,7 +154,7 @@ gemm_nt_f16x3w_kernel(const GemmParams p) {
     }
     if (ktA + 1 < nk) {
       ++ktA;
-      if (CONV) { t_c += BK; if (t_c >= p.Cin) { t_c = 0; if (++t_kw == p.KW) { t_kw = 0; ++t_kh; } } }
+      if (CONV) gemm_tap_advance(p, BK, t_kh, t_kw, t_c);
     } else if (itA + 1 < my_tiles) {
       ktA = 0; ++itA; setup_a(itA);
     }
@@ -221,7 +216,7 @@ gemm_nt_f16x3w_kernel(const GemmParams p) {
   zero_acc();
 
   // ---- epilogue of tile `it` (registers -> global, no LDS): lane owns row m = .. + lr and, per accumulator quad g,
-  //      columns n .. n+3 with n = .. + 8g + 4*lh ------------------------------------------------------------------------
+  //      columns n .. n+3 with n = .. + gemm_acc_row(4g, lh) (operands swapped: the accumulator's rows are C's columns) -------
   auto epilogue = [&](int it) __attribute__((always_inline)) {
     int m0, n0; tile_mn(it, m0, n0);
     const float inv = 1.0f / 2048.f;
@@ -235,23 +230,12 @@ gemm_nt_f16x3w_kernel(const GemmParams p) {
       for (int j = 0; j < NT; ++j)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          const int n = n0 + wn * WTN + j * 32 + 8 * g + 4 * lh;
+          const int n = n0 + wn * WTN + j * 32 + gemm_acc_row(4 * g, lh);
           if (!mok || n >= p.N) continue;
           f32x4 v;
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = SINGLE ? acc[i][j][4 * g + e] : acc[i][j][4 * g + e] + acx[i][j][4 * g + e] * inv;
-          if (p.bias != nullptr) v += *reinterpret_cast<const f32x4*>(p.bias + n);
-          f32x4 rv = {0.f, 0.f, 0.f, 0.f};
-          if (p.residual != nullptr) rv = *reinterpret_cast<const f32x4*>(p.residual + rrow * p.ldr + n);
-          if (p.res_first) v += rv;
-          mdqe_act4(v, p.act, [&](int e) { return p.act_cols <= 0 || n + e < p.act_cols; });
-          if (!p.res_first) v += rv;
-          if (masked) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (n + e < p.mask_cols) v[e] = 0.f;
-          }
-          *reinterpret_cast<f32x4*>(p.C + (long)m * p.ldc + n) = v;
+          *reinterpret_cast<f32x4*>(p.C + (long)m * p.ldc + n) = gemm_epilogue4<false>(p, v, m, n, rrow, masked);
         }
     }
   };
@@ -381,11 +365,7 @@ static int launch_f16x3w(const GemmParams& p, hipStream_t st) {
   const int nbm = (p.M + 127) / 128, nbn = (p.N + BN - 1) / BN;
   const size_t smem = (size_t)3 * (SINGLE ? 1 : 2) * (128 * 32 * 2 + BN * 32 * 2);       // 3 stages x (A hi[, A lo], B hi[, B lo])
   auto kern = gemm_nt_f16x3w_kernel<BN, CONV, SINGLE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
+  if (smem > 64 * 1024 && mdqe_allow_lds(reinterpret_cast<const void*>(kern), (int)smem) != hipSuccess) return MDQE_ELAUNCH;
   if (g_num_cus == 0) {
     int dev = 0, n = 0;
     (void)hipGetDevice(&dev);

@@ -15,8 +15,7 @@
 // immediate) with the ragged-K check behind a uniform branch; interior tiles of plain products on a few-instruction epilogue (buffer
 // addressing with scalar offsets, one specialised copy per form behind uniform branches); the LayerNorm epilogue on buffer resources
 // whose range check replaces the row guards.  Uniform conditions are branches, never selects.
-#include "common.h"
-#include "gemm_params.h"
+#include "gemm_device.h"
 #include <type_traits>
 
 // NS = LDS stages.  2 (one K-step of look-ahead) is the default: several blocks share a SIMD and one block's load latency hides
@@ -64,11 +63,7 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
   const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
   const int nblk = nbm * nbn;
   const int nall = p.planes > 1 ? nblk * p.planes : nblk;
-  int bid = blockIdx.x;
-  {
-    const int q = nall / 8, r = nall % 8, xcd = bid % 8, i = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-  }
+  int bid = gemm_xcd_tile(blockIdx.x, nall);
   const int plane = bid / nblk;
   bid -= plane * nblk;
   const int bm = bid / nbn, bn = bid % nbn;
@@ -95,9 +90,7 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
     if (irow < BM) {
       int m = m0 + irow; if (m > p.M - 1) m = p.M - 1;
       if (CONV) {
-        const int ow = m % p.OW; const int t = m / p.OW; const int oh = t % p.OH; const int img = t / p.OH;
-        ih0[j] = oh * p.stride - p.pad; iw0[j] = ow * p.stride - p.pad;
-        voff[j] = (unsigned)(((long)img * p.img_stride + ((long)ih0[j] * p.Wd + iw0[j]) * p.Cin) * 4) + (unsigned)(kch[j] * 4);   // may wrap
+        voff[j] = gemm_conv_row(p, m, ih0[j], iw0[j]) + (unsigned)(kch[j] * 4);
       } else if (!CAT && !LN && p.swin_ws > 0) {   // window-ordered row m -> its pixel of the [B, H, W, lda] map (or zeros)
         const int ws = p.swin_ws, nWx = (p.swin_W + ws - 1) / ws, nWy = (p.swin_H + ws - 1) / ws;
         const int ix = m % ws; int t = m / ws;
@@ -109,7 +102,8 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
       } else {
         voff[j] = (unsigned)((long)m * p.lda * 4) + (unsigned)(kch[j] * 4);
         if constexpr (CAT) {                       // the second operand's row: pixel (oh*stride, ow*stride) of image img
-          const int ow = m % p.OW; const int t = m / p.OW; const int oh = t % p.OH; const int img = t / p.OH;
+          int img, oh, ow;
+          gemm_row_pixel(p, m, img, oh, ow);
           const long r2 = ((long)img * p.H + (long)oh * p.stride) * p.Wd + (long)ow * p.stride;
           voff2[j] = (unsigned)(r2 * p.lda2 * 4) + (unsigned)(kch[j] * 4);
         }
@@ -127,23 +121,21 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
   const int kt0 = kbeg / BK;
   const int nk = (kend - kbeg + BK - 1) / BK;
   int t_kh = 0, t_kw = 0, t_c = 0;                 // conv: filter tap of the K-step about to be issued (Cin % 16 == 0)
-  if (CONV) { const int tap = kbeg / p.Cin; t_c = kbeg - tap * p.Cin; t_kh = tap / p.KW; t_kw = tap - t_kh * p.KW; }
+  if (CONV) gemm_tap_seek(p, kbeg, t_kh, t_kw, t_c);
 
   auto issue_impl = [&](int kt, int buf, auto tail_) __attribute__((always_inline)) {
     constexpr bool ktail = decltype(tail_)::value;   // the last K-step of a ragged K checks lanes against K
     const int k0 = kt * BK;
     float* base = lds + buf * (ROWS * BK);
     int tap_off = 0;
-    if (CONV) tap_off = ((t_kh * p.Wd + t_kw) * p.Cin + t_c) * 4;
+    if (CONV) tap_off = gemm_tap_bytes(p, t_kh, t_kw, t_c);
 #pragma unroll
     for (int j = 0; j < IPW; ++j) {
       const int irow0 = (wave * IPW + j) * 16;       // wave-uniform
       unsigned off = voff[j];
       if (irow0 < BM) {
         if (CONV) {
-          const int ih = ih0[j] + t_kh, iw = iw0[j] + t_kw;
-          const bool ok = (ih >= 0) && (ih < p.H) && (iw >= 0) && (iw < p.Wd);
-          off = ok ? off + (unsigned)tap_off : OOB_OFF;
+          off = gemm_tap_addr(p, ih0[j] + t_kh, iw0[j] + t_kw, off, tap_off);
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void*)(base + irow0 * BK), 16, off, 0, 0, 0);
         } else if (CAT && k0 >= p.K1) {              // (wave-uniform: K1 is a multiple of the K-step)
           off = voff2[j];
@@ -158,7 +150,7 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (__attribute__((address_space(3))) void*)(base + irow0 * BK), 16, off, k0 * 4, 0, 0);
       }
     }
-    if (CONV) { t_c += BK; if (t_c >= p.Cin) { t_c = 0; if (++t_kw == p.KW) { t_kw = 0; ++t_kh; } } }
+    if (CONV) gemm_tap_advance(p, BK, t_kh, t_kw, t_c);
   };
   // Two copies behind a UNIFORM branch: folded into one, the ragged-K check is a compare + select per LDS-DMA address in EVERY step,
   // and every vector instruction of this loop is matrix-pipe time (the f32 MFMA runs at the vector rate).  The empty asm keeps the
@@ -193,14 +185,9 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
   for (int s = 0; s < NS - 1; ++s)
     if (s < nk) issue(kt0 + s, s);
   if (p.stamps) t_pro = wall_clock64();
-  // One K-step on LDS stage S (compile-time: the fragment reads of a stage are then `base register + immediate`, where a run-time
-  // stage costs one vector add per fragment address per step).
-  auto kstep2 = [&](int kt, auto S_) __attribute__((always_inline)) {
-    constexpr int S = decltype(S_)::value;
-    wait_vmcnt<0>();
-    __syncthreads();
-    if (kt + 1 < nk) issue(kt0 + kt + 1, S ^ 1);
-    const float* sI = lds + S * (ROWS * BK);
+  // The arithmetic of one K-step on the LDS stage at sI: both 8-wide halves' fragments up front (the second hides behind the first
+  // 16 MFMAs), then 2 x 16 MFMAs.
+  auto mma_stage = [&](const float* sI) __attribute__((always_inline)) {
     f32x4 a0[MT], b0[NT], a1[MT], b1[NT];
 #pragma unroll
     for (int i = 0; i < MT; ++i) a0[i] = *reinterpret_cast<const f32x4*>(sI + fa[i]);
@@ -227,51 +214,41 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[i][s], b1[j][s], acc[i][j], 0, 0, 0);
   };
   if constexpr (NS == 2) {
+    // One K-step on LDS stage S (compile-time: the fragment reads of a stage are then `base register + immediate`, where a run-time
+    // stage costs one vector add per fragment address per step).
+    auto kstep2 = [&](int kt, auto S_) __attribute__((always_inline)) {
+      constexpr int S = decltype(S_)::value;
+      wait_vmcnt<0>();                                 // this wave's LDS-DMA for step kt has landed
+      __syncthreads();                                 // ... and everybody else's; all reads of the buffer refilled next are done
+      if (kt + 1 < nk) issue(kt0 + kt + 1, S ^ 1);
+      mma_stage(lds + S * (ROWS * BK));
+    };
     for (int kt = 0; kt < nk; kt += 2) {
       kstep2(kt, std::integral_constant<int, 0>{});
       if (kt + 1 < nk) kstep2(kt + 1, std::integral_constant<int, 1>{});
     }
-  } else
-  for (int kt = 0; kt < nk; ++kt) {
-    // this wave's LDS-DMA for step kt has landed: at most the loads of the stages issued after it may still be in flight
-    if constexpr (NS == 2) {
-      wait_vmcnt<0>();
-    } else if constexpr (NS == 3) {
-      if (nk - 1 - kt >= 1) wait_vmcnt<IPW>(); else wait_vmcnt<0>();     // step kt + 1 may still be in flight
-    } else {
-      const int behind = nk - 1 - kt;                  // stages already issued behind step kt: min(NS - 2, behind)
-      if (behind >= 2) wait_vmcnt<2 * IPW>(); else if (behind == 1) wait_vmcnt<IPW>(); else wait_vmcnt<0>();
+  } else {
+    for (int kt = 0; kt < nk; ++kt) {
+      // at most the loads of the stages issued after step kt may still be in flight: min(NS - 2, steps left behind kt) of them
+      const int behind = nk - 1 - kt;
+      if (NS > 3 && behind >= 2) wait_vmcnt<2 * IPW>(); else if (behind >= 1) wait_vmcnt<IPW>(); else wait_vmcnt<0>();
+      __syncthreads();
+      if (kt + NS - 1 < nk) issue(kt0 + kt + NS - 1, (kt + NS - 1) % NS);
+      mma_stage(lds + (kt % NS) * (ROWS * BK));
     }
-    __syncthreads();                                   // ... and everybody else's; all reads of the buffer refilled next are done
-    if (kt + NS - 1 < nk) issue(kt0 + kt + NS - 1, (kt + NS - 1) % NS);
-    const float* sI = lds + (kt % NS) * (ROWS * BK);
-    f32x4 a0[MT], b0[NT], a1[MT], b1[NT];              // both 8-wide halves up front: the second hides behind 16 MFMAs
-#pragma unroll
-    for (int i = 0; i < MT; ++i) a0[i] = *reinterpret_cast<const f32x4*>(sI + fa[i]);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) b0[j] = *reinterpret_cast<const f32x4*>(sI + fb[j]);
-#pragma unroll
-    for (int i = 0; i < MT; ++i) a1[i] = *reinterpret_cast<const f32x4*>(sI + (fa[i] ^ 8));
-#pragma unroll
-    for (int j = 0; j < NT; ++j) b1[j] = *reinterpret_cast<const f32x4*>(sI + (fb[j] ^ 8));
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[i][s], b0[j][s], acc[i][j], 0, 0, 0);
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[i][s], b1[j][s], acc[i][j], 0, 0, 0);
   }
 
   if (p.stamps) t_loop = wall_clock64();
+  // Every epilogue restages one 32x32 sub-tile at a time through the wave's own 4-KB LDS slice (no block barrier): a[r] is
+  // C(row = gemm_acc_row(r, lh), col = lr) of the sub-tile; afterwards a lane owns 4 consecutive columns of a row and 8 lanes cover
+  // one 128-B line of C.
+  float* const sC = lds + wave * 1024;
+  auto restage = [&](const f32x16& a) __attribute__((always_inline)) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sC[gemm_acc_row(r, lh) * 32 + lr] = a[r];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+  };
   if constexpr (LN) {
     // ---- LayerNorm epilogue (BN == N: the block owns whole rows): y = LN(acc + bias + residual) * gamma + beta.
     // Sub-tiles are restaged as below (a lane gets 4 consecutive columns of 4 rows per sub-tile) but stay in registers;
@@ -279,7 +256,6 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
     // squares) as in layernorm_kernel.  C may alias the residual: a wave only rewrites the elements it read.
     static_assert(!LN || (WM == 1 && BN == 256), "LN epilogue: one wave row, 256 columns");
     __syncthreads();
-    float* sC = lds + wave * 1024;
     float* red1 = lds + NW * 1024;
     float* red2 = red1 + NW * BM;
     f32x4 vv[MT][NT][4];
@@ -299,10 +275,7 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
     const unsigned vR = (unsigned)((rsub * p.ldr + c4 * 4) * 4), vC = (unsigned)((rsub * p.ldc + c4 * 4) * 4);
     auto stage = [&](auto i_, auto j_) __attribute__((always_inline)) {
       constexpr int i = decltype(i_)::value, j = decltype(j_)::value;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sC[((r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + lr] = acc[i][j][r];
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
+      restage(acc[i][j]);
       const int n = wn * 64 + j * 32 + c4 * 4;
       const f32x4 bv = p.bias != nullptr ? *reinterpret_cast<const f32x4*>(p.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -438,11 +411,8 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
     return;
   }
 
-  // ---- epilogue: per-wave restage of one 32x32 sub-tile at a time through the wave's own 4-KB LDS slice ----------------
-  // acc[i][j][r] is C(row = (r&3) + 8*(r>>2) + 4*lh, col = lr) of the sub-tile; after the restage a lane owns 4 consecutive
-  // columns of a row and 8 lanes cover one 128-B line of C.
+  // ---- epilogue ------------------------------------------------------------------------------------------------------
   __syncthreads();                                   // every wave is done reading the last K-step
-  float* sC = lds + wave * 1024;
   const bool vec = p.vec_ok;
 
   // ---- fast path (round 4): an interior tile of a plain product -- bias, none / ReLU / GELU on every column, optional full residual.
@@ -508,10 +478,7 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
         auto fsub = [&](auto i_, auto j_, auto s_) __attribute__((always_inline)) {
           constexpr int i = decltype(i_)::value, j = decltype(j_)::value, sidx = decltype(s_)::value;
           constexpr int nsub = MT * NT;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sC[((r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + lr] = acc[i][j][r];
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_wave_barrier();
+          restage(acc[i][j]);
           if constexpr (RES && sidx + 1 < nsub) {        // the next sub-tile's residual rows, BEFORE this one's stores
             constexpr int s1 = sidx + 1;
             constexpr int i1 = (NT > 1) ? s1 / NT : s1, j1 = (NT > 1) ? s1 % NT : 0;
@@ -592,10 +559,7 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
   }
   auto sub = [&](auto i_, auto j_) __attribute__((always_inline)) {
       constexpr int i = decltype(i_)::value, j = decltype(j_)::value;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sC[((r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + lr] = acc[i][j][r];
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
+      restage(acc[i][j]);
       // (rolled, round 4: the body -- bias, side term, residual, activation, mask, the ragged-edge path -- is long, and sixteen unrolled
       // copies of it per kernel made the epilogue an instruction-cache problem)
 #pragma unroll 1
@@ -615,26 +579,7 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
         const long rrow = p.res_mod > 0 ? (m % p.res_mod) : m;
         const bool masked = p.rowmask != nullptr && p.rowmask[m];
         if (vec && (n + 3 < p.N)) {
-          if (p.bias != nullptr) v += *reinterpret_cast<const f32x4*>(p.bias + n);
-          if (p.side != nullptr && n < p.side_cols) {        // rank-4 side term (side_cols % 4 == 0)
-            const f32x4 s4 = *reinterpret_cast<const f32x4*>(p.side + (long)m * 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const f32x4 w4 = *reinterpret_cast<const f32x4*>(p.side_w + (long)(n + e) * 4);
-              v[e] += (s4[0] * w4[0] + s4[1] * w4[1]) + (s4[2] * w4[2] + s4[3] * w4[3]);
-            }
-          }
-          f32x4 rv = {0.f, 0.f, 0.f, 0.f};
-          if (p.residual != nullptr) rv = *reinterpret_cast<const f32x4*>(p.residual + rrow * p.ldr + n);
-          if (p.res_first) v += rv;
-          mdqe_act4(v, p.act, [&](int e) { return p.act_cols <= 0 || n + e < p.act_cols; });
-          if (!p.res_first) v += rv;
-          if (masked) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (n + e < p.mask_cols) v[e] = 0.f;
-          }
-          *reinterpret_cast<f32x4*>(pC + (long)m * p.ldc + n) = v;
+          *reinterpret_cast<f32x4*>(pC + (long)m * p.ldc + n) = gemm_epilogue4<true>(p, v, m, n, rrow, masked);
         } else {
           // ragged edge / unaligned operands: element by element, ROLLED (the vector rotates through the loop so that no register is
           // indexed dynamically) -- the generic activation switch, tanhf included, appears once here instead of four times
@@ -643,17 +588,7 @@ gemm_nt_f32_k16_kernel(const GemmParams p) {
             if (n + e >= p.N) break;
             const float ve = v[0];
             v = f32x4{v[1], v[2], v[3], ve};
-            float x = ve + (p.bias != nullptr ? p.bias[n + e] : 0.f);
-            if (p.side != nullptr && n + e < p.side_cols) {
-              const float* s4 = p.side + (long)m * 4; const float* w4 = p.side_w + (long)(n + e) * 4;
-              x += (s4[0] * w4[0] + s4[1] * w4[1]) + (s4[2] * w4[2] + s4[3] * w4[3]);
-            }
-            const float rv = p.residual != nullptr ? p.residual[rrow * p.ldr + n + e] : 0.f;
-            if (p.res_first) x += rv;
-            if (p.act != MDQE_ACT_NONE && (p.act_cols <= 0 || n + e < p.act_cols)) x = mdqe_act(x, p.act);
-            if (!p.res_first) x += rv;
-            if (masked && n + e < p.mask_cols) x = 0.f;
-            pC[(long)m * p.ldc + n + e] = x;
+            pC[(long)m * p.ldc + n + e] = gemm_epilogue1<true>(p, ve, m, n + e, rrow, masked);
           }
         }
       }
@@ -706,11 +641,9 @@ static int launch_k16_(const GemmParams& p, hipStream_t st) {
     if (g_k16_stages == 3) return launch_k16_ns_<BM, BN, WM, WN, CONV, LN, 3>(p, st);
   }
   if constexpr (!LN && BM * BN <= 64 * 64) {
-    // small tiles on a small grid (about one block per CU or less per SIMD wave slot): deep look-ahead
-    const long blocks = (long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * (p.ksplit > 1 ? p.ksplit : 1);
-    // measured (tools/gemm_stages_ab.py, r02): no gain -- 14.8 vs 14.9 us on [5292,256]x[256,256], 10 us even for 16 blocks: the
-    // floor of these launches is not the look-ahead depth.  Kept as a measured alternative behind the debug switch.
-    (void)blocks;
+    // small tiles on a small grid (about one block per CU or less per SIMD wave slot): deep look-ahead.  Measured
+    // (tools/gemm_stages_ab.py, r02): no gain -- 14.8 vs 14.9 us on [5292,256]x[256,256], 10 us even for 16 blocks: the floor of
+    // these launches is not the look-ahead depth.  Kept as a measured alternative behind the debug switch.
     if (g_k16_stages == 4) return launch_k16_ns_<BM, BN, WM, WN, CONV, LN, 4>(p, st);
   }
   return launch_k16_ns_<BM, BN, WM, WN, CONV, LN, 2>(p, st);

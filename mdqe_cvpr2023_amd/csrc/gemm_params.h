@@ -1,4 +1,5 @@
-// Shared parameter block of the GEMM kernels (gemm.hip, gemm_f16x3.hip).
+// Shared parameter block of the GEMM kernels (gemm.hip, gemm_k16.hip, gemm_f16x3.hip, gemm_f16x3w.hip) and the launchers
+// through which the front door (gemm_api.hip) reaches them.  The kernels' shared device code is in gemm_device.h.
 #pragma once
 struct GemmParams {
   const float* A; const float* W; float* C;
@@ -44,9 +45,12 @@ struct GemmParams {
 
 #define OOB_OFF 0xFFFFFFF0u
 
+// Every launcher launches its kernel only: the caller follows a split-K launch with the reduce pass (gemm_api.hip finish_splitk).
+// defined in gemm.hip (K-step 32; tile 1 128x128, 2 128x64, 3 64x64)
+int mdqe_launch_gemm_k32(const GemmParams& p, int tile, hipStream_t st);
 // defined in gemm_f16x3.hip
 int mdqe_launch_gemm_f16x3(const GemmParams& p, int tile, hipStream_t st);
-// defined in gemm_k16.hip (tile 1/2/3 as gemm.hip; the caller launches the split-K reduce pass)
+// defined in gemm_k16.hip (tile 1/2/3 as gemm.hip, and its own 4-9)
 int mdqe_launch_gemm_k16(const GemmParams& p, int tile, hipStream_t st);
 // defined in gemm_f16x3w.hip (bn = 256 or 128)
 int mdqe_launch_gemm_f16x3w(const GemmParams& p, int bn, hipStream_t st);
