@@ -440,6 +440,19 @@ int mdqe_final_masks_u8(const float* logits, int n_sel, const int* inst_idx_dev,
 int mdqe_final_masks_rle(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
                          int h, int w, int Ho, int Wo, int cap, int* pos, int* n_pos, void* stream);
 
+/* The same two sweeps with the geometry of every final mask gathered on the way -- what a consumer otherwise gets from the masks on
+ * the host (pycocotools area / toBbox, mdqe/data/pycocotools/mask.py:93-101; BitMasks.get_bounding_boxes, mdqe/mdqe.py:554; the
+ * visualiser's per-frame pass, demo/clip/visualizer_from_json.py:94-103; the `bboxes` / `areas` the YTVIS loader requires per frame,
+ * mdqe/data/datasets/ytvis.py:280-290).  geom int32 [n_sel*Fw, 5]: row k*Fw+f = (area, xmin, ymin, xmax, ymax) of the set pixels of
+ * (selected row k, window frame f) in output pixels, inclusive; an empty mask has area 0 and xmin = Wo > xmax = -1, ymin = Ho > ymax
+ * = -1 (as mdqe_image_mask_stats_f32).  out / pos / n_pos exactly as the entry points above write them (one definition of the bit);
+ * geom is fully overwritten on every call (no pre-initialisation), integers, identical from run to run; (long)Ho*Wo < 2^31. */
+int mdqe_final_masks_u8_geom(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
+                             int h, int w, int Ho, int Wo, unsigned char* out, long out_inst_stride, int f_off,
+                             int* geom, void* stream);
+int mdqe_final_masks_rle_geom(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
+                              int h, int w, int Ho, int Wo, int cap, int* pos, int* n_pos, int* geom, void* stream);
+
 /* ---- COCO single-image branch, after the decoder (MDQE.inference_image, mdqe/mdqe.py:486-556), on the centre frame's
  * low-resolution logits [n,Hm,Wm]; aligned_bilinear x`factor` in closed form, crop [:h,:w].
  * stats[k] = {sum(sigmoid*[sigmoid>0.5]), count(sigmoid>0.5), xmin, ymin, xmax, ymax of (logit > 0)} (:512-516, :526;

@@ -437,3 +437,169 @@ extern "C" int mdqe_final_masks_u8(const float* logits, int n_sel, const int* in
                      Wo, out, out_inst_stride, f_off, inst_idx_dev, total);
   return mdqe_launch_status();
 }
+
+// ------------------------------------------------------------------------------------------------
+// Geometry of the final masks in the sweep that decides them: per (selected row k, window frame f) the number of set
+// pixels and their tight box, geom[k*Fw+f] = (area, xmin, ymin, xmax, ymax) in output pixels, inclusive; an empty mask
+// is (0, Wo, Ho, -1, -1) (xmin > xmax, ymin > ymax: the convention of image_mask_stats).  What pycocotools' area /
+// toBbox (mdqe/data/pycocotools/mask.py:93-101) and d2's BitMasks.get_bounding_boxes (mdqe/mdqe.py:554) compute on the
+// host from the masks.  Every bit comes from final_mask_pixel, so masks and geometry cannot disagree.  All integer:
+// the result does not depend on the order in which blocks finish.
+// ------------------------------------------------------------------------------------------------
+struct MaskGeom { int cnt, x0, y0, x1, y1; };
+
+__device__ __forceinline__ void geom_add(MaskGeom& g, int v, int Y, int X) {
+  g.cnt += v;
+  g.x0 = v ? min(g.x0, X) : g.x0; g.x1 = v ? max(g.x1, X) : g.x1;
+  g.y0 = v ? min(g.y0, Y) : g.y0; g.y1 = v ? max(g.y1, Y) : g.y1;
+}
+
+// 256 threads: registers -> wave (__shfl_xor over 64 lanes) -> the 4 waves through red[20]; the total is valid in thread 0
+__device__ __forceinline__ MaskGeom geom_block_reduce(MaskGeom g, int* red) {
+  for (int o = 32; o > 0; o >>= 1) {
+    g.cnt += __shfl_xor(g.cnt, o);
+    g.x0 = min(g.x0, __shfl_xor(g.x0, o)); g.x1 = max(g.x1, __shfl_xor(g.x1, o));
+    g.y0 = min(g.y0, __shfl_xor(g.y0, o)); g.y1 = max(g.y1, __shfl_xor(g.y1, o));
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[wave * 5 + 0] = g.cnt; red[wave * 5 + 1] = g.x0; red[wave * 5 + 2] = g.y0; red[wave * 5 + 3] = g.x1; red[wave * 5 + 4] = g.y1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int wv = 1; wv < 4; ++wv) {
+      g.cnt += red[wv * 5 + 0];
+      g.x0 = min(g.x0, red[wv * 5 + 1]); g.y0 = min(g.y0, red[wv * 5 + 2]);
+      g.x1 = max(g.x1, red[wv * 5 + 3]); g.y1 = max(g.y1, red[wv * 5 + 4]);
+    }
+  }
+  return g;
+}
+
+__global__ void __launch_bounds__(256)
+geom_init_kernel(int* __restrict__ geom, int rows, int Ho, int Wo) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < rows * 5) { const int c = i % 5; geom[i] = c == 0 ? 0 : c == 1 ? Wo : c == 2 ? Ho : -1; }
+}
+
+// Dense form.  final_mask_kernel spreads one mask over many blocks of a flat grid-stride loop; here a block owns a band of
+// `band` rows of ONE mask (blockIdx.x = mask * n_bands + band index), so all its pixels share one row of geom: one set of
+// integer atomics per block that saw a set pixel, into the row geom_init_kernel prepared.  A band is contiguous in `out`,
+// so a wave's byte stores stay contiguous as in final_mask_kernel.
+__global__ void __launch_bounds__(256)
+final_mask_geom_kernel(const float* __restrict__ lg, int Fw, int Hm, int Wm, int factor, int h, int w, int Ho, int Wo,
+                       unsigned char* __restrict__ out, long out_inst_stride, int f_off, const int* __restrict__ inst_idx,
+                       int band, int n_bands, int* __restrict__ geom) {
+  const int mask = blockIdx.x / n_bands, b = blockIdx.x - mask * n_bands;
+  const int k = mask / Fw, f = mask - k * Fw;
+  const float* m = lg + ((long)inst_idx[k] * Fw + f) * Hm * Wm;
+  const float sy_scale = (float)h / (float)Ho, sx_scale = (float)w / (float)Wo;
+  const int Y0 = b * band, rows = min(band, Ho - Y0);
+  unsigned char* o = out + (long)k * out_inst_stride + ((long)(f_off + f) * Ho + Y0) * Wo;
+  const int npix = rows * Wo;
+  MaskGeom g = {0, Wo, Ho, -1, -1};
+#pragma unroll 4                       // (bounded: left alone the compiler unrolls this loop into ~250 VGPRs)
+  for (int i = threadIdx.x; i < npix; i += 256) {
+    const int y = i / Wo, X = i - y * Wo, Y = Y0 + y;
+    const int v = final_mask_pixel(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, Y, X);
+    o[i] = (unsigned char)v;
+    geom_add(g, v, Y, X);
+  }
+  __shared__ int red[20];
+  g = geom_block_reduce(g, red);
+  if (threadIdx.x == 0 && g.cnt > 0) {
+    int* r = geom + (long)mask * 5;
+    atomicAdd(r + 0, g.cnt);
+    atomicMin(r + 1, g.x0); atomicMin(r + 2, g.y0);
+    atomicMax(r + 3, g.x1); atomicMax(r + 4, g.y1);
+  }
+}
+
+// RLE form: final_mask_rle_kernel (one block per mask, the same two sweeps, the same positions) with the geometry gathered in the
+// first sweep and written by one thread: no atomics, no initialisation.
+__global__ void __launch_bounds__(256)
+final_mask_rle_geom_kernel(const float* __restrict__ lg, int Fw, int Hm, int Wm, int factor, int h, int w, int Ho, int Wo,
+                           const int* __restrict__ inst_idx, int cap, int* __restrict__ pos, int* __restrict__ n_pos,
+                           int* __restrict__ geom) {
+  const int k = blockIdx.x / Fw, f = blockIdx.x - k * Fw;
+  const float* m = lg + ((long)inst_idx[k] * Fw + f) * Hm * Wm;
+  const float sy_scale = (float)h / (float)Ho, sx_scale = (float)w / (float)Wo;
+  const int total = Ho * Wo;
+  const int seg = (total + 255) / 256;
+  const int p0 = min((int)threadIdx.x * seg, total), p1 = min(p0 + seg, total);
+  int prev0 = 0;
+  if (p0 > 0 && p0 < total) prev0 = final_mask_pixel(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, (p0 - 1) % Ho, (p0 - 1) / Ho);
+  int cnt = 0, prev = prev0;
+  MaskGeom g = {0, Wo, Ho, -1, -1};
+#pragma unroll 8
+  for (int p = p0; p < p1; ++p) {
+    const int X = p / Ho, Y = p - X * Ho;
+    const int v = final_mask_pixel(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, Y, X);
+    cnt += (v != prev);
+    prev = v;
+    geom_add(g, v, Y, X);
+  }
+  __shared__ int sc[256];
+  __shared__ int red[20];
+  sc[threadIdx.x] = cnt;
+  g = geom_block_reduce(g, red);                       // (its barrier also publishes sc[])
+  if (threadIdx.x == 0) {
+    int* r = geom + (long)blockIdx.x * 5;
+    r[0] = g.cnt; r[1] = g.x0; r[2] = g.y0; r[3] = g.x1; r[4] = g.y1;
+  }
+  for (int o = 1; o < 256; o <<= 1) {                  // inclusive scan
+    const int add = (int)threadIdx.x >= o ? sc[threadIdx.x - o] : 0;
+    __syncthreads();
+    sc[threadIdx.x] += add;
+    __syncthreads();
+  }
+  int off = sc[threadIdx.x] - cnt;
+  if (threadIdx.x == 255) n_pos[blockIdx.x] = sc[255];
+  int* out = pos + (long)blockIdx.x * cap;
+  prev = prev0;
+#pragma unroll 8
+  for (int p = p0; p < p1; ++p) {
+    const int v = final_mask_pixel(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, p % Ho, p / Ho);
+    if (v != prev) { if (off < cap) out[off] = p; ++off; }
+    prev = v;
+  }
+}
+
+extern "C" int mdqe_final_masks_rle_geom(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
+                                         int h, int w, int Ho, int Wo, int cap, int* pos, int* n_pos, int* geom, void* stream) {
+  MDQE_REQUIRE(n_sel >= 0 && Fw >= 0 && Hm > 0 && Wm > 0 && factor >= 1 && h > 0 && w > 0 && Ho > 0 && Wo > 0 && cap > 0);
+  MDQE_REQUIRE(h <= Hm * factor && w <= Wm * factor && (long)Ho * Wo < 0x7FFFFFFFL);
+  if (n_sel == 0 || Fw == 0) return MDQE_OK;
+  MDQE_CHECK_PTR(logits); MDQE_CHECK_PTR(inst_idx_dev); MDQE_CHECK_PTR(pos); MDQE_CHECK_PTR(n_pos); MDQE_CHECK_PTR(geom);
+  mdqe_clear_error();
+  hipLaunchKernelGGL(final_mask_rle_geom_kernel, dim3((unsigned)(n_sel * Fw)), dim3(256), 0, (hipStream_t)stream, logits, Fw, Hm, Wm,
+                     factor, h, w, Ho, Wo, inst_idx_dev, cap, pos, n_pos, geom);
+  return mdqe_launch_status();
+}
+
+extern "C" int mdqe_final_masks_u8_geom(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
+                                        int h, int w, int Ho, int Wo, unsigned char* out, long out_inst_stride, int f_off,
+                                        int* geom, void* stream) {
+  MDQE_REQUIRE(n_sel >= 0 && Fw >= 0 && Hm > 0 && Wm > 0 && factor >= 1 && h > 0 && w > 0 && Ho > 0 && Wo > 0);
+  MDQE_REQUIRE(h <= Hm * factor && w <= Wm * factor && (long)Ho * Wo < 0x7FFFFFFFL);
+  if (n_sel == 0 || Fw == 0) return MDQE_OK;
+  MDQE_CHECK_PTR(logits); MDQE_CHECK_PTR(inst_idx_dev); MDQE_CHECK_PTR(out); MDQE_CHECK_PTR(geom);
+  // bands per mask: enough blocks to fill the device when the window holds few masks (about 16 blocks of 256 threads per CU), but
+  // at least ~1024 pixels (4 per thread) per block so that the reduction and the atomics stay a small part of a block's work
+  const long n_masks = (long)n_sel * Fw;
+  MDQE_REQUIRE(n_masks * 5 < 0x7FFFFFFFL);
+  long want = (4096 + n_masks - 1) / n_masks;
+  const long most = ((long)Ho * Wo + 1023) / 1024;
+  if (want > most) want = most;
+  if (want > Ho) want = Ho;
+  if (want < 1) want = 1;
+  const int band = (int)((Ho + want - 1) / want);
+  const int n_bands = (Ho + band - 1) / band;
+  MDQE_REQUIRE(n_masks * n_bands < 0x7FFFFFFFL);
+  mdqe_clear_error();
+  const int rows = (int)n_masks;
+  hipLaunchKernelGGL(geom_init_kernel, dim3((unsigned)((rows * 5 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, geom, rows, Ho, Wo);
+  hipLaunchKernelGGL(final_mask_geom_kernel, dim3((unsigned)(n_masks * n_bands)), dim3(256), 0, (hipStream_t)stream, logits, Fw, Hm, Wm,
+                     factor, h, w, Ho, Wo, out, out_inst_stride, f_off, inst_idx_dev, band, n_bands, geom);
+  return mdqe_launch_status();
+}

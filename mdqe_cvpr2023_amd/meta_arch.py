@@ -97,6 +97,9 @@ class MDQE(nn.Module):
         self.trk_priority = int(os.environ.get("MDQE_TRK_PRIORITY", "0"))
         self.resize_on_device = False               # True: frames arrive at native size and get the mapper's ResizeShortestEdge here
         self.rle_output = False                     # True: forward() returns per-frame COCO RLEs ("pred_rles") instead of dense masks
+        # True: forward() on a video adds "pred_boxes" (float32 [L, 4] XYXY_ABS per output) and "pred_areas" (int64 [L]) of the final masks,
+        # gathered by the kernels that write / encode the masks (ops.final_masks_geom / final_masks_rle_geom); off: nothing changes
+        self.geometry_output = False
         self.merge_on_cpu = None                    # None: cfg.merge_on_cpu (MODEL.MDQE.MERGE_ON_CPU); True / False override it
         # Final masks of a tracker window leave the device when the window is flushed (pinned host buffers, copied under the later
         # windows' compute) instead of in one pass + one 100-MB copy after the last window.  Independent of MERGE_ON_CPU, which in the
@@ -897,13 +900,14 @@ class MDQE(nn.Module):
         while state["cur"] is not None:
             yield guarded(step)
 
-    def online_video(self, height=None, width=None, emit="masks", keep=False):
+    def online_video(self, height=None, width=None, emit="masks", keep=False, geometry=False):
         """An online session over ONE video whose frames arrive in pushes (a camera, a stream, a video too long to hold): push()
         returns each tracker window as soon as it is final, close() the rest, result() the video-level scores / labels / tracks.
         height / width: output mask size (default: the frame size); emit: "masks" (bool [n, F, H, W] per window) or "rle"; keep:
-        result() also carries forward()'s "pred_masks" / "pred_rles", bit-identical.  See online.py."""
+        result() also carries forward()'s "pred_masks" / "pred_rles", bit-identical; geometry: every window carries `boxes` / `areas` of its
+        final masks and result() "pred_boxes" / "pred_areas" (with or without keep), equal to forward()'s with geometry_output.  See online.py."""
         from .online import OnlineVideo
-        return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep)
+        return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep, geometry=geometry)
 
     def inference_image(self, batched_inputs):
         """COCO single-image branch: MDQE.forward :213-236 -> mdqe.forward (models/mdqe.py:62-70) -> decoder
@@ -979,6 +983,22 @@ class MDQE(nn.Module):
         inst = torch.div(ti, K, rounding_mode="floor").tolist()
         return sc, labels, inst
 
+    @staticmethod
+    def track_geometry(rows, n_frames, out_size, windows):
+        """Per output j the [n_frames] geometry of row rows[j] from the windows' geom tables: `windows` = (f_off, nf, n rows this window
+        holds, geom int32 [n, nf, 5] on the host).  Frames of windows in which the row did not exist yet stay empty -- zero boxes and
+        areas, like its masks (mdqe/mdqe.py:442).  -> {"pred_boxes": [float32 [n_frames, 4]], "pred_areas": [int64 [n_frames]]}."""
+        from . import rle as R
+        Ho, Wo = int(out_size[0]), int(out_size[1])
+        tabs = {}
+        for r in set(rows):
+            t = torch.tensor([0, Wo, Ho, -1, -1], dtype=torch.int32).repeat(int(n_frames), 1)
+            for f_off, nf, n_w, g in windows:
+                if r < n_w:
+                    t[f_off:f_off + nf] = torch.as_tensor(g)[r]
+            tabs[r] = R.geom_to_boxes(t)
+        return {"pred_boxes": [tabs[r][0].clone() for r in rows], "pred_areas": [tabs[r][1].clone() for r in rows]}
+
     def inference_video(self, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True):
         """mdqe/mdqe.py:430-471.  The x4 aligned-bilinear up-sampling, sigmoid, crop (:357-358), nearest resize to the
         original size and the 0.5 threshold (:458-462) run as ONE kernel per window; windows in which an instance did not
@@ -990,6 +1010,12 @@ class MDQE(nn.Module):
         Ho, Wo = int(image_size[0]), int(image_size[1])
         if not emit_masks:
             return {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels, "pred_masks": []}
+        geometry = bool(self.geometry_output)
+        if early is not None and geometry:
+            early["done"].synchronize()                            # (the geom tables ride on the mask copies' stream)
+            geo = self.track_geometry(inst, n_frames, (Ho, Wo), early["geom"])
+        else:
+            geo = {}
         if early is not None and self.rle_output:
             from . import rle as R
             empty = {"size": [Ho, Wo], "counts": R.counts_to_strings([Ho * Wo], [1])[0].decode("utf-8")}
@@ -1002,17 +1028,21 @@ class MDQE(nn.Module):
                         for f in range(nf):
                             per_inst[i][f_off + f] = {"size": [Ho, Wo], "counts": strs[i * nf + f].decode("utf-8")}
             return {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels,
-                    "pred_rles": [per_inst[i] for i in inst]}
+                    "pred_rles": [per_inst[i] for i in inst], **geo}
         if early is not None:
             early["done"].synchronize()
             hosts = early["host"]                                  # per instance: [n_frames, Ho, Wo] uint8, pinned
             return {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels,
-                    "pred_masks": [hosts[i].view(torch.bool)[:n_frames] for i in inst]}
+                    "pred_masks": [hosts[i].view(torch.bool)[:n_frames] for i in inst], **geo}
         out = torch.zeros(len(sel), n_frames, Ho, Wo, dtype=torch.uint8, device=self.device)
         sel_dev = torch.tensor(sel, dtype=torch.int32, device=self.device)
+        geoms = []                                                 # per window: (f_off, frames, rows written, geom on the device)
         for f_off, m in windows:
             cnt = sum(1 for i in sel if i < m.shape[0])       # sel is ascending: these are its first `cnt` entries
-            if cnt:
+            if cnt and geometry and out.is_cuda:
+                _, g = ops.final_masks_geom(m, sel_dev[:cnt], self.cfg.match_stride, frame_hw[0], frame_hw[1], Ho, Wo, out, f_off)
+                geoms.append((f_off, int(m.shape[1]), cnt, g))
+            elif cnt:
                 ops.final_masks(m, sel_dev[:cnt], self.cfg.match_stride, frame_hw[0], frame_hw[1], Ho, Wo, out, f_off)
         if out.is_cuda:                                            # one D2H into pinned memory (pageable copies run at a fraction of PCIe)
             hbuf = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)
@@ -1022,12 +1052,19 @@ class MDQE(nn.Module):
         else:
             host = out.view(torch.bool)
         pos = {i: p for p, i in enumerate(sel)}
+        if geometry and out.is_cuda:                               # rows of `out` = positions in sel; the copies follow the masks' sync
+            geo = self.track_geometry([pos[i] for i in inst], n_frames, (Ho, Wo),
+                                      [(f, nf, cnt, g.view(cnt, nf, 5).cpu()) for f, nf, cnt, g in geoms])
+        elif geometry:                                             # no device window: from the masks, on the host
+            from . import rle as R
+            bx, ar = R.geom_to_boxes(R.geometry_dense(host))
+            geo = {"pred_boxes": [bx[pos[i]].clone() for i in inst], "pred_areas": [ar[pos[i]].clone() for i in inst]}
         if self.rle_output:                                        # no early path (CPU device / unknown length): encode on the host
             from . import rle as R
             enc = {i: [R.encode_dense(fm.numpy()) for fm in host[pos[i]]] for i in sel}
-            return {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels, "pred_rles": [enc[i] for i in inst]}
+            return {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels, "pred_rles": [enc[i] for i in inst], **geo}
         return {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels,
-                "pred_masks": [host[pos[i]] for i in inst]}
+                "pred_masks": [host[pos[i]] for i in inst], **geo}
 
 
 class ClipMerger:
@@ -1038,9 +1075,11 @@ class ClipMerger:
     tracker_cls = OverTracker               # (tests without a GPU substitute a stand-in bank, tests/_standins.py)
     EARLY_TRACKS = 48                       # tracks per video the early-mask path budgets pinned memory for
 
-    def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True, online=None):
+    def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True, online=None, geometry=None):
         self.model, self.frame_hw, self.out_size, self.mask_hw = model, frame_hw, out_size, mask_hw
         self.emit_masks = emit_masks                # False: scores / labels only (ranks > 0 of a sharded video)
+        # boxes and areas of the final masks from the kernels that produce them (None: model.geometry_output; online sessions pass theirs)
+        self.geometry = bool(getattr(model, "geometry_output", False) if geometry is None else geometry)
         # online ("masks" | "rle"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their RLE -- of every
         # current track are built and appended to `emitted`; neither the logits nor a host buffer stay here (n_frames is unknown)
         self.online = online
@@ -1150,18 +1189,24 @@ class ClipMerger:
             model._copy_stream = torch.cuda.Stream(self.dev)
         cs = model._copy_stream
         if self.early is None:
-            self.early = {"host": [], "windows": [], "done": torch.cuda.Event(), "rle": []}
+            self.early = {"host": [], "windows": [], "done": torch.cuda.Event(), "rle": [], "geom": []}
         if model.rle_output:                        # run boundaries instead of dense masks: KBs instead of MBs per window
             if n:
                 idx = torch.arange(n, dtype=torch.int32, device=self.dev)
                 cap = 4 * (Ho + Wo) + 64                # a blob crosses a column twice: generous for anything mask-like
                 while True:
-                    pos, n_pos = ops.final_masks_rle(m, idx, model.cfg.match_stride, self.frame_hw[0], self.frame_hw[1], Ho, Wo, cap)
+                    if self.geometry:
+                        pos, n_pos, geom = ops.final_masks_rle_geom(m, idx, model.cfg.match_stride, self.frame_hw[0], self.frame_hw[1],
+                                                                    Ho, Wo, cap)
+                    else:
+                        pos, n_pos = ops.final_masks_rle(m, idx, model.cfg.match_stride, self.frame_hw[0], self.frame_hw[1], Ho, Wo, cap)
                     mx = int(n_pos.max())               # (sync on the tracker stream; the window's logits are final here)
                     if mx <= cap:
                         break
                     cap = mx
                 self.early["rle"].append((self.f_off, nf, n, pos[:, :max(mx, 1)].cpu().numpy(), n_pos.cpu().numpy()))
+                if self.geometry:
+                    self.early["geom"].append((self.f_off, nf, n, geom.view(n, nf, 5).cpu()))
             self.early["windows"].append((self.f_off, nf, n))
             return
         hosts = self.early["host"]
@@ -1173,12 +1218,20 @@ class ClipMerger:
         if n:
             dev = torch.empty(n, nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
             idx = torch.arange(n, dtype=torch.int32, device=self.dev)
-            ops.final_masks(m, idx, model.cfg.match_stride, self.frame_hw[0], self.frame_hw[1], Ho, Wo, dev, 0)
+            if self.geometry:                       # the window's [n, nf, 5] table follows its masks to the host on the same stream / event
+                _, geom = ops.final_masks_geom(m, idx, model.cfg.match_stride, self.frame_hw[0], self.frame_hw[1], Ho, Wo, dev, 0)
+                hgeom = torch.empty((n, nf, 5), dtype=torch.int32, pin_memory=True)
+                self.early["geom"].append((self.f_off, nf, n, hgeom))
+            else:
+                ops.final_masks(m, idx, model.cfg.match_stride, self.frame_hw[0], self.frame_hw[1], Ho, Wo, dev, 0)
             cs.wait_stream(self.side)
             with torch.cuda.stream(cs):
                 for i in range(n):
                     hosts[i][self.f_off:self.f_off + nf].copy_(dev[i], non_blocking=True)
                 dev.record_stream(cs)
+                if self.geometry:
+                    hgeom.copy_(geom.view(n, nf, 5), non_blocking=True)
+                    geom.record_stream(cs)
                 self.early["done"].record(cs)
         self.early["windows"].append((self.f_off, nf, n))
 
@@ -1192,6 +1245,8 @@ class ClipMerger:
         Ho, Wo = int(self.out_size[0]), int(self.out_size[1])
         ms, (fh, fw) = model.cfg.match_stride, self.frame_hw
         rec = {"frames": (self.f_off, self.f_off + nf), "cls_probs": c, "ready": None}
+        if self.geometry:
+            rec["geom"] = torch.zeros((0, nf, 5), dtype=torch.int32)     # (no tracks yet; replaced below)
         idx = torch.arange(n, dtype=torch.int32, device=self.dev)
         if self.online == "rle":
             from . import rle as R
@@ -1199,11 +1254,16 @@ class ClipMerger:
             if n:
                 cap = 4 * (Ho + Wo) + 64
                 while True:
-                    pos, n_pos = ops.final_masks_rle(m, idx, ms, fh, fw, Ho, Wo, cap)
+                    if self.geometry:
+                        pos, n_pos, geom = ops.final_masks_rle_geom(m, idx, ms, fh, fw, Ho, Wo, cap)
+                    else:
+                        pos, n_pos = ops.final_masks_rle(m, idx, ms, fh, fw, Ho, Wo, cap)
                     mx = int(n_pos.max())
                     if mx <= cap:
                         break
                     cap = mx
+                if self.geometry:
+                    rec["geom"] = geom.view(n, nf, 5).cpu()
                 counts, lengths = R.positions_to_counts(pos[:, :max(mx, 1)].cpu().numpy(), n_pos.cpu().numpy(), Ho * Wo)
                 strs = R.counts_to_strings(counts, lengths)
                 rles = [[{"size": [Ho, Wo], "counts": strs[i * nf + f].decode("utf-8")} for f in range(nf)] for i in range(n)]
@@ -1216,12 +1276,19 @@ class ClipMerger:
             model._copy_stream = torch.cuda.Stream(self.dev)
         cs = model._copy_stream
         dev = torch.empty(n, nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
-        ops.final_masks(m, idx, ms, fh, fw, Ho, Wo, dev, 0)
+        if self.geometry:
+            _, geom = ops.final_masks_geom(m, idx, ms, fh, fw, Ho, Wo, dev, 0)
+            rec["geom"] = torch.empty((n, nf, 5), dtype=torch.int32, pin_memory=True)
+        else:
+            ops.final_masks(m, idx, ms, fh, fw, Ho, Wo, dev, 0)
         host = model.pinned_mask_buffer((n, nf, Ho, Wo))
         cs.wait_stream(self.side)
         with torch.cuda.stream(cs):
             host.copy_(dev, non_blocking=True)
             dev.record_stream(cs)
+            if self.geometry:
+                rec["geom"].copy_(geom.view(n, nf, 5), non_blocking=True)
+                geom.record_stream(cs)
             rec["ready"] = torch.cuda.Event()
             rec["ready"].record(cs)
         rec["masks"] = host.view(torch.bool)

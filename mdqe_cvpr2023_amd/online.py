@@ -1,9 +1,10 @@
 """Online video inference: frames arrive in pushes of any size, tracker windows come back as soon as they are final.
 
-    ov = model.online_video(height=H, width=W, emit="masks", keep=False)
+    ov = model.online_video(height=H, width=W, emit="masks", keep=False, geometry=False)
     for chunk in source:                   # [n, 3, h, w] uint8 / float32, host or device, n >= 1 (n == 0: no-op)
         for win in ov.push(chunk):         # the windows this push completed, in order
             win.frames, win.track_ids, win.cls_probs, win.masks   # (or win.rles with emit="rle")
+            win.boxes, win.areas           # geometry=True: XYXY_ABS float32 [n, F, 4] and pixel counts int64 [n, F] of those masks
     for win in ov.close():                 # the clamped last clip and the final flush
         ...
     res = ov.result()                      # {"image_size", "pred_scores", "pred_labels", "pred_track_ids"} (+ "pred_masks" / "pred_rles" if keep)
@@ -12,7 +13,9 @@ Same clips in the same order and the same window flushes as `MDQE.forward` on th
 keep=True the result equals forward()'s bit for bit.  A push runs every clip whose frames are all present (the schedule's last clip,
 `end > L`, can only run at close(), when L is known); each frame goes through the per-frame stages once -- a clip that straddles two
 pushes reads the carried cache rows of the earlier frames (`_Carry`, at most T-1 frames).  What stays on the device between pushes is
-the tracker bank and the carry; the masks of a window leave for the host when it is flushed.  MERGE_ON_CPU has no meaning here (it
+the tracker bank and the carry; the masks of a window leave for the host when it is flushed.  With geometry=True the kernels that
+write / encode a window's masks also return each mask's pixel count and tight box (ops.final_masks_geom / final_masks_rle_geom): no pass
+over the masks on the host, no decoding of the RLEs; result() then carries "pred_boxes" / "pred_areas" whatever `keep` says.  MERGE_ON_CPU has no meaning here (it
 only places the window results the offline merge waits on).  One GPU, one video per session.
 """
 import contextlib
@@ -96,16 +99,19 @@ class _Carry:
 class Window:
     """One tracker window: frames [f0, f1), tracker instance index of each row, this window's class probabilities per track
     (provisional: the video-level class is decided at close), and the final masks -- bool [n, f1-f0, H, W] on the host -- or,
-    with emit="rle", per track per frame {"size", "counts"}."""
+    with emit="rle", per track per frame {"size", "counts"}.  With geometry=True: boxes float32 [n, f1-f0, 4] ([xmin, ymin, xmax+1,
+    ymax+1] in output pixels, zeros for an empty mask) and areas int64 [n, f1-f0] of those masks."""
     frames: tuple
     track_ids: list
     cls_probs: torch.Tensor
     masks: torch.Tensor = None
     rles: list = None
+    boxes: torch.Tensor = None
+    areas: torch.Tensor = None
 
 
 class OnlineVideo:
-    def __init__(self, model, height=None, width=None, emit="masks", keep=False):
+    def __init__(self, model, height=None, width=None, emit="masks", keep=False, geometry=False):
         if emit not in ("masks", "rle"):
             raise ValueError("online_video: emit must be 'masks' or 'rle'")
         if model.cfg.is_coco:
@@ -113,6 +119,8 @@ class OnlineVideo:
         if model.device.type != "cuda":
             raise RuntimeError("online_video: the model must be on a HIP device (the product has no CPU path)")
         self.model, self.emit, self.keep = model, emit, bool(keep)
+        self.geometry = bool(geometry)
+        self.geoms = []                           # per window (f0, frames, tracks, geom [n, F, 5] host): a few KB, kept without `keep`
         self.height, self.width = height, width
         cfg = model.cfg
         self.T, self.stride, self.win = cfg.n_frames_test, cfg.clip_stride, cfg.n_frames_window_test
@@ -143,7 +151,8 @@ class OnlineVideo:
         self.geo = model.engine.geometry(h, w)
         self.out_size = (int(self.height if self.height is not None else h0), int(self.width if self.width is not None else w0))
         self.mask_hw = (self.geo.Hp // cfg.match_stride, self.geo.Wp // cfg.match_stride)
-        self.merger = ClipMerger(model, self.hw, self.out_size, self.mask_hw, n_frames=None, online=self.emit)
+        self.merger = ClipMerger(model, self.hw, self.out_size, self.mask_hw, n_frames=None, online=self.emit,
+                                 geometry=self.geometry)
         shapes = model.engine.cache_shapes(self.geo)
         per_frame = 4 * sum(int(np.prod(sh)) for sh in shapes.values())
         forced = int(os.environ.get("MDQE_CACHE_FRAMES", "0"))
@@ -174,8 +183,13 @@ class OnlineVideo:
             if r["ready"] is not None:
                 r["ready"].synchronize()
             n = int(r["cls_probs"].shape[0])
+            boxes = areas = None
+            if self.geometry:                     # (the table came with the masks: same stream and event, or the same sync as the positions)
+                from . import rle as R
+                boxes, areas = R.geom_to_boxes(r["geom"])
+                self.geoms.append((r["frames"][0], r["frames"][1] - r["frames"][0], n, r["geom"]))
             out.append(Window(frames=r["frames"], track_ids=list(range(n)), cls_probs=r["cls_probs"],
-                              masks=r.get("masks"), rles=r.get("rles")))
+                              masks=r.get("masks"), rles=r.get("rles"), boxes=boxes, areas=areas))
         del self.merger.emitted[:]
         if self.keep:
             self.kept.extend(out)
@@ -230,7 +244,8 @@ class OnlineVideo:
     def result(self):
         """After close(): {"image_size", "pred_scores", "pred_labels", "pred_track_ids"} -- the video-level top-k of
         `inference_video`; pred_track_ids[j] is the track behind output j.  keep=True adds "pred_masks" (or "pred_rles"),
-        assembled from the windows handed out, equal to forward()'s."""
+        assembled from the windows handed out, equal to forward()'s; geometry=True adds "pred_boxes" / "pred_areas" (forward()'s with
+        model.geometry_output), with or without keep."""
         if not self.closed:
             raise RuntimeError("online_video: result() before close()")
         if self._result is not None:
@@ -240,6 +255,8 @@ class OnlineVideo:
         sc, labels, inst = self.model.select_tracks(self.merger.cls_clips)
         Ho, Wo = self.out_size
         res = {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels, "pred_track_ids": list(inst)}
+        if self.geometry:
+            res.update(self.model.track_geometry(list(inst), self.received, (Ho, Wo), self.geoms))
         if self.keep:
             sel = sorted(set(inst))
             if self.emit == "rle":

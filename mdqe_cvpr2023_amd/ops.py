@@ -551,6 +551,22 @@ def final_masks(logits, inst_idx, factor, h, w, Ho, Wo, out, f_off):
     return out
 
 
+def final_masks_geom(logits, inst_idx, factor, h, w, Ho, Wo, out, f_off, geom=None):
+    """ops.final_masks plus, from the same sweep, geom int32 [n_sel*Fw, 5]: row k*Fw+f = (area, xmin, ymin, xmax, ymax) of the set
+    pixels of (row k, window frame f), inclusive; an empty mask is (0, Wo, Ho, -1, -1).  `geom`: a buffer to write into (fully overwritten, whatever it held).  -> (out, geom)."""
+    _chk(logits, "logits")
+    n, Fw, Hm, Wm = logits.shape
+    k = int(inst_idx.numel())
+    _chk(inst_idx, "inst_idx", torch.int32)
+    if (not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 4 or out.shape[0] < k or (out.shape[0] and not out[0].is_contiguous())
+            or tuple(out.shape[2:]) != (Ho, Wo) or f_off < 0 or f_off + Fw > out.shape[1]):
+        raise RuntimeError("final_masks_geom: out must be CUDA uint8 [>= n_sel, >= f_off + Fw, Ho, Wo]")
+    geom = _geom_rows(geom, k * Fw, logits.device)
+    check(lib.mdqe_final_masks_u8_geom(ptr(logits), k, ptr(inst_idx), Fw, Hm, Wm, factor, h, w, Ho, Wo, ptr(out), out.stride(0), f_off,
+                                       ptr(geom), cur_stream()), "final_masks_geom")
+    return out, geom
+
+
 def layernorm_post(x, gamma, beta, post, eps=1e-5, out=None):
     """out = LN(x)*gamma + beta + post."""
     _chk(x, "x"); _chk(post, "post")
@@ -665,6 +681,29 @@ def final_masks_rle(logits, inst_idx, factor, h, w, Ho, Wo, cap):
     check(lib.mdqe_final_masks_rle(ptr(logits), k, ptr(inst_idx), Fw, Hm, Wm, factor, h, w, Ho, Wo, cap, ptr(pos), ptr(n_pos),
                                    cur_stream()), "final_masks_rle")
     return pos, n_pos
+
+
+def _geom_rows(geom, rows, device):
+    if geom is None:
+        return torch.empty(rows, 5, dtype=torch.int32, device=device)
+    _chk(geom, "geom", torch.int32)
+    if tuple(geom.shape) != (rows, 5):
+        raise RuntimeError("final_masks_geom: geom must be int32 [n_sel * Fw, 5]")
+    return geom
+
+
+def final_masks_rle_geom(logits, inst_idx, factor, h, w, Ho, Wo, cap, geom=None):
+    """ops.final_masks_rle plus the geom rows of ops.final_masks_geom from the same sweep -> (pos, n_pos, geom)."""
+    _chk(logits, "logits")
+    n, Fw, Hm, Wm = logits.shape
+    k = int(inst_idx.numel())
+    pos = torch.empty(k * Fw, cap, dtype=torch.int32, device=logits.device)
+    n_pos = torch.empty(k * Fw, dtype=torch.int32, device=logits.device)
+    _chk(inst_idx, "inst_idx", torch.int32)
+    geom = _geom_rows(geom, k * Fw, logits.device)
+    check(lib.mdqe_final_masks_rle_geom(ptr(logits), k, ptr(inst_idx), Fw, Hm, Wm, factor, h, w, Ho, Wo, cap, ptr(pos), ptr(n_pos),
+                                        ptr(geom), cur_stream()), "final_masks_rle_geom")
+    return pos, n_pos, geom
 
 
 # ---- per-clip stages (csrc/clip_ops.hip) -----------------------------------------------------------------------------
