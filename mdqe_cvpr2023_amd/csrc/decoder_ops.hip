@@ -366,63 +366,6 @@ final_mask_kernel(const float* __restrict__ lg, int Fw, int Hm, int Wm, int fact
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Final masks straight to COCO run-length form (SURVEY §8f.1: the result writer's
-// mask_util.encode(np.array(mask[:, :, None], order="F")), mdqe/data/ytvis_eval.py:307-312, i.e. cocoapi rleEncode): the
-// mask of (instance k, frame f) is never materialised -- one block walks its pixels in COLUMN-major order, every thread a
-// contiguous segment, evaluating final_mask_pixel on the fly, and emits the positions p where the value differs from
-// p-1 (value before the first pixel = 0).  Runs are the differences of consecutive positions (host).  Two sweeps: count
-// per thread -> block scan -> write.  pos [n_sel*Fw, cap], n_pos [n_sel*Fw] (may exceed cap: the host then falls back).
-// ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-final_mask_rle_kernel(const float* __restrict__ lg, int Fw, int Hm, int Wm, int factor, int h, int w, int Ho, int Wo,
-                      const int* __restrict__ inst_idx, int cap, int* __restrict__ pos, int* __restrict__ n_pos) {
-  const int k = blockIdx.x / Fw, f = blockIdx.x - k * Fw;
-  const float* m = lg + ((long)inst_idx[k] * Fw + f) * Hm * Wm;
-  const float sy_scale = (float)h / (float)Ho, sx_scale = (float)w / (float)Wo;
-  const int total = Ho * Wo;
-  const int seg = (total + 255) / 256;
-  const int p0 = min((int)threadIdx.x * seg, total), p1 = min(p0 + seg, total);
-  int prev0 = 0;
-  if (p0 > 0 && p0 < total) prev0 = final_mask_pixel(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, (p0 - 1) % Ho, (p0 - 1) / Ho);
-  int cnt = 0, prev = prev0;
-  for (int p = p0; p < p1; ++p) {
-    const int v = final_mask_pixel(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, p % Ho, p / Ho);
-    cnt += (v != prev);
-    prev = v;
-  }
-  __shared__ int sc[256];
-  sc[threadIdx.x] = cnt;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {                  // inclusive scan
-    const int add = (int)threadIdx.x >= o ? sc[threadIdx.x - o] : 0;
-    __syncthreads();
-    sc[threadIdx.x] += add;
-    __syncthreads();
-  }
-  int off = sc[threadIdx.x] - cnt;
-  if (threadIdx.x == 255) n_pos[blockIdx.x] = sc[255];
-  int* out = pos + (long)blockIdx.x * cap;
-  prev = prev0;
-  for (int p = p0; p < p1; ++p) {
-    const int v = final_mask_pixel(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, p % Ho, p / Ho);
-    if (v != prev) { if (off < cap) out[off] = p; ++off; }
-    prev = v;
-  }
-}
-
-extern "C" int mdqe_final_masks_rle(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
-                                    int h, int w, int Ho, int Wo, int cap, int* pos, int* n_pos, void* stream) {
-  MDQE_REQUIRE(n_sel >= 0 && Fw >= 0 && Hm > 0 && Wm > 0 && factor >= 1 && h > 0 && w > 0 && Ho > 0 && Wo > 0 && cap > 0);
-  MDQE_REQUIRE(h <= Hm * factor && w <= Wm * factor && (long)Ho * Wo < 0x7FFFFFFFL);
-  if (n_sel == 0 || Fw == 0) return MDQE_OK;
-  MDQE_CHECK_PTR(logits); MDQE_CHECK_PTR(inst_idx_dev); MDQE_CHECK_PTR(pos); MDQE_CHECK_PTR(n_pos);
-  mdqe_clear_error();
-  hipLaunchKernelGGL(final_mask_rle_kernel, dim3((unsigned)(n_sel * Fw)), dim3(256), 0, (hipStream_t)stream, logits, Fw, Hm, Wm, factor,
-                     h, w, Ho, Wo, inst_idx_dev, cap, pos, n_pos);
-  return mdqe_launch_status();
-}
-
 extern "C" int mdqe_final_masks_u8(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
                                    int h, int w, int Ho, int Wo, unsigned char* out, long out_inst_stride, int f_off,
                                    void* stream) {
@@ -515,12 +458,20 @@ final_mask_geom_kernel(const float* __restrict__ lg, int Fw, int Hm, int Wm, int
   }
 }
 
-// RLE form: final_mask_rle_kernel (one block per mask, the same two sweeps, the same positions) with the geometry gathered in the
-// first sweep and written by one thread: no atomics, no initialisation.
+// ------------------------------------------------------------------------------------------------
+// Final masks straight to COCO run-length form (SURVEY §8f.1: the result writer's
+// mask_util.encode(np.array(mask[:, :, None], order="F")), mdqe/data/ytvis_eval.py:307-312, i.e. cocoapi rleEncode): the
+// mask of (instance k, frame f) is never materialised -- one block walks its pixels in COLUMN-major order, every thread a
+// contiguous segment, evaluating final_mask_pixel on the fly, and emits the positions p where the value differs from
+// p-1 (value before the first pixel = 0).  Runs are the differences of consecutive positions (host).  Two sweeps: count
+// per thread -> block scan -> write.  pos [n_sel*Fw, cap], n_pos [n_sel*Fw] (may exceed cap: the host then falls back).
+// GEOM: the geometry is gathered in the first sweep and written by one thread -- no atomics, no initialisation.
+// ------------------------------------------------------------------------------------------------
+template <bool GEOM>
 __global__ void __launch_bounds__(256)
-final_mask_rle_geom_kernel(const float* __restrict__ lg, int Fw, int Hm, int Wm, int factor, int h, int w, int Ho, int Wo,
-                           const int* __restrict__ inst_idx, int cap, int* __restrict__ pos, int* __restrict__ n_pos,
-                           int* __restrict__ geom) {
+final_mask_rle_kernel(const float* __restrict__ lg, int Fw, int Hm, int Wm, int factor, int h, int w, int Ho, int Wo,
+                      const int* __restrict__ inst_idx, int cap, int* __restrict__ pos, int* __restrict__ n_pos,
+                      int* __restrict__ geom) {
   const int k = blockIdx.x / Fw, f = blockIdx.x - k * Fw;
   const float* m = lg + ((long)inst_idx[k] * Fw + f) * Hm * Wm;
   const float sy_scale = (float)h / (float)Ho, sx_scale = (float)w / (float)Wo;
@@ -531,21 +482,31 @@ final_mask_rle_geom_kernel(const float* __restrict__ lg, int Fw, int Hm, int Wm,
   if (p0 > 0 && p0 < total) prev0 = final_mask_pixel(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, (p0 - 1) % Ho, (p0 - 1) / Ho);
   int cnt = 0, prev = prev0;
   MaskGeom g = {0, Wo, Ho, -1, -1};
-#pragma unroll 8
-  for (int p = p0; p < p1; ++p) {
+  auto count = [&](int p) {
     const int X = p / Ho, Y = p - X * Ho;
     const int v = final_mask_pixel(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, Y, X);
     cnt += (v != prev);
     prev = v;
-    geom_add(g, v, Y, X);
+    if constexpr (GEOM) geom_add(g, v, Y, X);
+  };
+  // (the unroll bound belongs to the GEOM instance alone: the plain one is left to the compiler's own choice)
+  if constexpr (GEOM) {
+#pragma unroll 8
+    for (int p = p0; p < p1; ++p) count(p);
+  } else {
+    for (int p = p0; p < p1; ++p) count(p);
   }
   __shared__ int sc[256];
-  __shared__ int red[20];
   sc[threadIdx.x] = cnt;
-  g = geom_block_reduce(g, red);                       // (its barrier also publishes sc[])
-  if (threadIdx.x == 0) {
-    int* r = geom + (long)blockIdx.x * 5;
-    r[0] = g.cnt; r[1] = g.x0; r[2] = g.y0; r[3] = g.x1; r[4] = g.y1;
+  if constexpr (GEOM) {
+    __shared__ int red[20];
+    g = geom_block_reduce(g, red);                     // (its barrier also publishes sc[])
+    if (threadIdx.x == 0) {
+      int* r = geom + (long)blockIdx.x * 5;
+      r[0] = g.cnt; r[1] = g.x0; r[2] = g.y0; r[3] = g.x1; r[4] = g.y1;
+    }
+  } else {
+    __syncthreads();
   }
   for (int o = 1; o < 256; o <<= 1) {                  // inclusive scan
     const int add = (int)threadIdx.x >= o ? sc[threadIdx.x - o] : 0;
@@ -557,12 +518,29 @@ final_mask_rle_geom_kernel(const float* __restrict__ lg, int Fw, int Hm, int Wm,
   if (threadIdx.x == 255) n_pos[blockIdx.x] = sc[255];
   int* out = pos + (long)blockIdx.x * cap;
   prev = prev0;
-#pragma unroll 8
-  for (int p = p0; p < p1; ++p) {
+  auto emit = [&](int p) {
     const int v = final_mask_pixel(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, p % Ho, p / Ho);
     if (v != prev) { if (off < cap) out[off] = p; ++off; }
     prev = v;
+  };
+  if constexpr (GEOM) {
+#pragma unroll 8
+    for (int p = p0; p < p1; ++p) emit(p);
+  } else {
+    for (int p = p0; p < p1; ++p) emit(p);
   }
+}
+
+extern "C" int mdqe_final_masks_rle(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
+                                    int h, int w, int Ho, int Wo, int cap, int* pos, int* n_pos, void* stream) {
+  MDQE_REQUIRE(n_sel >= 0 && Fw >= 0 && Hm > 0 && Wm > 0 && factor >= 1 && h > 0 && w > 0 && Ho > 0 && Wo > 0 && cap > 0);
+  MDQE_REQUIRE(h <= Hm * factor && w <= Wm * factor && (long)Ho * Wo < 0x7FFFFFFFL);
+  if (n_sel == 0 || Fw == 0) return MDQE_OK;
+  MDQE_CHECK_PTR(logits); MDQE_CHECK_PTR(inst_idx_dev); MDQE_CHECK_PTR(pos); MDQE_CHECK_PTR(n_pos);
+  mdqe_clear_error();
+  hipLaunchKernelGGL(final_mask_rle_kernel<false>, dim3((unsigned)(n_sel * Fw)), dim3(256), 0, (hipStream_t)stream, logits, Fw, Hm, Wm, factor,
+                     h, w, Ho, Wo, inst_idx_dev, cap, pos, n_pos, nullptr);
+  return mdqe_launch_status();
 }
 
 extern "C" int mdqe_final_masks_rle_geom(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
@@ -572,7 +550,7 @@ extern "C" int mdqe_final_masks_rle_geom(const float* logits, int n_sel, const i
   if (n_sel == 0 || Fw == 0) return MDQE_OK;
   MDQE_CHECK_PTR(logits); MDQE_CHECK_PTR(inst_idx_dev); MDQE_CHECK_PTR(pos); MDQE_CHECK_PTR(n_pos); MDQE_CHECK_PTR(geom);
   mdqe_clear_error();
-  hipLaunchKernelGGL(final_mask_rle_geom_kernel, dim3((unsigned)(n_sel * Fw)), dim3(256), 0, (hipStream_t)stream, logits, Fw, Hm, Wm,
+  hipLaunchKernelGGL(final_mask_rle_kernel<true>, dim3((unsigned)(n_sel * Fw)), dim3(256), 0, (hipStream_t)stream, logits, Fw, Hm, Wm,
                      factor, h, w, Ho, Wo, inst_idx_dev, cap, pos, n_pos, geom);
   return mdqe_launch_status();
 }

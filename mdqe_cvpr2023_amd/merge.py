@@ -1,0 +1,336 @@
+"""The second half of the clip loop (mdqe/mdqe.py:337-366, 430-471): `ClipMerger` (tracker update per clip, window flushes) and
+`video_result` (the video's result from the flushed windows); `meta_arch.MDQE` keeps its entry points as delegates.  A flushed window
+becomes final masks per window into pinned memory (`_early_masks`), per window as a record (`_online_window`, online.OnlineVideo) or all
+windows in one pass at the end (`video_result`).  What the three share is written once: `dense_masks` / `rle_positions` (window logits
+-> masks / run boundaries, with or without geometry), `to_host` (the hop on the copy stream), `rle.positions_to_rles`, `stitch`."""
+import contextlib
+import dataclasses
+import os
+
+import torch
+
+from . import rle as R
+from .tracking import Clips, OverTracker
+
+
+def dense_masks(m, idx, stride, frame_hw, out_size, geometry, out, f_off):
+    """Final masks of rows `idx` (int32, device) of window logits m [n, F, Hm, Wm] into out[:len(idx), f_off:f_off + F] (uint8, device).
+    -> the window's geometry table int32 [len(idx), F, 5] on the device (geometry), else None."""
+    from . import ops
+    (fh, fw), (Ho, Wo) = frame_hw, out_size
+    if geometry:
+        return ops.final_masks_geom(m, idx, stride, fh, fw, Ho, Wo, out, f_off)[1].view(int(idx.numel()), int(m.shape[1]), 5)
+    ops.final_masks(m, idx, stride, fh, fw, Ho, Wo, out, f_off)
+
+
+def rle_positions(m, idx, stride, frame_hw, out_size, geometry):
+    """Run boundaries instead of dense masks (KBs instead of MBs per window) of rows `idx` of window logits m, on the host -> (pos
+    [len(idx) * F, >= 1], n_pos [len(idx) * F], numpy; geometry table int32 [len(idx), F, 5] or None).  One host sync, on `n_pos.max()`."""
+    from . import ops
+    (fh, fw), (Ho, Wo) = frame_hw, out_size
+    cap = 4 * (Ho + Wo) + 64                            # a blob crosses a column twice: generous for anything mask-like
+    while True:
+        if geometry:
+            pos, n_pos, geom = ops.final_masks_rle_geom(m, idx, stride, fh, fw, Ho, Wo, cap)
+        else:
+            pos, n_pos = ops.final_masks_rle(m, idx, stride, fh, fw, Ho, Wo, cap)
+        mx = int(n_pos.max())
+        if mx <= cap:
+            break
+        cap = mx
+    return pos[:, :max(mx, 1)].cpu().numpy(), n_pos.cpu().numpy(), geom.view(int(idx.numel()), int(m.shape[1]), 5).cpu() if geometry else None
+
+
+def copy_stream(model):
+    """The model's copy stream, created at the first call (the order streams are first used in decides their queues: `MDQE._make_streams`)."""
+    if model._copy_stream is None:
+        model._copy_stream = torch.cuda.Stream(model.device)
+    return model._copy_stream
+
+
+def to_host(cs, side, masks, copies, geom, event):
+    """A window's dense masks (device, produced on stream `side`) to pinned host memory on the copy stream `cs`: `copies` = (pinned
+    destination, part of `masks`) pairs.  The geometry table (or None) rides on the same stream; `event` is recorded behind both.
+    -> the table in pinned memory (valid once `event` has fired), or None."""
+    hgeom = None if geom is None else torch.empty(geom.shape, dtype=torch.int32, pin_memory=True)
+    cs.wait_stream(side)
+    with torch.cuda.stream(cs):
+        for dst, src in copies:
+            dst.copy_(src, non_blocking=True)
+        masks.record_stream(cs)
+        if geom is not None:
+            hgeom.copy_(geom, non_blocking=True)
+            geom.record_stream(cs)
+        event.record(cs)
+    return hgeom
+
+
+def stitch(rows, n_frames, windows, empty, join):
+    """Per output j, row rows[j] over the whole video.  `windows`: (f_off, frames, n rows the window holds, piece) in video order,
+    piece[r] = row r's part for those frames; `join(parts)` concatenates.  Frames no window holds for a row -- those before the window
+    in which its track first appears (mdqe/mdqe.py:442) -- are `empty(count)`.  Outputs of the same row share one object."""
+    out = {}
+    for r in set(rows):
+        parts, at = [], 0
+        for f_off, nf, n, piece in windows:
+            if r < n:
+                if f_off > at:
+                    parts.append(empty(f_off - at))
+                parts.append(piece[r])
+                at = f_off + nf
+        if at < n_frames or not parts:
+            parts.append(empty(n_frames - at))
+        out[r] = join(parts)
+    return [out[r] for r in rows]
+
+
+def stitch_rles(rows, n_frames, out_size, windows):
+    """`stitch` of per-window RLE lists (piece[r]: one dict per frame): per output the list of its n_frames RLE dicts."""
+    return stitch(rows, n_frames, windows, lambda k: [R.empty_rle(out_size) for _ in range(k)], lambda parts: sum(parts, []))
+
+
+def track_geometry(rows, n_frames, out_size, windows):
+    """Per output j the [n_frames] geometry of row rows[j] from the windows' geom tables: `windows` = (f_off, nf, n rows this window
+    holds, geom int32 [n, nf, 5] on the host).  -> {"pred_boxes": [float32 [n_frames, 4]], "pred_areas": [int64 [n_frames]]}."""
+    Ho, Wo = int(out_size[0]), int(out_size[1])
+    none = torch.tensor([[0, Wo, Ho, -1, -1]], dtype=torch.int32)
+    wins = [(f, nf, n, torch.as_tensor(g)) for f, nf, n, g in windows]
+    geo = [R.geom_to_boxes(t) for t in stitch(rows, int(n_frames), wins, lambda k: none.repeat(k, 1), torch.cat)]   # (fresh tensors per output)
+    return {"pred_boxes": [b for b, _ in geo], "pred_areas": [a for _, a in geo]}
+
+
+def select_tracks(cls_clips, num_classes):
+    """mdqe/mdqe.py:431-454 without the masks: the video-level class scores of every track from its per-window class rows
+    (`cls_clips`, [tracks so far, K] per window) and their top-k -> (scores [k] host tensor, labels, track index of each output)."""
+    total = cls_clips[-1].shape[0]
+    cc = torch.stack([torch.cat([c, c.new_zeros(total - c.shape[0], c.shape[1])]) for c in cls_clips])
+    out_cls = (0.75 * cc.mean(0) + 0.25 * cc.max(0)[0]).flatten().cpu()
+    k = min(max(int(out_cls.gt(0.05).sum()), 10), out_cls.numel())   # (the reference's topk(max(.,10)), :449-450, assumes >= 10 scores)
+    sc, ti = out_cls.topk(k, sorted=False)
+    return sc, (ti % num_classes).tolist(), torch.div(ti, num_classes, rounding_mode="floor").tolist()
+
+
+@dataclasses.dataclass
+class EarlyMasks:
+    """What `ClipMerger._early_masks` has brought to the host by the end of the video, for every track (not only the selected ones)."""
+    done: object                                                      # event behind the last copy into `hosts` / the pinned tables of `geom`
+    hosts: list = dataclasses.field(default_factory=list)             # dense: per track, pinned uint8 [L, Ho, Wo]
+    rle: list = dataclasses.field(default_factory=list)               # RLE: per window (f_off, frames, tracks, pos, n_pos) of rle_positions
+    geom: list = dataclasses.field(default_factory=list)              # per window (f_off, frames, tracks, int32 [tracks, frames, 5] host)
+
+
+def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True):
+    """mdqe/mdqe.py:430-471.  The x4 aligned-bilinear up-sampling, sigmoid, crop (:357-358), nearest resize to the original size and
+    the 0.5 threshold (:458-462) run as ONE kernel per window; windows in which an instance did not exist yet stay zero (:442).
+    `early` (EarlyMasks): the masks of every tracked instance are on the host already, only the selection is left.  Without it
+    (`windows`: (f_off, mean logits) per flushed window) the selected tracks' masks are produced here, in one pass and one copy."""
+    sc, labels, inst = model.select_tracks(cls_clips)
+    Ho, Wo = int(image_size[0]), int(image_size[1])
+    res = {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels}
+    if not emit_masks:
+        return dict(res, pred_masks=[])
+    geometry = bool(model.geometry_output)
+    rows, geoms = inst, early.geom if early is not None else []
+    if early is not None and model.rle_output:
+        res["pred_rles"] = stitch_rles(inst, n_frames, (Ho, Wo), [(f, nf, n, R.positions_to_rles(pos, n_pos, (Ho, Wo), nf))
+                                                                  for f, nf, n, pos, n_pos in early.rle])
+    elif early is not None:
+        early.done.synchronize()                                   # (the geom tables ride on the mask copies' stream)
+        res["pred_masks"] = [early.hosts[i].view(torch.bool)[:n_frames] for i in inst]
+    else:
+        sel = sorted(set(inst))
+        rows = [sel.index(i) for i in inst]                        # rows of `out` = positions in sel
+        out = torch.zeros(len(sel), n_frames, Ho, Wo, dtype=torch.uint8, device=model.device)
+        sel_dev = torch.tensor(sel, dtype=torch.int32, device=model.device)
+        for f_off, m in windows:
+            cnt = sum(1 for i in sel if i < m.shape[0])           # sel is ascending: these are its first `cnt` entries
+            if cnt:
+                geoms.append((f_off, int(m.shape[1]), cnt,
+                              dense_masks(m, sel_dev[:cnt], model.cfg.match_stride, frame_hw, (Ho, Wo), geometry, out, f_off)))
+        hbuf = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)   # one D2H into pinned memory (pageable copies run at a fraction of PCIe)
+        hbuf.copy_(out, non_blocking=True)
+        torch.cuda.current_stream(model.device).synchronize()
+        host = hbuf.view(torch.bool)
+        if geometry:                                               # (the copies follow the masks' sync)
+            geoms = [(f, nf, cnt, g.cpu()) for f, nf, cnt, g in geoms]
+        if model.rle_output:                                       # no early path (unknown length): encode on the host
+            enc = [[R.encode_dense(fm.numpy()) for fm in host[p]] for p in range(len(sel))]
+            res["pred_rles"] = [enc[p] for p in rows]
+        else:
+            res["pred_masks"] = [host[p] for p in rows]
+    if geometry:
+        res.update(track_geometry(rows, n_frames, (Ho, Wo), geoms))
+    return res
+
+
+class ClipMerger:
+    """Incremental form of the clip loop's second half (mdqe/mdqe.py:337-366): tracker update per clip, window flushes,
+    final video merge.  The tracker runs on its own HIP stream so that its small kernels and per-clip host syncs overlap
+    with per-frame work the producer has already queued on the main stream."""
+
+    tracker_cls = OverTracker               # (tests without a GPU substitute a stand-in bank, tests/_standins.py)
+    EARLY_TRACKS = 48                       # tracks per video the early-mask path budgets pinned memory for
+
+    def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True, online=None, geometry=None):
+        self.model, self.frame_hw, self.out_size, self.mask_hw = model, frame_hw, out_size, mask_hw
+        self.emit_masks = emit_masks                # False: scores / labels only (ranks > 0 of a sharded video)
+        # boxes and areas of the final masks from the kernels that produce them (None: model.geometry_output; online sessions pass theirs)
+        self.geometry = bool(getattr(model, "geometry_output", False) if geometry is None else geometry)
+        # online ("masks" | "rle"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their RLE -- of every
+        # current track are built and appended to `emitted`; neither the logits nor a host buffer stay here (n_frames is unknown)
+        self.online = online
+        self.emitted = []
+        self.n_frames = n_frames                    # total frames of the video when known: enables the early mask path
+        self.early = None                           # EarlyMasks, from the first window the early path takes
+        # MODEL.MDQE.MERGE_ON_CPU (mdqe/mdqe.py:185-186,337,354-355; True in R50_ovis_720 / swinl_ovis): the device the window results
+        # wait on for the end of the video -- a memory-placement switch, the outputs are the same.  WHEN the final masks are produced is
+        # a separate choice (`model.early_masks`, default on for both settings since round 3): per flushed window, into pinned host
+        # buffers under the later windows' compute -- the window's stride-4 logits are then dropped at once under EITHER setting (nothing
+        # reads them again) -- or, off, in one pass + one copy at the end, which needs the logits of every window and keeps them in HBM
+        # whatever MERGE_ON_CPU says.
+        self.merge_on_cpu = bool(model.cfg.merge_on_cpu if model.merge_on_cpu is None else model.merge_on_cpu)
+        self.early_on = bool(getattr(model, "early_masks", True))
+        # The early path holds one pinned [n_frames, Ho, Wo] buffer per TRACK (the late path: per selected output).  Budget: an estimate
+        # of EARLY_TRACKS tracks must fit into MDQE_EARLY_PINNED_GB (default 24) of pinned host memory, else the late path is taken for
+        # this video (a 120-frame 360p video: 27.6 MB per track; one rank's view of a 1920-frame one: 442 MB per track).
+        if self.early_on and n_frames is not None:
+            per_track = int(n_frames) * int(out_size[0]) * int(out_size[1])
+            if per_track * self.EARLY_TRACKS > float(os.environ.get("MDQE_EARLY_PINNED_GB", "24")) * 2 ** 30:
+                self.early_on = False
+        self.dev = model.device
+        self.use_side = self.dev.type == "cuda"
+        self.main = torch.cuda.current_stream(self.dev) if self.use_side else None
+        if self.use_side and model._trk_stream is None:
+            model._trk_stream = torch.cuda.Stream(self.dev, priority=getattr(model, "trk_priority", 0))
+        self.side = model._trk_stream if self.use_side else None
+        self.side_is_current = False                # set by sharding.ReplayThread in its own thread
+        self.saved, self.tracker = 0, None
+        self.cls_clips, self.windows, self.f_off = [], [], 0    # windows: (f_off, mean logits) the late path still has to turn into masks
+        self.done = False
+
+    def feed(self, start, end, last, res):
+        """Returns True once the last clip has been consumed."""
+        return self.feed_many([(start, end, last, res)])
+
+    def feed_many(self, items):
+        """Clip results in global order.  The clips between two window flushes go to the tracker as ONE native call
+        (`OverTracker.update_many`: no Python between clips -- what keeps rank 0's replay of a gathered round off the critical
+        path of a sharded video).  Returns True once the last clip has been consumed."""
+        cfg = self.model.cfg
+        stride, win = cfg.clip_stride, cfg.n_frames_window_test
+        run = []
+        for it in items:
+            run.append(it)
+            start, last = it[0], it[2]
+            if last or (start + stride >= win * (self.saved + 1)):
+                self._consume(run, True, last)
+                run = []
+                if last:
+                    break
+        if run:
+            self._consume(run, False, False)
+        return self.done
+
+    def _consume(self, run, flush, last):
+        cfg = self.model.cfg
+        T, stride, win = cfg.n_frames_test, cfg.clip_stride, cfg.n_frames_window_test
+        # (a replay thread makes the tracker stream its current stream once instead of entering a stream context per clip)
+        ctx = torch.cuda.stream(self.side) if self.use_side and not self.side_is_current else contextlib.nullcontext()
+        with ctx:
+            clips, seen = [], set()
+            for start, end, _, res in run:
+                if self.use_side:
+                    ev = res.get("ready")
+                    if ev is None:
+                        self.side.wait_stream(self.main)
+                    elif id(ev) not in seen:            # the clips of one decoder batch share their event
+                        seen.add(id(ev))
+                        self.side.wait_event(ev)
+                    res["pred_masks"].record_stream(self.side)
+                clips.append(Clips(range(start, end), res))
+            if self.tracker is None:
+                self.tracker = self.tracker_cls(cfg.n_max_inst, T, win, stride, cfg.num_classes, cfg.mask_dim, cfg.hidden_dim,
+                                                self.mask_hw, self.dev, cfg.apply_cls_thres)
+            self.tracker.update_many(clips)
+            if flush:
+                c, m = self.tracker.get_result(is_last_clip=last)   # m: mean logits [n, F, Hm, Wm] of this window
+                self.cls_clips.append(c)
+                m = m.contiguous()
+                # only the late path keeps the window's stride-4 logits for the rest of the video (under either MERGE_ON_CPU setting)
+                if not self.emit_masks:
+                    pass
+                elif self.online:
+                    self.emitted.append(self._online_window(c, m))
+                elif self.use_side and self.n_frames is not None and (self.early_on or self.model.rle_output):
+                    self._early_masks(m)
+                else:
+                    self.windows.append((self.f_off, m))
+                self.f_off += m.shape[1]
+                self.saved += 1
+        self.done = self.done or bool(last)
+
+    def _early_masks(self, m):
+        """Final masks of EVERY instance tracked so far for the window just flushed (m: [n, F, Hm, Wm] mean logits), copied to
+        pinned host memory on a copy stream while later windows compute; finish() then only selects rows.  A few rows may
+        be produced in vain (instances that miss the final top-k).  One pinned buffer per track (no re-allocation as tracks
+        appear; the caching host allocator recycles the blocks of the previous call).  model.rle_output: the run boundaries instead."""
+        model = self.model
+        n, nf = int(m.shape[0]), int(m.shape[1])
+        Ho, Wo = int(self.out_size[0]), int(self.out_size[1])
+        cs = copy_stream(model)
+        if self.early is None:
+            self.early = EarlyMasks(done=torch.cuda.Event())
+        early = self.early
+        if not n:
+            return
+        args = (m, torch.arange(n, dtype=torch.int32, device=self.dev), model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry)
+        if model.rle_output:
+            pos, n_pos, geom = rle_positions(*args)
+            early.rle.append((self.f_off, nf, n, pos, n_pos))
+        else:
+            while len(early.hosts) < n:             # a new track: its own pinned [L, Ho, Wo] buffer, zero before its first window (:442)
+                hbuf = model.pinned_mask_buffer((int(self.n_frames), Ho, Wo))
+                if self.f_off > 0:
+                    hbuf[:self.f_off].zero_()
+                early.hosts.append(hbuf)
+            dev = torch.empty(n, nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
+            geom = to_host(cs, self.side, dev, [(h[self.f_off:self.f_off + nf], d) for h, d in zip(early.hosts, dev)], dense_masks(*args, dev, 0),
+                           early.done)
+        if self.geometry:
+            early.geom.append((self.f_off, nf, n, geom))
+
+    def _online_window(self, c, m):
+        """Online mode: the window just flushed (c: class rows [n, K] on the host, m: mean logits [n, F, Hm, Wm]) as a record --
+        frames, class rows, and the final masks of tracks 0..n-1: dense masks copied to a pinned host buffer on the copy stream
+        (`ready` fires when they and the geometry table are there), or their RLE dicts."""
+        n, nf = int(m.shape[0]), int(m.shape[1])
+        Ho, Wo = int(self.out_size[0]), int(self.out_size[1])
+        rec = {"frames": (self.f_off, self.f_off + nf), "cls_probs": c, "ready": None}
+        geom = torch.zeros((0, nf, 5), dtype=torch.int32) if self.geometry else None    # (the table of a window without tracks)
+        args = (m, torch.arange(n, dtype=torch.int32, device=self.dev), self.model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry)
+        if self.online == "rle":
+            rec["rles"] = []
+            if n:
+                pos, n_pos, geom = rle_positions(*args)
+                rec["rles"] = R.positions_to_rles(pos, n_pos, (Ho, Wo), nf)
+        elif not n:
+            rec["masks"] = torch.zeros((0, nf, Ho, Wo), dtype=torch.bool)
+        else:
+            cs = copy_stream(self.model)
+            dev = torch.empty(n, nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
+            geom = dense_masks(*args, dev, 0)
+            host = self.model.pinned_mask_buffer((n, nf, Ho, Wo))
+            rec["ready"] = torch.cuda.Event()
+            geom = to_host(cs, self.side, dev, [(host, dev)], geom, rec["ready"])
+            rec["masks"] = host.view(torch.bool)
+        if self.geometry:
+            rec["geom"] = geom
+        return rec
+
+    def finish(self):
+        if self.use_side:
+            self.main.wait_stream(self.side)
+            for _, m in self.windows:
+                m.record_stream(self.main)
+        return self.model.inference_video(self.out_size, self.cls_clips, self.windows, self.frame_hw, self.f_off, early=self.early,
+                                          emit_masks=self.emit_masks)

@@ -23,7 +23,8 @@ import torch.nn.functional as F
 from .config import MDQEConfig, from_d2_cfg
 from .engine import Engine
 from .params import ALIASES, full_manifest, random_state
-from .tracking import Clips, OverTracker
+from . import merge
+from .merge import ClipMerger      # (merge_clips, sharding and online resolve the class through THIS namespace at call time)
 
 
 def _register(root: nn.Module, dotted: str, tensor: torch.Tensor, buffer=False):
@@ -970,338 +971,15 @@ class MDQE(nn.Module):
         return [{"instances": res}]
 
     def select_tracks(self, cls_clips):
-        """mdqe/mdqe.py:431-454 without the masks: the video-level class scores of every track from its per-window class rows
-        (`cls_clips`, [tracks so far, K] per window) and their top-k -> (scores [k] host tensor, labels, track index of each output)."""
-        K = self.cfg.num_classes
-        total = cls_clips[-1].shape[0]
-        self.last_num_tracks = int(total)                      # tracks of the video just merged (diagnostics; bench.py reports it)
-        cc = torch.stack([torch.cat([c, c.new_zeros(total - c.shape[0], c.shape[1])]) for c in cls_clips])
-        out_cls = (0.75 * cc.mean(0) + 0.25 * cc.max(0)[0]).flatten().cpu()
-        k = min(max(int(out_cls.gt(0.05).sum()), 10), out_cls.numel())   # (the reference's topk(max(.,10)), :449-450, assumes >= 10 scores)
-        sc, ti = out_cls.topk(k, sorted=False)
-        labels = (ti % K).tolist()
-        inst = torch.div(ti, K, rounding_mode="floor").tolist()
-        return sc, labels, inst
+        """merge.select_tracks: (scores [k] host tensor, labels, track index of each output) of the video's top-k."""
+        self.last_num_tracks = int(cls_clips[-1].shape[0])     # tracks of the video just merged (diagnostics; bench.py reports it)
+        return merge.select_tracks(cls_clips, self.cfg.num_classes)
 
-    @staticmethod
-    def track_geometry(rows, n_frames, out_size, windows):
-        """Per output j the [n_frames] geometry of row rows[j] from the windows' geom tables: `windows` = (f_off, nf, n rows this window
-        holds, geom int32 [n, nf, 5] on the host).  Frames of windows in which the row did not exist yet stay empty -- zero boxes and
-        areas, like its masks (mdqe/mdqe.py:442).  -> {"pred_boxes": [float32 [n_frames, 4]], "pred_areas": [int64 [n_frames]]}."""
-        from . import rle as R
-        Ho, Wo = int(out_size[0]), int(out_size[1])
-        tabs = {}
-        for r in set(rows):
-            t = torch.tensor([0, Wo, Ho, -1, -1], dtype=torch.int32).repeat(int(n_frames), 1)
-            for f_off, nf, n_w, g in windows:
-                if r < n_w:
-                    t[f_off:f_off + nf] = torch.as_tensor(g)[r]
-            tabs[r] = R.geom_to_boxes(t)
-        return {"pred_boxes": [tabs[r][0].clone() for r in rows], "pred_areas": [tabs[r][1].clone() for r in rows]}
+    track_geometry = staticmethod(merge.track_geometry)
 
     def inference_video(self, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True):
-        """mdqe/mdqe.py:430-471.  The x4 aligned-bilinear up-sampling, sigmoid, crop (:357-358), nearest resize to the
-        original size and the 0.5 threshold (:458-462) run as ONE kernel per window; windows in which an instance did not
-        exist yet stay zero (:442).  `early` (ClipMerger, CUDA): the masks of every tracked instance were already produced
-        and copied to pinned host memory window by window, under the later windows' compute; only the selection is left."""
-        from . import ops
-        sc, labels, inst = self.select_tracks(cls_clips)
-        sel = sorted(set(inst))
-        Ho, Wo = int(image_size[0]), int(image_size[1])
-        if not emit_masks:
-            return {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels, "pred_masks": []}
-        geometry = bool(self.geometry_output)
-        if early is not None and geometry:
-            early["done"].synchronize()                            # (the geom tables ride on the mask copies' stream)
-            geo = self.track_geometry(inst, n_frames, (Ho, Wo), early["geom"])
-        else:
-            geo = {}
-        if early is not None and self.rle_output:
-            from . import rle as R
-            empty = {"size": [Ho, Wo], "counts": R.counts_to_strings([Ho * Wo], [1])[0].decode("utf-8")}
-            per_inst = {i: [dict(empty) for _ in range(n_frames)] for i in sel}     # before an instance's first window: empty masks (:442)
-            for f_off, nf, n_w, pos, n_pos in early["rle"]:
-                counts, lengths = R.positions_to_counts(pos, n_pos, Ho * Wo)
-                strs = R.counts_to_strings(counts, lengths)
-                for i in sel:
-                    if i < n_w:
-                        for f in range(nf):
-                            per_inst[i][f_off + f] = {"size": [Ho, Wo], "counts": strs[i * nf + f].decode("utf-8")}
-            return {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels,
-                    "pred_rles": [per_inst[i] for i in inst], **geo}
-        if early is not None:
-            early["done"].synchronize()
-            hosts = early["host"]                                  # per instance: [n_frames, Ho, Wo] uint8, pinned
-            return {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels,
-                    "pred_masks": [hosts[i].view(torch.bool)[:n_frames] for i in inst], **geo}
-        out = torch.zeros(len(sel), n_frames, Ho, Wo, dtype=torch.uint8, device=self.device)
-        sel_dev = torch.tensor(sel, dtype=torch.int32, device=self.device)
-        geoms = []                                                 # per window: (f_off, frames, rows written, geom on the device)
-        for f_off, m in windows:
-            cnt = sum(1 for i in sel if i < m.shape[0])       # sel is ascending: these are its first `cnt` entries
-            if cnt and geometry and out.is_cuda:
-                _, g = ops.final_masks_geom(m, sel_dev[:cnt], self.cfg.match_stride, frame_hw[0], frame_hw[1], Ho, Wo, out, f_off)
-                geoms.append((f_off, int(m.shape[1]), cnt, g))
-            elif cnt:
-                ops.final_masks(m, sel_dev[:cnt], self.cfg.match_stride, frame_hw[0], frame_hw[1], Ho, Wo, out, f_off)
-        if out.is_cuda:                                            # one D2H into pinned memory (pageable copies run at a fraction of PCIe)
-            hbuf = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)
-            hbuf.copy_(out, non_blocking=True)
-            torch.cuda.current_stream(self.device).synchronize()
-            host = hbuf.view(torch.bool)
-        else:
-            host = out.view(torch.bool)
-        pos = {i: p for p, i in enumerate(sel)}
-        if geometry and out.is_cuda:                               # rows of `out` = positions in sel; the copies follow the masks' sync
-            geo = self.track_geometry([pos[i] for i in inst], n_frames, (Ho, Wo),
-                                      [(f, nf, cnt, g.view(cnt, nf, 5).cpu()) for f, nf, cnt, g in geoms])
-        elif geometry:                                             # no device window: from the masks, on the host
-            from . import rle as R
-            bx, ar = R.geom_to_boxes(R.geometry_dense(host))
-            geo = {"pred_boxes": [bx[pos[i]].clone() for i in inst], "pred_areas": [ar[pos[i]].clone() for i in inst]}
-        if self.rle_output:                                        # no early path (CPU device / unknown length): encode on the host
-            from . import rle as R
-            enc = {i: [R.encode_dense(fm.numpy()) for fm in host[pos[i]]] for i in sel}
-            return {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels, "pred_rles": [enc[i] for i in inst], **geo}
-        return {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels,
-                "pred_masks": [host[pos[i]] for i in inst], **geo}
-
-
-class ClipMerger:
-    """Incremental form of the clip loop's second half (mdqe/mdqe.py:337-366): tracker update per clip, window flushes,
-    final video merge.  The tracker runs on its own HIP stream so that its small kernels and per-clip host syncs overlap
-    with per-frame work the producer has already queued on the main stream."""
-
-    tracker_cls = OverTracker               # (tests without a GPU substitute a stand-in bank, tests/_standins.py)
-    EARLY_TRACKS = 48                       # tracks per video the early-mask path budgets pinned memory for
-
-    def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True, online=None, geometry=None):
-        self.model, self.frame_hw, self.out_size, self.mask_hw = model, frame_hw, out_size, mask_hw
-        self.emit_masks = emit_masks                # False: scores / labels only (ranks > 0 of a sharded video)
-        # boxes and areas of the final masks from the kernels that produce them (None: model.geometry_output; online sessions pass theirs)
-        self.geometry = bool(getattr(model, "geometry_output", False) if geometry is None else geometry)
-        # online ("masks" | "rle"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their RLE -- of every
-        # current track are built and appended to `emitted`; neither the logits nor a host buffer stay here (n_frames is unknown)
-        self.online = online
-        self.emitted = []
-        self.n_frames = n_frames                    # total frames of the video when known: enables the early mask path
-        self.early = None
-        # MODEL.MDQE.MERGE_ON_CPU (mdqe/mdqe.py:185-186,337,354-355; True in R50_ovis_720 / swinl_ovis): the device the window results
-        # wait on for the end of the video -- a memory-placement switch, the outputs are the same.  WHEN the final masks are produced is
-        # a separate choice (`model.early_masks`, default on for both settings since round 3): per flushed window, into pinned host
-        # buffers under the later windows' compute -- the window's stride-4 logits are then dropped at once under EITHER setting (nothing
-        # reads them again) -- or, off, in one pass + one copy at the end, which needs the logits of every window and keeps them in HBM
-        # whatever MERGE_ON_CPU says.
-        self.merge_on_cpu = bool(model.cfg.merge_on_cpu if model.merge_on_cpu is None else model.merge_on_cpu)
-        self.early_on = bool(getattr(model, "early_masks", True))
-        # The early path holds one pinned [n_frames, Ho, Wo] buffer per TRACK (the late path: per selected output).  Budget: an estimate
-        # of EARLY_TRACKS tracks must fit into MDQE_EARLY_PINNED_GB (default 24) of pinned host memory, else the late path is taken for
-        # this video (a 120-frame 360p video: 27.6 MB per track; one rank's view of a 1920-frame one: 442 MB per track).
-        if self.early_on and n_frames is not None:
-            per_track = int(n_frames) * int(out_size[0]) * int(out_size[1])
-            if per_track * self.EARLY_TRACKS > float(os.environ.get("MDQE_EARLY_PINNED_GB", "24")) * 2 ** 30:
-                self.early_on = False
-        self.dev = model.device
-        self.use_side = self.dev.type == "cuda"
-        self.main = torch.cuda.current_stream(self.dev) if self.use_side else None
-        if self.use_side and model._trk_stream is None:
-            model._trk_stream = torch.cuda.Stream(self.dev, priority=getattr(model, "trk_priority", 0))
-        self.side = model._trk_stream if self.use_side else None
-        self.side_is_current = False                # set by sharding.ReplayThread in its own thread
-        self.saved, self.tracker = 0, None
-        self.cls_clips, self.windows, self.f_off = [], [], 0
-        self.done = False
-
-    def feed(self, start, end, last, res):
-        """Returns True once the last clip has been consumed."""
-        return self.feed_many([(start, end, last, res)])
-
-    def feed_many(self, items):
-        """Clip results in global order.  The clips between two window flushes go to the tracker as ONE native call
-        (`OverTracker.update_many`: no Python between clips -- what keeps rank 0's replay of a gathered round off the critical
-        path of a sharded video).  Returns True once the last clip has been consumed."""
-        cfg = self.model.cfg
-        stride, win = cfg.clip_stride, cfg.n_frames_window_test
-        run = []
-        for it in items:
-            run.append(it)
-            start, last = it[0], it[2]
-            if last or (start + stride >= win * (self.saved + 1)):
-                self._consume(run, True, last)
-                run = []
-                if last:
-                    break
-        if run:
-            self._consume(run, False, False)
-        return self.done
-
-    def _consume(self, run, flush, last):
-        cfg = self.model.cfg
-        T, stride, win = cfg.n_frames_test, cfg.clip_stride, cfg.n_frames_window_test
-        # (a replay thread makes the tracker stream its current stream once instead of entering a stream context per clip)
-        ctx = torch.cuda.stream(self.side) if self.use_side and not self.side_is_current else contextlib.nullcontext()
-        with ctx:
-            clips, seen = [], set()
-            for start, end, _, res in run:
-                if self.use_side:
-                    ev = res.get("ready")
-                    if ev is None:
-                        self.side.wait_stream(self.main)
-                    elif id(ev) not in seen:            # the clips of one decoder batch share their event
-                        seen.add(id(ev))
-                        self.side.wait_event(ev)
-                    res["pred_masks"].record_stream(self.side)
-                clips.append(Clips(range(start, end), res))
-            if self.tracker is None:
-                self.tracker = self.tracker_cls(cfg.n_max_inst, T, win, stride, cfg.num_classes, cfg.mask_dim, cfg.hidden_dim,
-                                                self.mask_hw, self.dev, cfg.apply_cls_thres)
-            self.tracker.update_many(clips)
-            if flush:
-                c, m = self.tracker.get_result(is_last_clip=last)   # m: mean logits [n, F, Hm, Wm] of this window
-                self.cls_clips.append(c)
-                m = m.contiguous()
-                if not self.emit_masks:
-                    self.windows.append((self.f_off, None))
-                elif self.online:
-                    self.emitted.append(self._online_window(c, m))
-                    self.windows.append((self.f_off, None))
-                elif self.use_side and self.n_frames is not None and (self.early_on or self.model.rle_output):
-                    self._early_masks(m)
-                    # inference_video returns from its `early` branch and never reads `windows` then: the stride-4 logits of a flushed
-                    # window are not kept for the rest of the video under either MERGE_ON_CPU setting (round 3 held them for nothing)
-                    self.windows.append((self.f_off, None))
-                else:
-                    self.windows.append((self.f_off, m))
-                self.f_off += m.shape[1]
-                self.saved += 1
-        self.done = self.done or bool(last)
-
-    def _early_masks(self, m):
-        """Final masks of EVERY instance tracked so far for the window just flushed (m: [n, F, Hm, Wm] mean logits), copied to
-        pinned host memory on a copy stream while later windows compute; finish() then only selects rows.  A few rows may
-        be produced in vain (instances that miss the final top-k).  One pinned buffer per track (no re-allocation as tracks
-        appear; the caching host allocator recycles the blocks of the previous call)."""
-        from . import ops
-        model = self.model
-        n, nf = int(m.shape[0]), int(m.shape[1])
-        Ho, Wo = int(self.out_size[0]), int(self.out_size[1])
-        if model._copy_stream is None:
-            model._copy_stream = torch.cuda.Stream(self.dev)
-        cs = model._copy_stream
-        if self.early is None:
-            self.early = {"host": [], "windows": [], "done": torch.cuda.Event(), "rle": [], "geom": []}
-        if model.rle_output:                        # run boundaries instead of dense masks: KBs instead of MBs per window
-            if n:
-                idx = torch.arange(n, dtype=torch.int32, device=self.dev)
-                cap = 4 * (Ho + Wo) + 64                # a blob crosses a column twice: generous for anything mask-like
-                while True:
-                    if self.geometry:
-                        pos, n_pos, geom = ops.final_masks_rle_geom(m, idx, model.cfg.match_stride, self.frame_hw[0], self.frame_hw[1],
-                                                                    Ho, Wo, cap)
-                    else:
-                        pos, n_pos = ops.final_masks_rle(m, idx, model.cfg.match_stride, self.frame_hw[0], self.frame_hw[1], Ho, Wo, cap)
-                    mx = int(n_pos.max())               # (sync on the tracker stream; the window's logits are final here)
-                    if mx <= cap:
-                        break
-                    cap = mx
-                self.early["rle"].append((self.f_off, nf, n, pos[:, :max(mx, 1)].cpu().numpy(), n_pos.cpu().numpy()))
-                if self.geometry:
-                    self.early["geom"].append((self.f_off, nf, n, geom.view(n, nf, 5).cpu()))
-            self.early["windows"].append((self.f_off, nf, n))
-            return
-        hosts = self.early["host"]
-        while len(hosts) < n:                       # a new track: its own pinned [L, Ho, Wo] buffer, zero before its first window (:442)
-            hbuf = model.pinned_mask_buffer((int(self.n_frames), Ho, Wo))
-            if self.f_off > 0:
-                hbuf[:self.f_off].zero_()
-            hosts.append(hbuf)
-        if n:
-            dev = torch.empty(n, nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
-            idx = torch.arange(n, dtype=torch.int32, device=self.dev)
-            if self.geometry:                       # the window's [n, nf, 5] table follows its masks to the host on the same stream / event
-                _, geom = ops.final_masks_geom(m, idx, model.cfg.match_stride, self.frame_hw[0], self.frame_hw[1], Ho, Wo, dev, 0)
-                hgeom = torch.empty((n, nf, 5), dtype=torch.int32, pin_memory=True)
-                self.early["geom"].append((self.f_off, nf, n, hgeom))
-            else:
-                ops.final_masks(m, idx, model.cfg.match_stride, self.frame_hw[0], self.frame_hw[1], Ho, Wo, dev, 0)
-            cs.wait_stream(self.side)
-            with torch.cuda.stream(cs):
-                for i in range(n):
-                    hosts[i][self.f_off:self.f_off + nf].copy_(dev[i], non_blocking=True)
-                dev.record_stream(cs)
-                if self.geometry:
-                    hgeom.copy_(geom.view(n, nf, 5), non_blocking=True)
-                    geom.record_stream(cs)
-                self.early["done"].record(cs)
-        self.early["windows"].append((self.f_off, nf, n))
-
-    def _online_window(self, c, m):
-        """Online mode: the window just flushed (c: class rows [n, K] on the host, m: mean logits [n, F, Hm, Wm]) as a record --
-        frames, class rows, and the final masks of tracks 0..n-1 by the kernels of the early path: dense masks copied to a pinned host
-        buffer on the copy stream (`ready` fires when they are there), or the RLE strings of `inference_video`'s early branch."""
-        from . import ops
-        model = self.model
-        n, nf = int(m.shape[0]), int(m.shape[1])
-        Ho, Wo = int(self.out_size[0]), int(self.out_size[1])
-        ms, (fh, fw) = model.cfg.match_stride, self.frame_hw
-        rec = {"frames": (self.f_off, self.f_off + nf), "cls_probs": c, "ready": None}
-        if self.geometry:
-            rec["geom"] = torch.zeros((0, nf, 5), dtype=torch.int32)     # (no tracks yet; replaced below)
-        idx = torch.arange(n, dtype=torch.int32, device=self.dev)
-        if self.online == "rle":
-            from . import rle as R
-            rles = []
-            if n:
-                cap = 4 * (Ho + Wo) + 64
-                while True:
-                    if self.geometry:
-                        pos, n_pos, geom = ops.final_masks_rle_geom(m, idx, ms, fh, fw, Ho, Wo, cap)
-                    else:
-                        pos, n_pos = ops.final_masks_rle(m, idx, ms, fh, fw, Ho, Wo, cap)
-                    mx = int(n_pos.max())
-                    if mx <= cap:
-                        break
-                    cap = mx
-                if self.geometry:
-                    rec["geom"] = geom.view(n, nf, 5).cpu()
-                counts, lengths = R.positions_to_counts(pos[:, :max(mx, 1)].cpu().numpy(), n_pos.cpu().numpy(), Ho * Wo)
-                strs = R.counts_to_strings(counts, lengths)
-                rles = [[{"size": [Ho, Wo], "counts": strs[i * nf + f].decode("utf-8")} for f in range(nf)] for i in range(n)]
-            rec["rles"] = rles
-            return rec
-        if not n:
-            rec["masks"] = torch.zeros((0, nf, Ho, Wo), dtype=torch.bool)
-            return rec
-        if model._copy_stream is None:
-            model._copy_stream = torch.cuda.Stream(self.dev)
-        cs = model._copy_stream
-        dev = torch.empty(n, nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
-        if self.geometry:
-            _, geom = ops.final_masks_geom(m, idx, ms, fh, fw, Ho, Wo, dev, 0)
-            rec["geom"] = torch.empty((n, nf, 5), dtype=torch.int32, pin_memory=True)
-        else:
-            ops.final_masks(m, idx, ms, fh, fw, Ho, Wo, dev, 0)
-        host = model.pinned_mask_buffer((n, nf, Ho, Wo))
-        cs.wait_stream(self.side)
-        with torch.cuda.stream(cs):
-            host.copy_(dev, non_blocking=True)
-            dev.record_stream(cs)
-            if self.geometry:
-                rec["geom"].copy_(geom.view(n, nf, 5), non_blocking=True)
-                geom.record_stream(cs)
-            rec["ready"] = torch.cuda.Event()
-            rec["ready"].record(cs)
-        rec["masks"] = host.view(torch.bool)
-        return rec
-
-    def finish(self):
-        if self.use_side:
-            self.main.wait_stream(self.side)
-            for _, m in self.windows:
-                if m is not None:
-                    m.record_stream(self.main)
-        return self.model.inference_video(self.out_size, self.cls_clips, self.windows, self.frame_hw, self.f_off, early=self.early,
-                                          emit_masks=self.emit_masks)
+        """mdqe/mdqe.py:430-471: the video's result from its flushed windows (merge.video_result)."""
+        return merge.video_result(self, image_size, cls_clips, windows, frame_hw, n_frames, early=early, emit_masks=emit_masks)
 
 
 class MDQE_MI355X(MDQE):

@@ -258,21 +258,11 @@ class OnlineVideo:
         if self.geometry:
             res.update(self.model.track_geometry(list(inst), self.received, (Ho, Wo), self.geoms))
         if self.keep:
-            sel = sorted(set(inst))
+            from . import merge
+            wins = [(w.frames[0], w.frames[1] - w.frames[0], len(w.track_ids), w.rles if self.emit == "rle" else w.masks) for w in self.kept]
             if self.emit == "rle":
-                from . import rle as R
-                empty = {"size": [Ho, Wo], "counts": R.counts_to_strings([Ho * Wo], [1])[0].decode("utf-8")}
-                per = {i: [] for i in sel}
-                for w in self.kept:
-                    nf = w.frames[1] - w.frames[0]
-                    for i in sel:            # before a track's first window: empty masks (mdqe/mdqe.py:442)
-                        per[i] += w.rles[i] if i < len(w.rles) else [dict(empty) for _ in range(nf)]
-                res["pred_rles"] = [per[i] for i in inst]
+                res["pred_rles"] = merge.stitch_rles(list(inst), self.received, (Ho, Wo), wins)
             else:
-                per = {}
-                for i in sel:
-                    per[i] = torch.cat([w.masks[i] if i < w.masks.shape[0] else
-                                        torch.zeros((w.frames[1] - w.frames[0], Ho, Wo), dtype=torch.bool) for w in self.kept])
-                res["pred_masks"] = [per[i] for i in inst]
+                res["pred_masks"] = merge.stitch(list(inst), self.received, wins, lambda k: torch.zeros((k, Ho, Wo), dtype=torch.bool), torch.cat)
         self._result = res
         return res

@@ -542,11 +542,24 @@ def sample_levels_mean(tokens, coords, shapes, starts, out=None):
     return out
 
 
-def final_masks(logits, inst_idx, factor, h, w, Ho, Wo, out, f_off):
-    """logits [n,Fw,Hm,Wm]; inst_idx int32 CUDA [n_sel]; out uint8 [n_sel_total, L, Ho, Wo] (rows 0..n_sel-1 written)."""
+def _final_mask_args(logits, inst_idx, check_idx, cap=None):
+    """The preamble of the four final-mask wrappers -> (n_sel, Fw, Hm, Wm) and, with `cap`, the RLE buffers pos, n_pos.  The two geometry
+    forms validate inst_idx, the two older ones pass it through."""
     _chk(logits, "logits")
     n, Fw, Hm, Wm = logits.shape
-    check(lib.mdqe_final_masks_u8(ptr(logits), int(inst_idx.numel()), ptr(inst_idx), Fw, Hm, Wm, factor, h, w, Ho, Wo, ptr(out),
+    if check_idx:
+        _chk(inst_idx, "inst_idx", torch.int32)
+    k = int(inst_idx.numel())
+    if cap is None:
+        return k, Fw, Hm, Wm
+    return (k, Fw, Hm, Wm, torch.empty(k * Fw, cap, dtype=torch.int32, device=logits.device),
+            torch.empty(k * Fw, dtype=torch.int32, device=logits.device))
+
+
+def final_masks(logits, inst_idx, factor, h, w, Ho, Wo, out, f_off):
+    """logits [n,Fw,Hm,Wm]; inst_idx int32 CUDA [n_sel]; out uint8 [n_sel_total, L, Ho, Wo] (rows 0..n_sel-1 written)."""
+    k, Fw, Hm, Wm = _final_mask_args(logits, inst_idx, False)
+    check(lib.mdqe_final_masks_u8(ptr(logits), k, ptr(inst_idx), Fw, Hm, Wm, factor, h, w, Ho, Wo, ptr(out),
                                   out.stride(0), f_off, cur_stream()), "final_masks")
     return out
 
@@ -554,10 +567,7 @@ def final_masks(logits, inst_idx, factor, h, w, Ho, Wo, out, f_off):
 def final_masks_geom(logits, inst_idx, factor, h, w, Ho, Wo, out, f_off, geom=None):
     """ops.final_masks plus, from the same sweep, geom int32 [n_sel*Fw, 5]: row k*Fw+f = (area, xmin, ymin, xmax, ymax) of the set
     pixels of (row k, window frame f), inclusive; an empty mask is (0, Wo, Ho, -1, -1).  `geom`: a buffer to write into (fully overwritten, whatever it held).  -> (out, geom)."""
-    _chk(logits, "logits")
-    n, Fw, Hm, Wm = logits.shape
-    k = int(inst_idx.numel())
-    _chk(inst_idx, "inst_idx", torch.int32)
+    k, Fw, Hm, Wm = _final_mask_args(logits, inst_idx, True)
     if (not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 4 or out.shape[0] < k or (out.shape[0] and not out[0].is_contiguous())
             or tuple(out.shape[2:]) != (Ho, Wo) or f_off < 0 or f_off + Fw > out.shape[1]):
         raise RuntimeError("final_masks_geom: out must be CUDA uint8 [>= n_sel, >= f_off + Fw, Ho, Wo]")
@@ -670,19 +680,6 @@ def image_final_masks(logits, idx, factor, h, w, Ho, Wo):
     return out
 
 
-def final_masks_rle(logits, inst_idx, factor, h, w, Ho, Wo, cap):
-    """logits [n,Fw,Hm,Wm]; inst_idx int32 CUDA [n_sel] -> (pos int32 [n_sel*Fw, cap], n_pos int32 [n_sel*Fw]): column-major
-    positions at which each final mask changes value (ops.final_masks never materialised)."""
-    _chk(logits, "logits")
-    n, Fw, Hm, Wm = logits.shape
-    k = int(inst_idx.numel())
-    pos = torch.empty(k * Fw, cap, dtype=torch.int32, device=logits.device)
-    n_pos = torch.empty(k * Fw, dtype=torch.int32, device=logits.device)
-    check(lib.mdqe_final_masks_rle(ptr(logits), k, ptr(inst_idx), Fw, Hm, Wm, factor, h, w, Ho, Wo, cap, ptr(pos), ptr(n_pos),
-                                   cur_stream()), "final_masks_rle")
-    return pos, n_pos
-
-
 def _geom_rows(geom, rows, device):
     if geom is None:
         return torch.empty(rows, 5, dtype=torch.int32, device=device)
@@ -692,14 +689,18 @@ def _geom_rows(geom, rows, device):
     return geom
 
 
+def final_masks_rle(logits, inst_idx, factor, h, w, Ho, Wo, cap):
+    """logits [n,Fw,Hm,Wm]; inst_idx int32 CUDA [n_sel] -> (pos int32 [n_sel*Fw, cap], n_pos int32 [n_sel*Fw]): column-major
+    positions at which each final mask changes value (ops.final_masks never materialised)."""
+    k, Fw, Hm, Wm, pos, n_pos = _final_mask_args(logits, inst_idx, False, cap)
+    check(lib.mdqe_final_masks_rle(ptr(logits), k, ptr(inst_idx), Fw, Hm, Wm, factor, h, w, Ho, Wo, cap, ptr(pos), ptr(n_pos),
+                                   cur_stream()), "final_masks_rle")
+    return pos, n_pos
+
+
 def final_masks_rle_geom(logits, inst_idx, factor, h, w, Ho, Wo, cap, geom=None):
     """ops.final_masks_rle plus the geom rows of ops.final_masks_geom from the same sweep -> (pos, n_pos, geom)."""
-    _chk(logits, "logits")
-    n, Fw, Hm, Wm = logits.shape
-    k = int(inst_idx.numel())
-    pos = torch.empty(k * Fw, cap, dtype=torch.int32, device=logits.device)
-    n_pos = torch.empty(k * Fw, dtype=torch.int32, device=logits.device)
-    _chk(inst_idx, "inst_idx", torch.int32)
+    k, Fw, Hm, Wm, pos, n_pos = _final_mask_args(logits, inst_idx, True, cap)
     geom = _geom_rows(geom, k * Fw, logits.device)
     check(lib.mdqe_final_masks_rle_geom(ptr(logits), k, ptr(inst_idx), Fw, Hm, Wm, factor, h, w, Ho, Wo, cap, ptr(pos), ptr(n_pos),
                                         ptr(geom), cur_stream()), "final_masks_rle_geom")

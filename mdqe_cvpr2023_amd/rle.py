@@ -187,6 +187,21 @@ def positions_to_counts(pos, n_pos, total):
     return runs[keep], lengths
 
 
+def positions_to_rles(pos, n_pos, size, frames):
+    """ops.final_masks_rle's pos [tracks * frames, cap], n_pos [tracks * frames] (on the host) of (H, W) masks -> per track, per frame
+    {"size", "counts": str}."""
+    H, W = int(size[0]), int(size[1])
+    counts, lengths = positions_to_counts(pos, n_pos, H * W)
+    strs = counts_to_strings(counts, lengths)
+    return [[{"size": [H, W], "counts": s.decode("utf-8")} for s in strs[i:i + frames]] for i in range(0, len(strs), frames)]
+
+
+def empty_rle(size):
+    """The RLE dict of an all-zero (H, W) mask: one run of H * W zeros."""
+    H, W = int(size[0]), int(size[1])
+    return {"size": [H, W], "counts": counts_to_strings([H * W], [1])[0].decode("utf-8")}
+
+
 def encode_dense(mask):
     """Host fallback: one [H,W] boolean mask (numpy / CPU tensor) -> {"size", "counts": str}, pycocotools-style."""
     m = np.asarray(mask).astype(np.uint8)

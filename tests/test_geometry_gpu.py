@@ -301,7 +301,7 @@ def test_zeros_before_a_tracks_first_window_late_and_early_paths(small, rle):
             cls_clips = [w[4] for w in wins]
             _, _, inst = model.select_tracks(cls_clips)
             assert set(inst) == {0, 1, 2, 3, 4}
-            # late path: inference_video's loop over the windows with f_off
+            # late path: merge.video_result's loop over the windows with f_off
             late = model.inference_video((Ho, Wo), cls_clips, [(w[0], w[3].cuda()) for w in wins], frame_hw, L)
             _check_hand(late, wins, frame_hw, Ho, Wo, inst)
             # early path: ClipMerger._early_masks per flushed window, finish() selects
@@ -314,10 +314,9 @@ def test_zeros_before_a_tracks_first_window_late_and_early_paths(small, rle):
                     mg._early_masks(m)
                 m.record_stream(mg.side)
                 mg.cls_clips.append(c)
-                mg.windows.append((mg.f_off, None))
                 mg.f_off += nf
             early = mg.finish()
-            assert mg.early is not None and len(mg.early["geom"]) == len(wins)
+            assert mg.early is not None and len(mg.early.geom) == len(wins)
             _check_hand(early, wins, frame_hw, Ho, Wo, inst)
             _equal_results(early, late, BASE | GEO | {"pred_rles" if rle else "pred_masks"})
     finally:

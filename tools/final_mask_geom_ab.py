@@ -1,4 +1,6 @@
-"""A/B of the final-mask kernels with and without geometry on one shipped 360p tracker window (15 tracks x 30 frames)."""
+"""A/B of the final-mask kernels with and without geometry on one tracker window of 15 tracks: the shipped 360p one (30 frames of
+360 x 640) or, `final_mask_geom_ab.py OUT H W FRAMES`, one of FRAMES frames of H x W (output size = frame size).  MDQE_HIP_LIB selects the
+library build, so two builds are compared by running the tool once per build."""
 import os, sys, statistics
 import torch
 import torch.nn.functional as F
@@ -6,7 +8,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from mdqe_cvpr2023_amd import ops
 
-n, Fw, Hm, Wm, h, w, Ho, Wo = 15, 30, 96, 160, 360, 640, 360, 640
+h, w, Fw = (int(v) for v in sys.argv[2:5]) if len(sys.argv) > 4 else (360, 640, 30)
+n, Hm, Wm, Ho, Wo = 15, (h + 31) // 32 * 8, (w + 31) // 32 * 8, h, w          # (the stride-4 map of the frame padded to a multiple of 32)
 g = torch.Generator().manual_seed(0)
 lg = (F.interpolate(torch.randn(n, Fw, 12, 20, generator=g) * 3, size=(Hm, Wm), mode="bilinear") - 1.0).contiguous().cuda()
 idx = torch.arange(n, dtype=torch.int32, device="cuda")
@@ -55,7 +58,8 @@ res = {name: [] for name, _ in variants}
 for r in range(7):
     for name, fn in variants:
         res[name].append(timed(fn, reps[name]))
-lines = ["# one 360p tracker window: n = 15 tracks x 30 frames, Hm x Wm = 96 x 160, h, w = Ho, Wo = 360, 640 (450 masks, 103.7 MB of uint8)",
+lines = ["# one tracker window: n = %d tracks x %d frames, Hm x Wm = %d x %d, h, w = Ho, Wo = %d, %d (%d masks, %.1f MB of uint8)"
+         % (n, Fw, Hm, Wm, Ho, Wo, n * Fw, n * Fw * Ho * Wo / 1e6),
          "# us per call, device events around >= 0.25 s of back-to-back launches, 7 alternations of all variants in one process",
          "# set pixels: %.1f %% of all; empty masks: %d of %d" % (100.0 * float(ar.sum()) / (n * Fw * Ho * Wo), int((ar == 0).sum()), n * Fw),
          "%-46s %6s %9s %9s %9s" % ("variant", "reps", "median", "min", "max")]
