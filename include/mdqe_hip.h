@@ -453,6 +453,18 @@ int mdqe_final_masks_u8_geom(const float* logits, int n_sel, const int* inst_idx
 int mdqe_final_masks_rle_geom(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
                               int h, int w, int Ho, int Wo, int cap, int* pos, int* n_pos, int* geom, void* stream);
 
+/* The other form of a window's final masks: ONE plane per frame that says which track owns each pixel (the form of DAVIS / VIPSeg
+ * PNGs, what a viewer paints from in a single pass).  With v_k the up-sampled logit of map inst_idx_dev[k] at the pixel and b_k its
+ * final-mask bit (the same expressions as the entry points above: one definition of both), out[f_off + f, Y, X] = 0 if no b_k is set,
+ * else inst_idx_dev[k*] + 1 for the smallest k* among the rows with b_k set and v_k equal to the largest v among them.  So out != 0
+ * exactly on the union of the dense masks, and a label names a track whose dense mask holds the pixel.  out uint8 [>= f_off + Fw, Ho,
+ * Wo]; n_sel <= 255 and every inst_idx_dev[k] < 255 (the caller's part: the indices live on the device).  geom: NULL, or int32
+ * [n_sel*Fw, 5] with the geometry of each label's VISIBLE region, row k*Fw+f, layout and empty convention of mdqe_final_masks_u8_geom;
+ * fully overwritten on every call, integers, identical from run to run.  Unlike the mask entry points, n_sel == 0 with Fw > 0 writes
+ * zeros to the Fw frames (a window without tracks is all background).  Never allocates, never synchronises. */
+int mdqe_final_label_map_u8(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
+                            int h, int w, int Ho, int Wo, unsigned char* out, int f_off, int* geom, void* stream);
+
 /* ---- COCO single-image branch, after the decoder (MDQE.inference_image, mdqe/mdqe.py:486-556), on the centre frame's
  * low-resolution logits [n,Hm,Wm]; aligned_bilinear x`factor` in closed form, crop [:h,:w].
  * stats[k] = {sum(sigmoid*[sigmoid>0.5]), count(sigmoid>0.5), xmin, ymin, xmax, ymax of (logit > 0)} (:512-516, :526;

@@ -1,6 +1,7 @@
 // Decoder-side kernels of the MDQE path for gfx950: small-sequence multi-head attention, grid-guided
 // query selection, multi-level content sampling, and the fused final-mask kernel.
 #include "common.h"
+#include <cstdlib>
 
 // ------------------------------------------------------------------------------------------------
 // nn.MultiheadAttention core for short sequences (Q <= 256 tokens, head dim D <= 64, D % 4 == 0):
@@ -338,19 +339,38 @@ extern "C" int mdqe_sample_levels_mean_f32(const float* tokens, int NI, long N, 
 // aligned_bilinear (util/misc.py:485-507) in closed form: pixel p reads source (max(p - f/2, 0))/f, clamped to the map.
 // logits [n, F, Hm, Wm] (mean logits of one tracker window); out uint8 [n, F_total, Ho, Wo] written at frame f_off.
 // ------------------------------------------------------------------------------------------------
-// one output pixel of the final mask (shared by the dense and the RLE form: identical arithmetic, identical bits)
-__device__ __forceinline__ int final_mask_pixel(const float* __restrict__ m, int Hm, int Wm, int factor, int h, int w, float sy_scale,
-                                                float sx_scale, int Y, int X) {
+// one output pixel of the final mask (shared by the dense, the RLE and the label-map form: identical arithmetic, identical bits), in
+// three steps: where the pixel reads (the same for every map of a window), the up-sampled logit there, and the threshold on it
+struct MaskTaps { int y0, y1, x0, x1; float ly, lx; };
+
+__device__ __forceinline__ MaskTaps final_mask_taps(int Hm, int Wm, int factor, int h, int w, float sy_scale, float sx_scale, int Y, int X) {
   const int sy = min((int)floorf(Y * sy_scale), h - 1), sx = min((int)floorf(X * sx_scale), w - 1);
   const float fy = (float)max(sy - factor / 2, 0) / (float)factor, fx = (float)max(sx - factor / 2, 0) / (float)factor;
   const int y0 = min((int)fy, Hm - 1), x0 = min((int)fx, Wm - 1);
   const int y1 = min(y0 + 1, Hm - 1), x1 = min(x0 + 1, Wm - 1);
-  const float ly = fy - y0, lx = fx - x0;
-  const float top = m[y0 * Wm + x0] * (1.f - lx) + m[y0 * Wm + x1] * lx;
-  const float bot = m[y1 * Wm + x0] * (1.f - lx) + m[y1 * Wm + x1] * lx;
-  const float v = top * (1.f - ly) + bot * ly;
+  return MaskTaps{y0, y1, x0, x1, fy - y0, fx - x0};
+}
+
+// (m: row 0 of the rows t.y0 / t.y1 count from, Wm floats apart)
+__device__ __forceinline__ float final_mask_value_at(const float* __restrict__ m, int Wm, const MaskTaps& t) {
+  const float top = m[t.y0 * Wm + t.x0] * (1.f - t.lx) + m[t.y0 * Wm + t.x1] * t.lx;
+  const float bot = m[t.y1 * Wm + t.x0] * (1.f - t.lx) + m[t.y1 * Wm + t.x1] * t.lx;
+  return top * (1.f - t.ly) + bot * t.ly;
+}
+
+__device__ __forceinline__ float final_mask_value(const float* __restrict__ m, int Hm, int Wm, int factor, int h, int w, float sy_scale,
+                                                  float sx_scale, int Y, int X) {
+  return final_mask_value_at(m, Wm, final_mask_taps(Hm, Wm, factor, h, w, sy_scale, sx_scale, Y, X));
+}
+
+__device__ __forceinline__ int final_mask_bit(float v) {
   const float p = 1.0f / (1.0f + expf(-v));
   return p > 0.5f ? 1 : 0;
+}
+
+__device__ __forceinline__ int final_mask_pixel(const float* __restrict__ m, int Hm, int Wm, int factor, int h, int w, float sy_scale,
+                                                float sx_scale, int Y, int X) {
+  return final_mask_bit(final_mask_value(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, Y, X));
 }
 
 __global__ void __launch_bounds__(256)
@@ -579,5 +599,152 @@ extern "C" int mdqe_final_masks_u8_geom(const float* logits, int n_sel, const in
   hipLaunchKernelGGL(geom_init_kernel, dim3((unsigned)((rows * 5 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, geom, rows, Ho, Wo);
   hipLaunchKernelGGL(final_mask_geom_kernel, dim3((unsigned)(n_masks * n_bands)), dim3(256), 0, (hipStream_t)stream, logits, Fw, Hm, Wm,
                      factor, h, w, Ho, Wo, out, out_inst_stride, f_off, inst_idx_dev, band, n_bands, geom);
+  return mdqe_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Label map: ONE uint8 plane per frame instead of one per track -- which track owns each pixel.  Among the selected rows whose
+// final-mask bit is set at the pixel (final_mask_bit of final_mask_value: the dense masks' own bit), the one with the largest
+// up-sampled logit wins, the first such row on an exact tie; out = inst_idx[k*] + 1, 0 where no bit is set.  So out != 0 exactly
+// on the union of the dense masks, and a label always names a track whose dense mask holds the pixel.
+// A block owns a band of output rows of one frame for ALL rows (blockIdx.x = frame * n_bands + band index): the taps of a pixel are
+// computed once and the loop over k only reads and blends.  STAGED (opt-in, see the entry point): the source rows the band reads, of
+// every selected map, are copied to LDS first (n_sel * src_cap * Wm floats; a band whose rows exceed src_cap reads global memory instead, so the bound is only a
+// size, never an assumption).  GEOM: geometry of each label's visible region as mdqe_final_masks_u8_geom lays it out; a thread
+// gathers the run of equal labels it meets in registers and adds it to the block's LDS table [n_sel, 5] with LDS integer atomics
+// when the label changes; after the band, thread k adds row k -- if the block saw label k -- to geom with global integer atomics.
+// LDS: ids[n_sel] | GEOM: tab[n_sel * 5] | STAGED: rows.
+// ------------------------------------------------------------------------------------------------
+template <bool STAGED, bool GEOM>
+__global__ void __launch_bounds__(256)
+final_label_map_kernel(const float* __restrict__ lg, int n_sel, int Fw, int Hm, int Wm, int factor, int h, int w, int Ho, int Wo,
+                       unsigned char* __restrict__ out, int f_off, const int* __restrict__ inst_idx, int band, int n_bands, int src_cap,
+                       int* __restrict__ geom) {
+  extern __shared__ int label_lds[];
+  int* ids = label_lds;
+  int* tab = label_lds + n_sel;
+  float* rows_lds = reinterpret_cast<float*>(label_lds + n_sel + (GEOM ? n_sel * 5 : 0));
+  const int f = blockIdx.x / n_bands, b = blockIdx.x - f * n_bands;
+  const float sy_scale = (float)h / (float)Ho, sx_scale = (float)w / (float)Wo;
+  const int Y0 = b * band, rows = min(band, Ho - Y0);
+  const long map_stride = (long)Hm * Wm;
+  for (int k = threadIdx.x; k < n_sel; k += 256) ids[k] = inst_idx[k];
+  if constexpr (GEOM)
+    for (int i = threadIdx.x; i < n_sel * 5; i += 256) { const int c = i % 5; tab[i] = c == 0 ? 0 : c == 1 ? Wo : c == 2 ? Ho : -1; }
+  int ylo = 0;
+  bool staged = false;
+  if constexpr (STAGED) {
+    // y0 and y1 do not decrease with Y: the band reads source rows [y0 of its first row, y1 of its last]
+    ylo = final_mask_taps(Hm, Wm, factor, h, w, sy_scale, sx_scale, Y0, 0).y0;
+    const int nr = final_mask_taps(Hm, Wm, factor, h, w, sy_scale, sx_scale, Y0 + rows - 1, 0).y1 - ylo + 1;
+    staged = nr <= src_cap;
+    if (staged) {
+      const int per = nr * Wm, slot = src_cap * Wm;
+      for (int i = threadIdx.x; i < n_sel * per; i += 256) {
+        const int k = i / per, j = i - k * per;
+        rows_lds[k * slot + j] = lg[((long)inst_idx[k] * Fw + f) * map_stride + (long)ylo * Wm + j];
+      }
+    }
+  }
+  __syncthreads();
+  unsigned char* o = out + ((long)(f_off + f) * Ho + Y0) * Wo;
+  const int npix = rows * Wo;
+  int cur = -1;
+  MaskGeom g = {0, Wo, Ho, -1, -1};
+  auto flush = [&]() {
+    if (cur >= 0) {
+      int* r = tab + cur * 5;
+      atomicAdd(r + 0, g.cnt);
+      atomicMin(r + 1, g.x0); atomicMin(r + 2, g.y0);
+      atomicMax(r + 3, g.x1); atomicMax(r + 4, g.y1);
+    }
+  };
+  for (int i = threadIdx.x; i < npix; i += 256) {
+    const int y = i / Wo, X = i - y * Wo, Y = Y0 + y;
+    MaskTaps t = final_mask_taps(Hm, Wm, factor, h, w, sy_scale, sx_scale, Y, X);
+    int best = -1;
+    float best_v = 0.f;
+    if (STAGED && staged) {
+      t.y0 -= ylo; t.y1 -= ylo;
+      const int slot = src_cap * Wm;
+      for (int k = 0; k < n_sel; ++k) {
+        const float v = final_mask_value_at(rows_lds + k * slot, Wm, t);
+        if (final_mask_bit(v) && (best < 0 || v > best_v)) { best = k; best_v = v; }
+      }
+    } else {
+      for (int k = 0; k < n_sel; ++k) {
+        const float v = final_mask_value_at(lg + ((long)ids[k] * Fw + f) * map_stride, Wm, t);
+        if (final_mask_bit(v) && (best < 0 || v > best_v)) { best = k; best_v = v; }
+      }
+    }
+    o[i] = best < 0 ? (unsigned char)0 : (unsigned char)(ids[best] + 1);
+    if constexpr (GEOM) {
+      if (best != cur) { flush(); cur = best; g = MaskGeom{0, Wo, Ho, -1, -1}; }
+      geom_add(g, 1, Y, X);
+    }
+  }
+  if constexpr (GEOM) {
+    flush();
+    __syncthreads();
+    for (int k = threadIdx.x; k < n_sel; k += 256) {
+      const int* s = tab + k * 5;
+      if (s[0] > 0) {
+        int* r = geom + ((long)k * Fw + f) * 5;
+        atomicAdd(r + 0, s[0]);
+        atomicMin(r + 1, s[1]); atomicMin(r + 2, s[2]);
+        atomicMax(r + 3, s[3]); atomicMax(r + 4, s[4]);
+      }
+    }
+  }
+}
+
+extern "C" int mdqe_final_label_map_u8(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
+                                       int h, int w, int Ho, int Wo, unsigned char* out, int f_off, int* geom, void* stream) {
+  MDQE_REQUIRE(n_sel >= 0 && n_sel <= 255 && Fw >= 0 && Hm > 0 && Wm > 0 && factor >= 1 && h > 0 && w > 0 && Ho > 0 && Wo > 0 && f_off >= 0);
+  MDQE_REQUIRE(h <= Hm * factor && w <= Wm * factor && (long)Ho * Wo < 0x7FFFFFFFL && (long)Hm * Wm < 0x7FFFFFFFL);
+  if (Fw == 0) return MDQE_OK;
+  MDQE_CHECK_PTR(out);
+  if (n_sel > 0) { MDQE_CHECK_PTR(logits); MDQE_CHECK_PTR(inst_idx_dev); }
+  // bands per frame: about 8 blocks of 256 threads per CU over the window, at least ~1024 pixels (4 per thread, each for all rows) a block
+  long want = (2048 + Fw - 1) / Fw;
+  const long most = ((long)Ho * Wo + 1023) / 1024;
+  if (want > most) want = most;
+  if (want > Ho) want = Ho;
+  if (want < 1) want = 1;
+  int band = (int)((Ho + want - 1) / want);
+  // The rows are read through the caches by default.  MDQE_LABEL_MAP_STAGE=1 stages them in LDS first where they fit: measured on one
+  // MI355X (profiles/label_map_ab.txt, 15 tracks x 30 frames) the staged form is level without geometry (158.7 against 158.3 us at
+  // 360p, 484.5 against 480.0 at 640 x 1138) and 12-22 % slower with it (202.8 / 181.4, 636.7 / 523.5): neighbouring output pixels read
+  // the same few map rows, so they hit L1 anyway, and the staged form adds the copy, a barrier and 38-52 KB of LDS per block.  Kept for
+  // tools/label_map_ab.py and the tests.  A band of `band` output rows spans at most s = ceil((band-1) * h / Ho) + 1 source pixels, hence floor((factor - 1 + s)
+  // / factor) + 2 rows of the map; the band is halved until all selected maps' rows fit 64 KB (what a block gets without a function
+  // attribute), else the rows are read through the caches after all.
+  const bool with_geom = geom != nullptr && n_sel > 0;
+  const long head = (long)n_sel * (with_geom ? 6 : 1) * 4;
+  const char* env = getenv("MDQE_LABEL_MAP_STAGE");
+  bool stage = n_sel > 0 && env != nullptr && env[0] == '1';
+  int src_cap = 0;
+  int sband = band;
+  while (stage) {
+    const long s = ((long)(sband - 1) * h + Ho - 1) / Ho + 1;
+    long cap = (factor - 1 + s) / factor + 2;
+    if (cap > Hm) cap = Hm;
+    if (head + (long)n_sel * cap * Wm * 4 <= 64 * 1024) { src_cap = (int)cap; band = sband; break; }
+    if (sband <= 2) stage = false;
+    sband = (sband + 1) / 2;
+  }
+  const int n_bands = (Ho + band - 1) / band;
+  MDQE_REQUIRE((long)Fw * n_bands < 0x7FFFFFFFL && (long)n_sel * Fw * 5 < 0x7FFFFFFFL);
+  const size_t lds = (size_t)(head + (stage ? (long)n_sel * src_cap * Wm * 4 : 0));
+  mdqe_clear_error();
+  if (with_geom)
+    hipLaunchKernelGGL(geom_init_kernel, dim3((unsigned)((n_sel * Fw * 5 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, geom, n_sel * Fw, Ho, Wo);
+  const dim3 grid((unsigned)(Fw * n_bands));
+#define MDQE_LABEL_LAUNCH(S, G)                                                                                                     \
+  hipLaunchKernelGGL((final_label_map_kernel<S, G>), grid, dim3(256), lds, (hipStream_t)stream, logits, n_sel, Fw, Hm, Wm, factor, h, w, \
+                     Ho, Wo, out, f_off, inst_idx_dev, band, n_bands, src_cap, geom)
+  if (stage) { if (with_geom) MDQE_LABEL_LAUNCH(true, true); else MDQE_LABEL_LAUNCH(true, false); }
+  else { if (with_geom) MDQE_LABEL_LAUNCH(false, true); else MDQE_LABEL_LAUNCH(false, false); }
+#undef MDQE_LABEL_LAUNCH
   return mdqe_launch_status();
 }

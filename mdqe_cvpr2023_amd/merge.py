@@ -2,7 +2,9 @@
 `video_result` (the video's result from the flushed windows); `meta_arch.MDQE` keeps its entry points as delegates.  A flushed window
 becomes final masks per window into pinned memory (`_early_masks`), per window as a record (`_online_window`, online.OnlineVideo) or all
 windows in one pass at the end (`video_result`).  What the three share is written once: `dense_masks` / `rle_positions` (window logits
--> masks / run boundaries, with or without geometry), `to_host` (the hop on the copy stream), `rle.positions_to_rles`, `stitch`."""
+-> masks / run boundaries, with or without geometry), `to_host` (the hop on the copy stream), `rle.positions_to_rles`, `stitch`.
+`label_maps` is the third output form (model.label_output, online "labels"): one uint8 plane per frame that names the track owning each
+pixel, from the same three places; its frames are disjoint between windows, so it needs no `stitch`."""
 import contextlib
 import dataclasses
 import os
@@ -21,6 +23,20 @@ def dense_masks(m, idx, stride, frame_hw, out_size, geometry, out, f_off):
     if geometry:
         return ops.final_masks_geom(m, idx, stride, fh, fw, Ho, Wo, out, f_off)[1].view(int(idx.numel()), int(m.shape[1]), 5)
     ops.final_masks(m, idx, stride, fh, fw, Ho, Wo, out, f_off)
+
+
+def label_maps(m, stride, frame_hw, out_size, geometry, out, f_off):
+    """The label map of window logits m [n, F, Hm, Wm] into out[f_off:f_off + F] (uint8 [>= f_off + F, Ho, Wo], device): per pixel the
+    track (row + 1) with the largest up-sampled logit among ALL n rows whose final mask holds the pixel, 0 = background (n = 0: zeros).
+    Every path lets all rows of the window compete, so the paths agree bit for bit, and a track that later misses the video-level top-k
+    still owns its pixels (rle.labels_keep drops such labels).  -> the geometry table of the labels' visible regions, int32 [n, F, 5] on
+    the device (geometry), else None."""
+    from . import ops
+    (fh, fw), (Ho, Wo) = frame_hw, out_size
+    n = int(m.shape[0])
+    idx = torch.arange(n, dtype=torch.int32, device=m.device)
+    geom = ops.final_label_map(m, idx, stride, fh, fw, Ho, Wo, out, f_off, geom=True if geometry else None)[1]
+    return geom.view(n, int(m.shape[1]), 5) if geometry else None
 
 
 def rle_positions(m, idx, stride, frame_hw, out_size, geometry):
@@ -117,6 +133,8 @@ class EarlyMasks:
     hosts: list = dataclasses.field(default_factory=list)             # dense: per track, pinned uint8 [L, Ho, Wo]
     rle: list = dataclasses.field(default_factory=list)               # RLE: per window (f_off, frames, tracks, pos, n_pos) of rle_positions
     geom: list = dataclasses.field(default_factory=list)              # per window (f_off, frames, tracks, int32 [tracks, frames, 5] host)
+    labels: object = None                                             # label map: ONE pinned uint8 [L, Ho, Wo] per video (model.label_output)
+    label_geom: list = dataclasses.field(default_factory=list)        # per window, as `geom`, of the labels' visible regions
 
 
 def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True):
@@ -130,6 +148,11 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
     if not emit_masks:
         return dict(res, pred_masks=[])
     geometry = bool(model.geometry_output)
+    labels = getattr(model, "label_output", False)
+    if labels:
+        res.update(label_result(model, inst, windows, frame_hw, n_frames, (Ho, Wo), early, geometry))
+        if labels == "only":                                       # no per-track planes in either form
+            return dict(res, pred_masks=[])
     rows, geoms = inst, early.geom if early is not None else []
     if early is not None and model.rle_output:
         res["pred_rles"] = stitch_rles(inst, n_frames, (Ho, Wo), [(f, nf, n, R.positions_to_rles(pos, n_pos, (Ho, Wo), nf))
@@ -163,6 +186,31 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
     return res
 
 
+def label_result(model, inst, windows, frame_hw, n_frames, out_size, early, geometry):
+    """The label-map keys of a video's result: "pred_label_map" (uint8 [L, Ho, Wo], host; label t + 1 = tracker row t, 0 = background),
+    "pred_track_ids" (the row behind output j, so pred_label_map == pred_track_ids[j] + 1 is output j's exclusive region) and, with
+    geometry, "pred_label_boxes" / "pred_label_areas" of those regions.  `early`: the map is on the host already (EarlyMasks.labels);
+    else it is produced here from `windows`, the same kernel over all rows of each window, in one pass and one copy."""
+    Ho, Wo = out_size
+    if early is not None:
+        early.done.synchronize()
+        host, geoms = early.labels[:n_frames], early.label_geom
+    else:
+        dev = torch.empty(n_frames, Ho, Wo, dtype=torch.uint8, device=model.device)    # (the windows tile [0, n_frames): every row is written)
+        geoms = [(f_off, int(m.shape[1]), int(m.shape[0]), label_maps(m, model.cfg.match_stride, frame_hw, (Ho, Wo), geometry, dev, f_off))
+                 for f_off, m in windows]
+        host = torch.empty(dev.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(dev, non_blocking=True)
+        torch.cuda.current_stream(model.device).synchronize()
+        if geometry:
+            geoms = [(f, nf, n, g.cpu()) for f, nf, n, g in geoms]
+    res = {"pred_label_map": host, "pred_track_ids": list(inst)}
+    if geometry:
+        geo = track_geometry(inst, n_frames, (Ho, Wo), geoms)
+        res.update(pred_label_boxes=geo["pred_boxes"], pred_label_areas=geo["pred_areas"])
+    return res
+
+
 class ClipMerger:
     """Incremental form of the clip loop's second half (mdqe/mdqe.py:337-366): tracker update per clip, window flushes,
     final video merge.  The tracker runs on its own HIP stream so that its small kernels and per-clip host syncs overlap
@@ -176,9 +224,12 @@ class ClipMerger:
         self.emit_masks = emit_masks                # False: scores / labels only (ranks > 0 of a sharded video)
         # boxes and areas of the final masks from the kernels that produce them (None: model.geometry_output; online sessions pass theirs)
         self.geometry = bool(getattr(model, "geometry_output", False) if geometry is None else geometry)
-        # online ("masks" | "rle"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their RLE -- of every
-        # current track are built and appended to `emitted`; neither the logits nor a host buffer stay here (n_frames is unknown)
+        # online ("masks" | "rle" | "labels"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their RLE, or
+        # their label map -- of every current track are built and appended to `emitted`; neither the logits nor a host buffer stay here
+        # (n_frames is unknown)
         self.online = online
+        # False | True | "only" (model.label_output): the label map next to -- or, "only", instead of -- the per-track planes
+        self.labels = getattr(model, "label_output", False) if emit_masks and not online else False
         self.emitted = []
         self.n_frames = n_frames                    # total frames of the video when known: enables the early mask path
         self.early = None                           # EarlyMasks, from the first window the early path takes
@@ -281,7 +332,16 @@ class ClipMerger:
         if self.early is None:
             self.early = EarlyMasks(done=torch.cuda.Event())
         early = self.early
-        if not n:
+        if self.labels:
+            # one pinned [L, Ho, Wo] map per video, whatever the number of tracks; a window without tracks is written too (zeros)
+            if early.labels is None:
+                early.labels = model.pinned_mask_buffer((int(self.n_frames), Ho, Wo))
+            dev = torch.empty(nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
+            geom = to_host(cs, self.side, dev, [(early.labels[self.f_off:self.f_off + nf], dev)],
+                           label_maps(m, model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry, dev, 0), early.done)
+            if self.geometry:
+                early.label_geom.append((self.f_off, nf, n, geom))
+        if not n or self.labels == "only":
             return
         args = (m, torch.arange(n, dtype=torch.int32, device=self.dev), model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry)
         if model.rle_output:
@@ -302,13 +362,22 @@ class ClipMerger:
     def _online_window(self, c, m):
         """Online mode: the window just flushed (c: class rows [n, K] on the host, m: mean logits [n, F, Hm, Wm]) as a record --
         frames, class rows, and the final masks of tracks 0..n-1: dense masks copied to a pinned host buffer on the copy stream
-        (`ready` fires when they and the geometry table are there), or their RLE dicts."""
+        (`ready` fires when they and the geometry table are there), or their RLE dicts, or ("labels") their label map uint8 [F, Ho, Wo],
+        copied the same way, with the geometry of the labels' visible regions."""
         n, nf = int(m.shape[0]), int(m.shape[1])
         Ho, Wo = int(self.out_size[0]), int(self.out_size[1])
         rec = {"frames": (self.f_off, self.f_off + nf), "cls_probs": c, "ready": None}
         geom = torch.zeros((0, nf, 5), dtype=torch.int32) if self.geometry else None    # (the table of a window without tracks)
         args = (m, torch.arange(n, dtype=torch.int32, device=self.dev), self.model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry)
-        if self.online == "rle":
+        if self.online == "labels":                                  # one plane per frame; a window without tracks is all background
+            cs = copy_stream(self.model)
+            dev = torch.empty(nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
+            geom = label_maps(m, self.model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry, dev, 0)
+            host = self.model.pinned_mask_buffer((nf, Ho, Wo))
+            rec["ready"] = torch.cuda.Event()
+            geom = to_host(cs, self.side, dev, [(host, dev)], geom, rec["ready"])
+            rec["labels"] = host
+        elif self.online == "rle":
             rec["rles"] = []
             if n:
                 pos, n_pos, geom = rle_positions(*args)

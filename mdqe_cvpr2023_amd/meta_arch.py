@@ -101,6 +101,13 @@ class MDQE(nn.Module):
         # True: forward() on a video adds "pred_boxes" (float32 [L, 4] XYXY_ABS per output) and "pred_areas" (int64 [L]) of the final masks,
         # gathered by the kernels that write / encode the masks (ops.final_masks_geom / final_masks_rle_geom); off: nothing changes
         self.geometry_output = False
+        # True: forward() on a video adds "pred_label_map" (uint8 [L, Ho, Wo] on the host: which track owns each pixel, label t + 1 = tracker
+        # row t, 0 = background; the row with the largest up-sampled logit among ALL tracks of the window whose mask holds the pixel --
+        # also one that misses the video-level top-k: rle.labels_keep drops those) and "pred_track_ids" (the row behind output j), built on
+        # the device by ops.final_label_map: 1 byte per pixel however many tracks.  "only": the same without the per-track planes
+        # ("pred_masks" is []: no dense-mask kernels, pinned buffers or copies).  With geometry_output also "pred_label_boxes" /
+        # "pred_label_areas" of the labels' visible regions.  False: nothing changes.  (A property: see `label_output` below.)
+        self.label_output = False
         self.merge_on_cpu = None                    # None: cfg.merge_on_cpu (MODEL.MDQE.MERGE_ON_CPU); True / False override it
         # Final masks of a tracker window leave the device when the window is flushed (pinned host buffers, copied under the later
         # windows' compute) instead of in one pass + one 100-MB copy after the last window.  Independent of MERGE_ON_CPU, which in the
@@ -247,6 +254,24 @@ class MDQE(nn.Module):
                 yield
         finally:
             cur.wait_stream(ws)
+
+    @property
+    def label_output(self):
+        return self.__dict__.get("_label_output", False)
+
+    @label_output.setter
+    def label_output(self, value):
+        if value not in (False, True, "only"):
+            raise ValueError("label_output must be False, True or 'only', got %r" % (value,))
+        if value:
+            self.check_label_capacity()
+        self.__dict__["_label_output"] = value
+
+    def check_label_capacity(self):
+        """uint8 labels are tracker row + 1: the bank may hold at most 255 rows."""
+        if int(self.cfg.n_max_inst) > 255:
+            raise ValueError("label maps are uint8 (label = track + 1): n_max_inst (MODEL.MDQE.MAX_NUM_INSTANCES) = %d exceeds 255"
+                             % int(self.cfg.n_max_inst))
 
     PIN_POOL_GB = float(os.environ.get("MDQE_PIN_POOL_GB", "8"))       # pinned host memory the model keeps for mask read-back between calls
 
@@ -904,8 +929,9 @@ class MDQE(nn.Module):
     def online_video(self, height=None, width=None, emit="masks", keep=False, geometry=False):
         """An online session over ONE video whose frames arrive in pushes (a camera, a stream, a video too long to hold): push()
         returns each tracker window as soon as it is final, close() the rest, result() the video-level scores / labels / tracks.
-        height / width: output mask size (default: the frame size); emit: "masks" (bool [n, F, H, W] per window) or "rle"; keep:
-        result() also carries forward()'s "pred_masks" / "pred_rles", bit-identical; geometry: every window carries `boxes` / `areas` of its
+        height / width: output mask size (default: the frame size); emit: "masks" (bool [n, F, H, W] per window), "rle" or "labels" (one
+        uint8 [F, H, W] map per window: which track owns each pixel, `label_output`'s rule); keep: result() also carries forward()'s
+        "pred_masks" / "pred_rles" / "pred_label_map", bit-identical; geometry: every window carries `boxes` / `areas` of its
         final masks and result() "pred_boxes" / "pred_areas" (with or without keep), equal to forward()'s with geometry_output.  See online.py."""
         from .online import OnlineVideo
         return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep, geometry=geometry)

@@ -3,7 +3,7 @@
     ov = model.online_video(height=H, width=W, emit="masks", keep=False, geometry=False)
     for chunk in source:                   # [n, 3, h, w] uint8 / float32, host or device, n >= 1 (n == 0: no-op)
         for win in ov.push(chunk):         # the windows this push completed, in order
-            win.frames, win.track_ids, win.cls_probs, win.masks   # (or win.rles with emit="rle")
+            win.frames, win.track_ids, win.cls_probs, win.masks   # (or win.rles with emit="rle", win.labels with emit="labels")
             win.boxes, win.areas           # geometry=True: XYXY_ABS float32 [n, F, 4] and pixel counts int64 [n, F] of those masks
     for win in ov.close():                 # the clamped last clip and the final flush
         ...
@@ -17,6 +17,12 @@ the tracker bank and the carry; the masks of a window leave for the host when it
 write / encode a window's masks also return each mask's pixel count and tight box (ops.final_masks_geom / final_masks_rle_geom): no pass
 over the masks on the host, no decoding of the RLEs; result() then carries "pred_boxes" / "pred_areas" whatever `keep` says.  MERGE_ON_CPU has no meaning here (it
 only places the window results the offline merge waits on).  One GPU, one video per session.
+
+emit="labels": a window carries ONE uint8 [F, H, W] map instead of n planes (`win.labels`; win.masks / win.rles are None): per pixel
+track_id + 1 of the track that owns it -- the largest up-sampled logit among the window's tracks whose mask holds the pixel -- and 0
+for background (ops.final_label_map; 1 byte per pixel however many tracks).  geometry=True then describes the labels' visible regions
+(win.boxes / win.areas, result()'s "pred_label_boxes" / "pred_label_areas"); keep=True adds "pred_label_map", equal to forward()'s
+with model.label_output.  A label can name a track that misses the video-level top-k: rle.labels_keep(map, result["pred_track_ids"]).
 """
 import contextlib
 import dataclasses
@@ -100,7 +106,10 @@ class Window:
     """One tracker window: frames [f0, f1), tracker instance index of each row, this window's class probabilities per track
     (provisional: the video-level class is decided at close), and the final masks -- bool [n, f1-f0, H, W] on the host -- or,
     with emit="rle", per track per frame {"size", "counts"}.  With geometry=True: boxes float32 [n, f1-f0, 4] ([xmin, ymin, xmax+1,
-    ymax+1] in output pixels, zeros for an empty mask) and areas int64 [n, f1-f0] of those masks."""
+    ymax+1] in output pixels, zeros for an empty mask) and areas int64 [n, f1-f0] of those masks.  With emit="labels": `labels`, uint8
+    [f1-f0, H, W] on the host (track_ids[i] + 1 where track i owns the pixel, 0 = background), masks and rles None, boxes / areas those
+    of the labels' visible regions.  (`labels` is an init-only pseudo-field stored as a plain attribute: dataclasses.fields(Window) is
+    what it was.)"""
     frames: tuple
     track_ids: list
     cls_probs: torch.Tensor
@@ -108,12 +117,18 @@ class Window:
     rles: list = None
     boxes: torch.Tensor = None
     areas: torch.Tensor = None
+    labels: dataclasses.InitVar[torch.Tensor] = None
+
+    def __post_init__(self, labels):
+        self.labels = labels
 
 
 class OnlineVideo:
     def __init__(self, model, height=None, width=None, emit="masks", keep=False, geometry=False):
-        if emit not in ("masks", "rle"):
-            raise ValueError("online_video: emit must be 'masks' or 'rle'")
+        if emit not in ("masks", "rle", "labels"):
+            raise ValueError("online_video: emit must be 'masks', 'rle' or 'labels'")
+        if emit == "labels":
+            model.check_label_capacity()
         if model.cfg.is_coco:
             raise RuntimeError("online_video: a COCO image config takes the single-image branch; online inference is for videos")
         if model.device.type != "cuda":
@@ -189,7 +204,7 @@ class OnlineVideo:
                 boxes, areas = R.geom_to_boxes(r["geom"])
                 self.geoms.append((r["frames"][0], r["frames"][1] - r["frames"][0], n, r["geom"]))
             out.append(Window(frames=r["frames"], track_ids=list(range(n)), cls_probs=r["cls_probs"],
-                              masks=r.get("masks"), rles=r.get("rles"), boxes=boxes, areas=areas))
+                              masks=r.get("masks"), rles=r.get("rles"), boxes=boxes, areas=areas, labels=r.get("labels")))
         del self.merger.emitted[:]
         if self.keep:
             self.kept.extend(out)
@@ -243,9 +258,9 @@ class OnlineVideo:
 
     def result(self):
         """After close(): {"image_size", "pred_scores", "pred_labels", "pred_track_ids"} -- the video-level top-k of
-        `inference_video`; pred_track_ids[j] is the track behind output j.  keep=True adds "pred_masks" (or "pred_rles"),
-        assembled from the windows handed out, equal to forward()'s; geometry=True adds "pred_boxes" / "pred_areas" (forward()'s with
-        model.geometry_output), with or without keep."""
+        `inference_video`; pred_track_ids[j] is the track behind output j.  keep=True adds "pred_masks" (or "pred_rles", or
+        "pred_label_map"), assembled from the windows handed out, equal to forward()'s; geometry=True adds "pred_boxes" / "pred_areas"
+        (forward()'s with model.geometry_output; emit="labels": "pred_label_boxes" / "pred_label_areas"), with or without keep."""
         if not self.closed:
             raise RuntimeError("online_video: result() before close()")
         if self._result is not None:
@@ -256,8 +271,13 @@ class OnlineVideo:
         Ho, Wo = self.out_size
         res = {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels, "pred_track_ids": list(inst)}
         if self.geometry:
-            res.update(self.model.track_geometry(list(inst), self.received, (Ho, Wo), self.geoms))
-        if self.keep:
+            geo = self.model.track_geometry(list(inst), self.received, (Ho, Wo), self.geoms)
+            if self.emit == "labels":                 # (the windows' tables describe the labels' visible regions, not the full masks)
+                geo = {"pred_label_boxes": geo["pred_boxes"], "pred_label_areas": geo["pred_areas"]}
+            res.update(geo)
+        if self.keep and self.emit == "labels":
+            res["pred_label_map"] = torch.cat([w.labels for w in self.kept])
+        elif self.keep:
             from . import merge
             wins = [(w.frames[0], w.frames[1] - w.frames[0], len(w.track_ids), w.rles if self.emit == "rle" else w.masks) for w in self.kept]
             if self.emit == "rle":

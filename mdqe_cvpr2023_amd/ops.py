@@ -577,6 +577,29 @@ def final_masks_geom(logits, inst_idx, factor, h, w, Ho, Wo, out, f_off, geom=No
     return out, geom
 
 
+def final_label_map(logits, inst_idx, factor, h, w, Ho, Wo, out, f_off, geom=None):
+    """One plane per frame instead of one per track: out[f_off + f] (uint8 [>= f_off + Fw, Ho, Wo], CUDA, contiguous) = which of the rows
+    `inst_idx` (int32 CUDA [n_sel]) of logits [n, Fw, Hm, Wm] owns each pixel -- inst_idx[k] + 1 for the row with the largest up-sampled
+    logit among those whose final-mask bit is set there (the first of them on an exact tie), 0 where none is set; n <= 255.  `geom`:
+    None, True (allocate) or an int32 [n_sel*Fw, 5] buffer -- the rows of ops.final_masks_geom for each label's visible region (fully
+    overwritten).  n_sel == 0 writes zeros to the Fw frames.  -> (out, geom or None)."""
+    # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
+    if logits.dim() != 4 or int(logits.shape[0]) > 255:
+        raise RuntimeError("final_label_map: logits must be [n <= 255, Fw, Hm, Wm] (uint8 labels), got %s" % (tuple(logits.shape),))
+    if inst_idx.dtype != torch.int32 or inst_idx.dim() != 1:
+        raise RuntimeError("final_label_map: inst_idx must be int32 [n_sel], got %s %s" % (inst_idx.dtype, tuple(inst_idx.shape)))
+    Fw = int(logits.shape[1])
+    if (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 3 or tuple(out.shape[1:]) != (Ho, Wo) or f_off < 0
+            or f_off + Fw > out.shape[0] or not out.is_contiguous() or not out.is_cuda):
+        raise RuntimeError("final_label_map: out must be contiguous CUDA uint8 [>= f_off + Fw = %d, Ho, Wo]" % (f_off + Fw))
+    k, Fw, Hm, Wm = _final_mask_args(logits, inst_idx, True)
+    if geom is not None:
+        geom = _geom_rows(None if geom is True else geom, k * Fw, logits.device)
+    check(lib.mdqe_final_label_map_u8(ptr(logits), k, ptr(inst_idx), Fw, Hm, Wm, factor, h, w, Ho, Wo, ptr(out), f_off,
+                                      ptr(geom) if geom is not None and k else None, cur_stream()), "final_label_map")
+    return out, geom
+
+
 def layernorm_post(x, gamma, beta, post, eps=1e-5, out=None):
     """out = LN(x)*gamma + beta + post."""
     _chk(x, "x"); _chk(post, "post")

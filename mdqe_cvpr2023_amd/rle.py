@@ -211,6 +211,37 @@ def encode_dense(mask):
     return {"size": [int(m.shape[0]), int(m.shape[1])], "counts": counts_to_strings(counts, lengths)[0].decode("utf-8")}
 
 
+# ---- label maps (model.label_output / online emit="labels"): uint8 [L, H, W], label t + 1 = track t, 0 = background ----------------------
+def labels_to_masks(label_map, track_ids):
+    """The exclusive region of each track of `track_ids` as a bool plane -> [len(track_ids), L, H, W] (tensor in, tensor out; else numpy)."""
+    if hasattr(label_map, "dim"):
+        import torch
+        ids = torch.as_tensor(list(track_ids), dtype=torch.int64).view(-1, 1, 1, 1) + 1
+        return label_map.unsqueeze(0) == ids.to(label_map.device)
+    lm = np.asarray(label_map)
+    return lm[None] == (np.asarray(list(track_ids), dtype=np.int64).reshape(-1, 1, 1, 1) + 1)
+
+
+def labels_keep(label_map, track_ids):
+    """The map with every label but those of `track_ids` set to 0 -- "only my selected tracks" (a map names every track of its window,
+    also one that misses the video-level top-k).  One pass through a 256-entry look-up table; same type and shape as the input."""
+    lut = np.zeros(256, dtype=np.uint8)
+    for t in track_ids:
+        if not 0 <= int(t) < 255:
+            raise ValueError("labels_keep: track id %r is outside 0..254" % (t,))
+        lut[int(t) + 1] = int(t) + 1
+    if hasattr(label_map, "dim"):
+        import torch
+        return torch.from_numpy(lut).to(label_map.device)[label_map.long()]
+    return lut[np.asarray(label_map)]
+
+
+def labels_to_rles(label_map, track_id):
+    """The exclusive region of one track as per-frame COCO RLE dicts (`encode_dense`) -> list of L {"size", "counts"}."""
+    lm = label_map.cpu().numpy() if hasattr(label_map, "dim") else np.asarray(label_map)
+    return [encode_dense(fm == int(track_id) + 1) for fm in lm]
+
+
 def instances_to_coco_json_video(inputs, outputs):
     """Drop-in for mdqe/data/ytvis_eval.py:288-324: list of {"video_id", "score", "category_id", "segmentations"}."""
     assert len(inputs) == 1, "More than one inputs are loaded for inference!"
