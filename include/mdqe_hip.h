@@ -15,6 +15,9 @@
  *   everything else            <- ATen/cuDNN/cuBLAS kernels the reference reaches through PyTorch on
  *                                 the same path (SURVEY.md §2a "Fused ops / ATen kernels"); each
  *                                 prototype names the reference call site it serves.
+ *   mdqe_render_overlay_u8     <- the demo's host-side painting (demo/clip/visualizer.py:83-170, overlay_instances: matplotlib
+ *                                 polygons blended at alpha 0.5 per frame); here one streaming kernel behind the label map, its
+ *                                 own integer rule (below), not the demo's anti-aliased picture.
  */
 #ifndef MDQE_HIP_H
 #define MDQE_HIP_H
@@ -464,6 +467,26 @@ int mdqe_final_masks_rle_geom(const float* logits, int n_sel, const int* inst_id
  * zeros to the Fw frames (a window without tracks is all background).  Never allocates, never synchronises. */
 int mdqe_final_label_map_u8(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
                             int h, int w, int Ho, int Wo, unsigned char* out, int f_off, int* geom, void* stream);
+
+/* The picture a viewer paints from that map: out[f_off + f, Y, X, c] (uint8, pixel-interleaved, [>= f_off + F, Ho, Wo, 3]) from labels
+ * (uint8 [F, Ho, Wo], what mdqe_final_label_map_u8 writes), the frames the caller handed in (frames: [F, 3, h0, w0] planar, uint8 if
+ * is_u8 else float32, consecutive frames frame_stride ELEMENTS apart -- a view into a larger store works -- or NULL) and palette (uint8
+ * [256, 3], in the frames' channel order: channel c of out is channel c of frames).  Integers only, ONE definition:
+ *   source pixel  sy = (Y*h0) / Ho, sx = (X*w0) / Wo (exact integer division: nearest sampling, the identity at equal sizes);
+ *   source value  s_c = frames[f, c, sy, sx]; float32 becomes min(max(rint(v), 0), 255), rint rounding half to even, NaN -> 0; no
+ *                 frames: s_c = 0 (paints onto black: a DAVIS-style colour map);
+ *   label         l = labels[f, Y, X];  l == 0 (background): out_c = s_c;
+ *   contour       else edge = for some d in 1..contour and some direction (+-d, 0), (0, +-d) the neighbour lies INSIDE the image and
+ *                 its label differs from l (a neighbour outside never counts: an object cut by the border gets no line along it;
+ *                 contour = 0: no contours);
+ *   colour        out_c = palette[l][c] if edge, else (s_c*(256 - a256) + palette[l][c]*a256 + 128) >> 8.
+ * a256 in 0..256, contour in 0..3, Ho*Wo*3 < 2^31 and F*Ho*Wo < 2^31, all checked before any pointer is looked at; F == 0 returns OK
+ * and launches nothing.  Nothing needs to be aligned (Wo, Ho*Wo*3, f_off*Ho*Wo*3 arbitrary).  No atomics: identical from run to run.
+ * Never allocates, never synchronises. */
+int mdqe_render_overlay_u8(const void* frames, int is_u8, long frame_stride, int h0, int w0,
+                           const unsigned char* labels, int F, int Ho, int Wo,
+                           const unsigned char* palette, int a256, int contour,
+                           unsigned char* out, int f_off, void* stream);
 
 /* ---- COCO single-image branch, after the decoder (MDQE.inference_image, mdqe/mdqe.py:486-556), on the centre frame's
  * low-resolution logits [n,Hm,Wm]; aligned_bilinear x`factor` in closed form, crop [:h,:w].

@@ -4,7 +4,8 @@ becomes final masks per window into pinned memory (`_early_masks`), per window a
 windows in one pass at the end (`video_result`).  What the three share is written once: `dense_masks` / `rle_positions` (window logits
 -> masks / run boundaries, with or without geometry), `to_host` (the hop on the copy stream), `rle.positions_to_rles`, `stitch`.
 `label_maps` is the third output form (model.label_output, online "labels"): one uint8 plane per frame that names the track owning each
-pixel, from the same three places; its frames are disjoint between windows, so it needs no `stitch`."""
+pixel, from the same three places; its frames are disjoint between windows, so it needs no `stitch`.  `overlay_frames` is the fourth
+(model.overlay_output, online "overlay"): that map painted over the frames the caller handed in (`FrameStore`), uint8 [F, Ho, Wo, 3]."""
 import contextlib
 import dataclasses
 import os
@@ -37,6 +38,76 @@ def label_maps(m, stride, frame_hw, out_size, geometry, out, f_off):
     idx = torch.arange(n, dtype=torch.int32, device=m.device)
     geom = ops.final_label_map(m, idx, stride, fh, fw, Ho, Wo, out, f_off, geom=True if geometry else None)[1]
     return geom.view(n, int(m.shape[1]), 5) if geometry else None
+
+
+class FrameStore:
+    """The frame source of `overlay_frames`: the frames the caller handed in, at their uploaded size and dtype (before
+    `resize_on_device`), on the device, as chunks in video order -- one per push of an online session, one for a whole offline video.
+    `pieces(f0, f1)` answers "frames [f0, f1)" with a list of (tensor [k, 3, h0, w0], first frame) that tile the range; a range that
+    spans two chunks comes back as two pieces.  `drop_before(f)` forgets the chunks that lie wholly before frame f, so what a session
+    holds is bounded by its schedule: the frames no window has emitted yet, plus less than one push."""
+
+    def __init__(self):
+        self.chunks = []                          # [first frame, tensor [n, 3, h0, w0], upload event or None, owned]
+
+    def add(self, first, frames, ready=None, owned=True):
+        """`ready`: the event behind the chunk's upload (None: the frames are there for the current stream; an event is recorded on
+        it).  owned=False: the tensor may be the CALLER's memory (frames that arrived on the device are not copied), which `own()`
+        replaces by a copy if it is still held."""
+        if int(frames.shape[0]):
+            if ready is None and frames.is_cuda:
+                ready = torch.cuda.Event()
+                ready.record(torch.cuda.current_stream(frames.device))
+            self.chunks.append([int(first), frames, ready, bool(owned)])
+
+    @property
+    def frames_held(self):
+        return sum(int(c[1].shape[0]) for c in self.chunks)
+
+    def drop_before(self, f):
+        self.chunks = [c for c in self.chunks if c[0] + int(c[1].shape[0]) > f]
+
+    def own(self):
+        """Before control returns to the caller: a chunk that stays and may alias the caller's buffer is copied (the caller may refill it)."""
+        for c in self.chunks:
+            if not c[3]:
+                c[1], c[3] = c[1].clone(), True
+                if c[1].is_cuda:                  # (the copy runs on the current stream; a later window's painting waits for it)
+                    c[2] = torch.cuda.Event()
+                    c[2].record(torch.cuda.current_stream(c[1].device))
+
+    def pieces(self, f0, f1, stream=None):
+        """`stream`: the stream that will read the pieces -- it waits for their uploads and the pieces are `record_stream`ed on it.
+        The upload is ordered before that stream's work transitively as well: the painting follows the window's flush, the flush its
+        clips' `ready` events, the clips the per-frame stages, and those waited for the upload (or, with `resize_on_device`, for the
+        resize that replaced the tensor, which waited for the whole upload).  The explicit wait costs nothing and does not lean on that."""
+        out = []
+        for first, t, ready, _ in self.chunks:
+            a, b = max(f0, first), min(f1, first + int(t.shape[0]))
+            if a < b:
+                if stream is not None:
+                    if ready is not None:
+                        stream.wait_event(ready)
+                    t.record_stream(stream)
+                out.append((t[a - first:b - first], a))
+        if sum(int(t.shape[0]) for t, _ in out) != f1 - f0:
+            raise RuntimeError("overlay: the frame store does not hold frames [%d, %d)" % (f0, f1))
+        return out
+
+
+def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, source, f0, style, out, o_off):
+    """A window's overlay: the label map of window logits m [n, F, Hm, Wm] into labels[l_off:l_off + F] (`label_maps`: all n rows
+    compete, as in every label path), then that map painted over video frames [f0, f0 + F) of `source` (a FrameStore) into
+    out[o_off:o_off + F] (uint8 [>= o_off + F, Ho, Wo, 3], device) in `style` (render.Style) -- one ops.render_overlay launch per
+    contiguous piece of source frames, on the stream the label map runs on (the current one).  -> `label_maps`' geometry table or None."""
+    from . import ops
+    geom = label_maps(m, stride, frame_hw, out_size, geometry, labels, l_off)
+    nf = int(m.shape[1])
+    pal = style.palette_on(m.device)
+    for t, first in source.pieces(int(f0), int(f0) + nf, stream=torch.cuda.current_stream(m.device)):
+        k, d = int(t.shape[0]), first - int(f0)
+        ops.render_overlay(labels[l_off + d:l_off + d + k], t, pal, out, o_off + d, style.a256, style.contour)
+    return geom
 
 
 def rle_positions(m, idx, stride, frame_hw, out_size, geometry):
@@ -135,9 +206,10 @@ class EarlyMasks:
     geom: list = dataclasses.field(default_factory=list)              # per window (f_off, frames, tracks, int32 [tracks, frames, 5] host)
     labels: object = None                                             # label map: ONE pinned uint8 [L, Ho, Wo] per video (model.label_output)
     label_geom: list = dataclasses.field(default_factory=list)        # per window, as `geom`, of the labels' visible regions
+    overlay: object = None                                            # overlay: ONE pinned uint8 [L, Ho, Wo, 3] per video (model.overlay_output)
 
 
-def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True):
+def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True, frame_source=None):
     """mdqe/mdqe.py:430-471.  The x4 aligned-bilinear up-sampling, sigmoid, crop (:357-358), nearest resize to the original size and
     the 0.5 threshold (:458-462) run as ONE kernel per window; windows in which an instance did not exist yet stay zero (:442).
     `early` (EarlyMasks): the masks of every tracked instance are on the host already, only the selection is left.  Without it
@@ -149,8 +221,9 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
         return dict(res, pred_masks=[])
     geometry = bool(model.geometry_output)
     labels = getattr(model, "label_output", False)
-    if labels:
-        res.update(label_result(model, inst, windows, frame_hw, n_frames, (Ho, Wo), early, geometry))
+    overlay = (frame_source, model.overlay_style) if frame_source is not None and getattr(model, "overlay_output", False) else None
+    if labels or overlay:
+        res.update(label_result(model, inst, windows, frame_hw, n_frames, (Ho, Wo), early, geometry and bool(labels), bool(labels), overlay))
         if labels == "only":                                       # no per-track planes in either form
             return dict(res, pred_masks=[])
     rows, geoms = inst, early.geom if early is not None else []
@@ -186,25 +259,42 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
     return res
 
 
-def label_result(model, inst, windows, frame_hw, n_frames, out_size, early, geometry):
+def label_result(model, inst, windows, frame_hw, n_frames, out_size, early, geometry, labels=True, overlay=None):
     """The label-map keys of a video's result: "pred_label_map" (uint8 [L, Ho, Wo], host; label t + 1 = tracker row t, 0 = background),
     "pred_track_ids" (the row behind output j, so pred_label_map == pred_track_ids[j] + 1 is output j's exclusive region) and, with
     geometry, "pred_label_boxes" / "pred_label_areas" of those regions.  `early`: the map is on the host already (EarlyMasks.labels);
-    else it is produced here from `windows`, the same kernel over all rows of each window, in one pass and one copy."""
+    else it is produced here from `windows`, the same kernel over all rows of each window, in one pass and one copy.
+    `overlay` = (FrameStore, render.Style): also "pred_overlay" (uint8 [L, Ho, Wo, 3], pinned host), that map painted over the frames
+    (`overlay_frames`); with labels=False the map itself stays a device scratch and is not returned."""
     Ho, Wo = out_size
+    host = pic = None
     if early is not None:
         early.done.synchronize()
-        host, geoms = early.labels[:n_frames], early.label_geom
+        geoms = early.label_geom
+        host = early.labels[:n_frames] if labels else None
+        pic = early.overlay[:n_frames] if overlay else None
     else:
         dev = torch.empty(n_frames, Ho, Wo, dtype=torch.uint8, device=model.device)    # (the windows tile [0, n_frames): every row is written)
-        geoms = [(f_off, int(m.shape[1]), int(m.shape[0]), label_maps(m, model.cfg.match_stride, frame_hw, (Ho, Wo), geometry, dev, f_off))
-                 for f_off, m in windows]
-        host = torch.empty(dev.shape, dtype=torch.uint8, pin_memory=True)
-        host.copy_(dev, non_blocking=True)
+        if overlay:
+            dpic = torch.empty(n_frames, Ho, Wo, 3, dtype=torch.uint8, device=model.device)
+            geoms = [(f_off, int(m.shape[1]), int(m.shape[0]), overlay_frames(m, model.cfg.match_stride, frame_hw, (Ho, Wo), geometry, dev, f_off,
+                                                                              overlay[0], f_off, overlay[1], dpic, f_off)) for f_off, m in windows]
+            pic = torch.empty(dpic.shape, dtype=torch.uint8, pin_memory=True)
+            pic.copy_(dpic, non_blocking=True)
+        else:
+            geoms = [(f_off, int(m.shape[1]), int(m.shape[0]), label_maps(m, model.cfg.match_stride, frame_hw, (Ho, Wo), geometry, dev, f_off))
+                     for f_off, m in windows]
+        if labels:
+            host = torch.empty(dev.shape, dtype=torch.uint8, pin_memory=True)
+            host.copy_(dev, non_blocking=True)
         torch.cuda.current_stream(model.device).synchronize()
         if geometry:
             geoms = [(f, nf, n, g.cpu()) for f, nf, n, g in geoms]
-    res = {"pred_label_map": host, "pred_track_ids": list(inst)}
+    res = {"pred_track_ids": list(inst)}
+    if labels:
+        res["pred_label_map"] = host
+    if overlay:
+        res["pred_overlay"] = pic
     if geometry:
         geo = track_geometry(inst, n_frames, (Ho, Wo), geoms)
         res.update(pred_label_boxes=geo["pred_boxes"], pred_label_areas=geo["pred_areas"])
@@ -219,17 +309,25 @@ class ClipMerger:
     tracker_cls = OverTracker               # (tests without a GPU substitute a stand-in bank, tests/_standins.py)
     EARLY_TRACKS = 48                       # tracks per video the early-mask path budgets pinned memory for
 
-    def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True, online=None, geometry=None):
+    def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True, online=None, geometry=None, frame_source=None,
+                 style=None):
         self.model, self.frame_hw, self.out_size, self.mask_hw = model, frame_hw, out_size, mask_hw
         self.emit_masks = emit_masks                # False: scores / labels only (ranks > 0 of a sharded video)
         # boxes and areas of the final masks from the kernels that produce them (None: model.geometry_output; online sessions pass theirs)
         self.geometry = bool(getattr(model, "geometry_output", False) if geometry is None else geometry)
-        # online ("masks" | "rle" | "labels"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their RLE, or
-        # their label map -- of every current track are built and appended to `emitted`; neither the logits nor a host buffer stay here
-        # (n_frames is unknown)
+        # online ("masks" | "rle" | "labels" | "overlay"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their
+        # RLE, or their label map, or that map and its overlay -- of every current track are built and appended to `emitted`; neither the
+        # logits nor a host buffer stay here (n_frames is unknown)
         self.online = online
         # False | True | "only" (model.label_output): the label map next to -- or, "only", instead of -- the per-track planes
         self.labels = getattr(model, "label_output", False) if emit_masks and not online else False
+        # the overlay (model.overlay_output, online "overlay"): the label map painted over the frames of `frame_source` (a FrameStore)
+        self.overlay = bool(getattr(model, "overlay_output", False)) if emit_masks and not online else online == "overlay"
+        self.frame_source = frame_source
+        self.style = style if style is not None else getattr(model, "overlay_style", None)
+        if self.overlay and frame_source is None:
+            raise ValueError("overlay output needs the frames of the whole video on this device; this path does not hold them (the sharded "
+                             "driver does not offer it: rank 0 does not hold every frame)")
         self.emitted = []
         self.n_frames = n_frames                    # total frames of the video when known: enables the early mask path
         self.early = None                           # EarlyMasks, from the first window the early path takes
@@ -246,7 +344,8 @@ class ClipMerger:
         # this video (a 120-frame 360p video: 27.6 MB per track; one rank's view of a 1920-frame one: 442 MB per track).
         if self.early_on and n_frames is not None:
             per_track = int(n_frames) * int(out_size[0]) * int(out_size[1])
-            if per_track * self.EARLY_TRACKS > float(os.environ.get("MDQE_EARLY_PINNED_GB", "24")) * 2 ** 30:
+            # (the overlay's one pinned [n_frames, Ho, Wo, 3] buffer counts too)
+            if per_track * (self.EARLY_TRACKS + (3 if self.overlay else 0)) > float(os.environ.get("MDQE_EARLY_PINNED_GB", "24")) * 2 ** 30:
                 self.early_on = False
         self.dev = model.device
         self.use_side = self.dev.type == "cuda"
@@ -332,14 +431,29 @@ class ClipMerger:
         if self.early is None:
             self.early = EarlyMasks(done=torch.cuda.Event())
         early = self.early
-        if self.labels:
-            # one pinned [L, Ho, Wo] map per video, whatever the number of tracks; a window without tracks is written too (zeros)
-            if early.labels is None:
-                early.labels = model.pinned_mask_buffer((int(self.n_frames), Ho, Wo))
+        if self.labels or self.overlay:
+            # one pinned [L, Ho, Wo] map per video, whatever the number of tracks; a window without tracks is written too (zeros).  The
+            # overlay: one pinned [L, Ho, Wo, 3] picture per video the same way; without label_output the map is a device scratch.
+            geometry = self.geometry and bool(self.labels)
             dev = torch.empty(nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
-            geom = to_host(cs, self.side, dev, [(early.labels[self.f_off:self.f_off + nf], dev)],
-                           label_maps(m, model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry, dev, 0), early.done)
-            if self.geometry:
+            copies, pic = [], None
+            if self.labels:
+                if early.labels is None:
+                    early.labels = model.pinned_mask_buffer((int(self.n_frames), Ho, Wo))
+                copies.append((early.labels[self.f_off:self.f_off + nf], dev))
+            if self.overlay:
+                if early.overlay is None:
+                    early.overlay = model.pinned_mask_buffer((int(self.n_frames), Ho, Wo, 3))
+                pic = torch.empty(nf, Ho, Wo, 3, dtype=torch.uint8, device=self.dev)
+                geom = overlay_frames(m, model.cfg.match_stride, self.frame_hw, self.out_size, geometry, dev, 0, self.frame_source, self.f_off,
+                                      self.style, pic, 0)
+                copies.append((early.overlay[self.f_off:self.f_off + nf], pic))
+            else:
+                geom = label_maps(m, model.cfg.match_stride, self.frame_hw, self.out_size, geometry, dev, 0)
+            geom = to_host(cs, self.side, dev, copies, geom, early.done)
+            if pic is not None:
+                pic.record_stream(cs)
+            if geometry:
                 early.label_geom.append((self.f_off, nf, n, geom))
         if not n or self.labels == "only":
             return
@@ -363,19 +477,29 @@ class ClipMerger:
         """Online mode: the window just flushed (c: class rows [n, K] on the host, m: mean logits [n, F, Hm, Wm]) as a record --
         frames, class rows, and the final masks of tracks 0..n-1: dense masks copied to a pinned host buffer on the copy stream
         (`ready` fires when they and the geometry table are there), or their RLE dicts, or ("labels") their label map uint8 [F, Ho, Wo],
-        copied the same way, with the geometry of the labels' visible regions."""
+        copied the same way, with the geometry of the labels' visible regions, or ("overlay") that map and its overlay uint8 [F, Ho, Wo, 3]."""
         n, nf = int(m.shape[0]), int(m.shape[1])
         Ho, Wo = int(self.out_size[0]), int(self.out_size[1])
         rec = {"frames": (self.f_off, self.f_off + nf), "cls_probs": c, "ready": None}
         geom = torch.zeros((0, nf, 5), dtype=torch.int32) if self.geometry else None    # (the table of a window without tracks)
         args = (m, torch.arange(n, dtype=torch.int32, device=self.dev), self.model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry)
-        if self.online == "labels":                                  # one plane per frame; a window without tracks is all background
+        if self.online in ("labels", "overlay"):                     # one plane per frame; a window without tracks is all background
             cs = copy_stream(self.model)
             dev = torch.empty(nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
-            geom = label_maps(m, self.model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry, dev, 0)
             host = self.model.pinned_mask_buffer((nf, Ho, Wo))
+            copies, pic = [(host, dev)], None
+            if self.overlay:                                         # ... and its picture over the frames pushed (a window without tracks: the frames)
+                pic = torch.empty(nf, Ho, Wo, 3, dtype=torch.uint8, device=self.dev)
+                geom = overlay_frames(m, self.model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry, dev, 0, self.frame_source,
+                                      self.f_off, self.style, pic, 0)
+                rec["overlay"] = self.model.pinned_mask_buffer((nf, Ho, Wo, 3))
+                copies.append((rec["overlay"], pic))
+            else:
+                geom = label_maps(m, self.model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry, dev, 0)
             rec["ready"] = torch.cuda.Event()
-            geom = to_host(cs, self.side, dev, [(host, dev)], geom, rec["ready"])
+            geom = to_host(cs, self.side, dev, copies, geom, rec["ready"])
+            if pic is not None:
+                pic.record_stream(cs)
             rec["labels"] = host
         elif self.online == "rle":
             rec["rles"] = []
@@ -401,5 +525,6 @@ class ClipMerger:
             self.main.wait_stream(self.side)
             for _, m in self.windows:
                 m.record_stream(self.main)
+        kw = {"frame_source": self.frame_source} if self.overlay else {}
         return self.model.inference_video(self.out_size, self.cls_clips, self.windows, self.frame_hw, self.f_off, early=self.early,
-                                          emit_masks=self.emit_masks)
+                                          emit_masks=self.emit_masks, **kw)

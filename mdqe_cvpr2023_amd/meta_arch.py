@@ -108,6 +108,12 @@ class MDQE(nn.Module):
         # ("pred_masks" is []: no dense-mask kernels, pinned buffers or copies).  With geometry_output also "pred_label_boxes" /
         # "pred_label_areas" of the labels' visible regions.  False: nothing changes.  (A property: see `label_output` below.)
         self.label_output = False
+        # True: forward() on a video adds "pred_overlay" (uint8 [L, Ho, Wo, 3], pinned host: the label map painted over the frames handed
+        # in, at their uploaded size -- before `resize_on_device` -- nearest-sampled to the output size; pixel-interleaved, channel order =
+        # the frames'; ops.render_overlay behind ops.final_label_map, 3 bytes per pixel however many tracks) and "pred_track_ids".  The map
+        # itself is returned only with label_output.  `overlay_style` (render.Style): alpha, contour reach, palette.  Videos only (the COCO
+        # image branch has no overlay), one device (sharding.py refuses it).  False: nothing changes.  (Properties: see below.)
+        self.overlay_output = False
         self.merge_on_cpu = None                    # None: cfg.merge_on_cpu (MODEL.MDQE.MERGE_ON_CPU); True / False override it
         # Final masks of a tracker window leave the device when the window is flushed (pinned host buffers, copied under the later
         # windows' compute) instead of in one pass + one 100-MB copy after the last window.  Independent of MERGE_ON_CPU, which in the
@@ -266,6 +272,32 @@ class MDQE(nn.Module):
         if value:
             self.check_label_capacity()
         self.__dict__["_label_output"] = value
+
+    @property
+    def overlay_output(self):
+        return self.__dict__.get("_overlay_output", False)
+
+    @overlay_output.setter
+    def overlay_output(self, value):
+        if value is not False and value is not True:
+            raise ValueError("overlay_output must be False or True, got %r" % (value,))
+        if value:
+            self.check_label_capacity()
+        self.__dict__["_overlay_output"] = value
+
+    @property
+    def overlay_style(self):
+        if "_overlay_style" not in self.__dict__:
+            from .render import Style
+            self.__dict__["_overlay_style"] = Style()
+        return self.__dict__["_overlay_style"]
+
+    @overlay_style.setter
+    def overlay_style(self, value):
+        from .render import Style
+        if not isinstance(value, Style):
+            raise ValueError("overlay_style must be a render.Style, got %r" % (value,))
+        self.__dict__["_overlay_style"] = value
 
     def check_label_capacity(self):
         """uint8 labels are tracker row + 1: the bank may hold at most 255 rows."""
@@ -757,9 +789,10 @@ class MDQE(nn.Module):
             raise RuntimeError("halo exchange: the chunk has no full-length group for its straddling clips (chunk_plan(..., halo_exchange=True) "
                                "merges a short last chunk into its neighbour)")
 
-    def merge_clips(self, results, frame_hw, out_size, mask_hw, n_frames=None):
-        """Tracker + window flushes + video merge (mdqe/mdqe.py:337-366) over clip results in global order."""
-        m = ClipMerger(self, frame_hw, out_size, mask_hw, n_frames)
+    def merge_clips(self, results, frame_hw, out_size, mask_hw, n_frames=None, frame_source=None):
+        """Tracker + window flushes + video merge (mdqe/mdqe.py:337-366) over clip results in global order.  frame_source: the video's
+        frames as handed in (merge.FrameStore), what `overlay_output` paints on."""
+        m = ClipMerger(self, frame_hw, out_size, mask_hw, n_frames, frame_source=frame_source)
         buf = []
         for item in results:                       # the clips of one decoder batch go to the tracker together
             buf.append(item)
@@ -831,7 +864,13 @@ class MDQE(nn.Module):
     def _frames_for(self, video):
         """(frames on the device, upload events, original (h0, w0)) of one input dict; the optional device-side resize
         (the mapper's eval augmentation) needs the whole upload."""
+        return self._frames_and_source(video)[:4]
+
+    def _frames_and_source(self, video):
+        """`_frames_for` and, behind it, the frames as uploaded -- before the device-side resize, what an overlay is painted on -- with
+        the event behind their upload (None: nothing was in flight) and whether an upload made them (else they may be the caller's tensor)."""
         frames_dev, h2d = self.upload_frames(video["image"])
+        src, src_ready, uploaded = frames_dev, (h2d[-1][1] if h2d else None), bool(h2d)
         h0, w0 = int(frames_dev.shape[-2]), int(frames_dev.shape[-1])
         if self.resize_on_device and frames_dev.dtype == torch.uint8:
             from .preprocess import resize_shortest_edge
@@ -839,20 +878,28 @@ class MDQE(nn.Module):
                 torch.cuda.current_stream(self.device).wait_event(h2d[-1][1])
                 h2d = None
             frames_dev = resize_shortest_edge(frames_dev, self.cfg.min_size_test, self.cfg.max_size_test)
-        return frames_dev, h2d, h0, w0
+        return frames_dev, h2d, h0, w0, src, src_ready, uploaded
+
+    def _frame_source(self, src, src_ready):
+        """The whole video as the frame source of an overlay (merge.FrameStore), or None with overlay_output off."""
+        if not self.overlay_output:
+            return None
+        store = merge.FrameStore()
+        store.add(0, src, src_ready)
+        return store
 
     def inference_vis(self, batched_inputs, trace=None):
         """mdqe/mdqe.py:291-366 with the compute-once schedule (same clips, same flush points)."""
         cfg = self.cfg
         video = batched_inputs[0]
-        frames_dev, h2d, h0, w0 = self._frames_for(video)
+        frames_dev, h2d, h0, w0, src, src_ready, _ = self._frames_and_source(video)
         L, h, w = frames_dev.shape[0], int(frames_dev.shape[-2]), int(frames_dev.shape[-1])
         out_size = (video.get("height", h0), video.get("width", w0))       # the mapper reports the ORIGINAL size as height/width
         geo = self.engine.geometry(h, w)
         ms = cfg.match_stride
         clips = self.clip_schedule(L, cfg.n_frames_test, cfg.clip_stride)
         return self.merge_clips(self.iter_clip_results(frames_dev, clips, 0, trace, h2d=h2d), (h, w), out_size,
-                                (geo.Hp // ms, geo.Wp // ms), n_frames=L)
+                                (geo.Hp // ms, geo.Wp // ms), n_frames=L, frame_source=self._frame_source(src, src_ready))
 
     def forward_stream(self, batches):
         """An eval loop over videos: yields `forward(b)` for every b of the iterable `batches`, in order, bit-identical to
@@ -869,9 +916,10 @@ class MDQE(nn.Module):
                 raise RuntimeError("MDQE eval takes exactly one video per call (mdqe/mdqe.py:292)")
             cfg = self.cfg
             video = b[0]
-            frames_dev, h2d, h0, w0 = self._frames_for(video)
+            frames_dev, h2d, h0, w0, src, src_ready, _ = self._frames_and_source(video)
             L, h, w = frames_dev.shape[0], int(frames_dev.shape[-2]), int(frames_dev.shape[-1])
-            st = {"done_frames": False, "out_size": (video.get("height", h0), video.get("width", w0)), "hw": (h, w), "L": L}
+            st = {"done_frames": False, "out_size": (video.get("height", h0), video.get("width", w0)), "hw": (h, w), "L": L,
+                  "source": self._frame_source(src, src_ready)}
             geo = self.engine.geometry(h, w)
             st["mask_hw"] = (geo.Hp // cfg.match_stride, geo.Wp // cfg.match_stride)
             clips = self.clip_schedule(L, cfg.n_frames_test, cfg.clip_stride)
@@ -916,7 +964,7 @@ class MDQE(nn.Module):
                 raise st["error"]
             if st["done_frames"]:
                 look_ahead(st)
-            out = self.merge_clips(st["gen"], st["hw"], st["out_size"], st["mask_hw"], n_frames=st["L"])
+            out = self.merge_clips(st["gen"], st["hw"], st["out_size"], st["mask_hw"], n_frames=st["L"], frame_source=st["source"])
             if state["next"] is None:
                 look_ahead(st)                             # (the generator ends only after its callback; belt and braces)
             state["cur"], state["next"] = state["next"], None
@@ -926,15 +974,17 @@ class MDQE(nn.Module):
         while state["cur"] is not None:
             yield guarded(step)
 
-    def online_video(self, height=None, width=None, emit="masks", keep=False, geometry=False):
+    def online_video(self, height=None, width=None, emit="masks", keep=False, geometry=False, style=None):
         """An online session over ONE video whose frames arrive in pushes (a camera, a stream, a video too long to hold): push()
         returns each tracker window as soon as it is final, close() the rest, result() the video-level scores / labels / tracks.
         height / width: output mask size (default: the frame size); emit: "masks" (bool [n, F, H, W] per window), "rle" or "labels" (one
-        uint8 [F, H, W] map per window: which track owns each pixel, `label_output`'s rule); keep: result() also carries forward()'s
-        "pred_masks" / "pred_rles" / "pred_label_map", bit-identical; geometry: every window carries `boxes` / `areas` of its
-        final masks and result() "pred_boxes" / "pred_areas" (with or without keep), equal to forward()'s with geometry_output.  See online.py."""
+        uint8 [F, H, W] map per window: which track owns each pixel, `label_output`'s rule) or "overlay" (that map and, painted from it
+        over the frames pushed, one uint8 [F, H, W, 3] picture per window in `style`, a render.Style; `overlay_output`'s picture); keep:
+        result() also carries forward()'s "pred_masks" / "pred_rles" / "pred_label_map" / "pred_overlay", bit-identical; geometry: every
+        window carries `boxes` / `areas` of its final masks and result() "pred_boxes" / "pred_areas" (with or without keep), equal to
+        forward()'s with geometry_output.  See online.py."""
         from .online import OnlineVideo
-        return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep, geometry=geometry)
+        return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep, geometry=geometry, style=style)
 
     def inference_image(self, batched_inputs):
         """COCO single-image branch: MDQE.forward :213-236 -> mdqe.forward (models/mdqe.py:62-70) -> decoder
@@ -1003,9 +1053,10 @@ class MDQE(nn.Module):
 
     track_geometry = staticmethod(merge.track_geometry)
 
-    def inference_video(self, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True):
+    def inference_video(self, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True, frame_source=None):
         """mdqe/mdqe.py:430-471: the video's result from its flushed windows (merge.video_result)."""
-        return merge.video_result(self, image_size, cls_clips, windows, frame_hw, n_frames, early=early, emit_masks=emit_masks)
+        return merge.video_result(self, image_size, cls_clips, windows, frame_hw, n_frames, early=early, emit_masks=emit_masks,
+                                  frame_source=frame_source)
 
 
 class MDQE_MI355X(MDQE):

@@ -23,6 +23,16 @@ track_id + 1 of the track that owns it -- the largest up-sampled logit among the
 for background (ops.final_label_map; 1 byte per pixel however many tracks).  geometry=True then describes the labels' visible regions
 (win.boxes / win.areas, result()'s "pred_label_boxes" / "pred_label_areas"); keep=True adds "pred_label_map", equal to forward()'s
 with model.label_output.  A label can name a track that misses the video-level top-k: rle.labels_keep(map, result["pred_track_ids"]).
+
+emit="overlay" (style=render.Style(alpha=0.5, contour=1, palette=None)): what emit="labels" gives and, painted from the map on the
+device, `win.overlay`: uint8 [F, H, W, 3] on the host, pixel-interleaved, channel order = the frames' -- the frames that were pushed
+with every track's region blended towards its colour and a full-colour line where regions meet (ops.render_overlay; 3 bytes per pixel
+of read-back however many tracks).  A track's colour depends on its tracker row only, so it is the same in every window.  win.labels
+says which colour is which track.  The picture is painted on the frames AS PUSHED: when height / width exceed their size it is a nearest
+up-sample of them -- for a sharp picture push original-size uint8 frames and set model.resize_on_device.  The session keeps each push's
+frames on the device until the windows they belong to are out: after any push `ov.frames_held <= frames not yet emitted + the largest
+push - 1` (whole pushes are dropped), so the store does not grow with the video.  keep=True adds "pred_overlay" [L, H, W, 3] and
+"pred_label_map" to result(), equal to forward()'s with model.overlay_output / label_output.
 """
 import contextlib
 import dataclasses
@@ -108,8 +118,9 @@ class Window:
     with emit="rle", per track per frame {"size", "counts"}.  With geometry=True: boxes float32 [n, f1-f0, 4] ([xmin, ymin, xmax+1,
     ymax+1] in output pixels, zeros for an empty mask) and areas int64 [n, f1-f0] of those masks.  With emit="labels": `labels`, uint8
     [f1-f0, H, W] on the host (track_ids[i] + 1 where track i owns the pixel, 0 = background), masks and rles None, boxes / areas those
-    of the labels' visible regions.  (`labels` is an init-only pseudo-field stored as a plain attribute: dataclasses.fields(Window) is
-    what it was.)"""
+    of the labels' visible regions.  With emit="overlay": `labels` as above and `overlay`, uint8 [f1-f0, H, W, 3] on the host, the
+    frames with that map painted on.  (`labels` and `overlay` are init-only pseudo-fields stored as plain attributes:
+    dataclasses.fields(Window) is what it was.)"""
     frames: tuple
     track_ids: list
     cls_probs: torch.Tensor
@@ -118,17 +129,24 @@ class Window:
     boxes: torch.Tensor = None
     areas: torch.Tensor = None
     labels: dataclasses.InitVar[torch.Tensor] = None
+    overlay: dataclasses.InitVar[torch.Tensor] = None
 
-    def __post_init__(self, labels):
+    def __post_init__(self, labels, overlay):
         self.labels = labels
+        self.overlay = overlay
 
 
 class OnlineVideo:
-    def __init__(self, model, height=None, width=None, emit="masks", keep=False, geometry=False):
-        if emit not in ("masks", "rle", "labels"):
-            raise ValueError("online_video: emit must be 'masks', 'rle' or 'labels'")
-        if emit == "labels":
+    def __init__(self, model, height=None, width=None, emit="masks", keep=False, geometry=False, style=None):
+        if emit not in ("masks", "rle", "labels", "overlay"):
+            raise ValueError("online_video: emit must be 'masks', 'rle', 'labels' or 'overlay'")
+        if emit in ("labels", "overlay"):
             model.check_label_capacity()
+        from .render import Style
+        if style is not None and (emit != "overlay" or not isinstance(style, Style)):
+            raise ValueError("online_video: style must be a render.Style and goes with emit='overlay'")
+        self.style = (style if style is not None else Style()) if emit == "overlay" else None
+        self.store = None                         # emit="overlay": the frames pushed and not yet painted (merge.FrameStore)
         if model.cfg.is_coco:
             raise RuntimeError("online_video: a COCO image config takes the single-image branch; online inference is for videos")
         if model.device.type != "cuda":
@@ -146,6 +164,12 @@ class OnlineVideo:
         self.kept = []
         self.closed = False
         self._result = None
+
+    @property
+    def frames_held(self):
+        """Frames the session holds on the device for painting (emit="overlay"; else 0): at most those no window has emitted yet plus
+        the largest push - 1."""
+        return self.store.frames_held if self.store is not None else 0
 
     @contextlib.contextmanager
     def _ctx(self):
@@ -166,8 +190,11 @@ class OnlineVideo:
         self.geo = model.engine.geometry(h, w)
         self.out_size = (int(self.height if self.height is not None else h0), int(self.width if self.width is not None else w0))
         self.mask_hw = (self.geo.Hp // cfg.match_stride, self.geo.Wp // cfg.match_stride)
+        if self.emit == "overlay":
+            from .merge import FrameStore
+            self.store = FrameStore()
         self.merger = ClipMerger(model, self.hw, self.out_size, self.mask_hw, n_frames=None, online=self.emit,
-                                 geometry=self.geometry)
+                                 geometry=self.geometry, frame_source=self.store, style=self.style)
         shapes = model.engine.cache_shapes(self.geo)
         per_frame = 4 * sum(int(np.prod(sh)) for sh in shapes.values())
         forced = int(os.environ.get("MDQE_CACHE_FRAMES", "0"))
@@ -204,8 +231,14 @@ class OnlineVideo:
                 boxes, areas = R.geom_to_boxes(r["geom"])
                 self.geoms.append((r["frames"][0], r["frames"][1] - r["frames"][0], n, r["geom"]))
             out.append(Window(frames=r["frames"], track_ids=list(range(n)), cls_probs=r["cls_probs"],
-                              masks=r.get("masks"), rles=r.get("rles"), boxes=boxes, areas=areas, labels=r.get("labels")))
+                              masks=r.get("masks"), rles=r.get("rles"), boxes=boxes, areas=areas, labels=r.get("labels"),
+                              overlay=r.get("overlay")))
         del self.merger.emitted[:]
+        if self.store is not None:
+            # the chunks that lie wholly before the first frame no window has emitted are done with; what stays and may be the caller's
+            # own device tensor is copied before control returns (the caller may refill its buffer for the next push)
+            self.store.drop_before(self.merger.f_off)
+            self.store.own()
         if self.keep:
             self.kept.extend(out)
         return out
@@ -223,11 +256,13 @@ class OnlineVideo:
             raise RuntimeError("online_video: frame size %s differs from the first push's %s" % (hw0, self.in_hw))
         with self._ctx():
             model = self.model
-            frames_dev, h2d, h0, w0 = model._frames_for({"image": frames})
+            frames_dev, h2d, h0, w0, src, src_ready, uploaded = model._frames_and_source({"image": frames})
             if self.merger is None:
                 self.in_hw = hw0
                 self._start(frames_dev, h0, w0)
             recs, r0 = [], self.received
+            if self.store is not None:
+                self.store.add(r0, src, src_ready, owned=uploaded)
             if n > self.chunk and h2d:
                 torch.cuda.current_stream(model.device).wait_event(h2d[-1][1])   # (sub-chunks: the whole upload first)
                 h2d = None
@@ -259,7 +294,7 @@ class OnlineVideo:
     def result(self):
         """After close(): {"image_size", "pred_scores", "pred_labels", "pred_track_ids"} -- the video-level top-k of
         `inference_video`; pred_track_ids[j] is the track behind output j.  keep=True adds "pred_masks" (or "pred_rles", or
-        "pred_label_map"), assembled from the windows handed out, equal to forward()'s; geometry=True adds "pred_boxes" / "pred_areas"
+        "pred_label_map", or that and "pred_overlay"), assembled from the windows handed out, equal to forward()'s; geometry=True adds "pred_boxes" / "pred_areas"
         (forward()'s with model.geometry_output; emit="labels": "pred_label_boxes" / "pred_label_areas"), with or without keep."""
         if not self.closed:
             raise RuntimeError("online_video: result() before close()")
@@ -272,11 +307,13 @@ class OnlineVideo:
         res = {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels, "pred_track_ids": list(inst)}
         if self.geometry:
             geo = self.model.track_geometry(list(inst), self.received, (Ho, Wo), self.geoms)
-            if self.emit == "labels":                 # (the windows' tables describe the labels' visible regions, not the full masks)
+            if self.emit in ("labels", "overlay"):                 # (the windows' tables describe the labels' visible regions, not the full masks)
                 geo = {"pred_label_boxes": geo["pred_boxes"], "pred_label_areas": geo["pred_areas"]}
             res.update(geo)
-        if self.keep and self.emit == "labels":
+        if self.keep and self.emit in ("labels", "overlay"):
             res["pred_label_map"] = torch.cat([w.labels for w in self.kept])
+            if self.emit == "overlay":
+                res["pred_overlay"] = torch.cat([w.overlay for w in self.kept])
         elif self.keep:
             from . import merge
             wins = [(w.frames[0], w.frames[1] - w.frames[0], len(w.track_ids), w.rles if self.emit == "rle" else w.masks) for w in self.kept]

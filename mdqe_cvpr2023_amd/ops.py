@@ -600,6 +600,45 @@ def final_label_map(logits, inst_idx, factor, h, w, Ho, Wo, out, f_off, geom=Non
     return out, geom
 
 
+def render_overlay(labels, frames, palette, out, f_off=0, a256=128, contour=1):
+    """The picture of a label map: out[f_off + f] (uint8 [>= f_off + F, Ho, Wo, 3], CUDA, contiguous, pixel-interleaved) painted from
+    labels (uint8 [F, Ho, Wo], ops.final_label_map's output), frames ([F, 3, h0, w0] uint8 or float32, each frame contiguous, the frames
+    any stride >= 3*h0*w0 apart -- a view into a larger store -- or None: onto black) and palette (uint8 [256, 3] in the frames' channel
+    order).  Background keeps the frame (nearest-sampled at another size), a labelled pixel becomes (s*(256 - a256) + colour*a256 + 128)
+    >> 8, and one with a neighbour of another label within `contour` pixels along an axis, inside the image, the plain colour: the
+    integer rule of include/mdqe_hip.h, mdqe_render_overlay_u8.  a256 in 0..256, contour in 0..3.  -> out."""
+    # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
+    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        raise RuntimeError("render_overlay: labels must be contiguous uint8 [F, Ho, Wo]")
+    F, Ho, Wo = (int(v) for v in labels.shape)
+    if not isinstance(a256, int) or not isinstance(contour, int) or not 0 <= a256 <= 256 or not 0 <= contour <= 3:
+        raise RuntimeError("render_overlay: a256 must be an int in 0..256 and contour an int in 0..3, got %r, %r" % (a256, contour))
+    if Ho < 1 or Wo < 1 or Ho * Wo * 3 >= 2 ** 31 or F * Ho * Wo >= 2 ** 31:
+        raise RuntimeError("render_overlay: Ho, Wo must be positive with Ho*Wo*3 < 2^31 and F*Ho*Wo < 2^31, got %s" % (tuple(labels.shape),))
+    if not torch.is_tensor(palette) or palette.dtype != torch.uint8 or tuple(palette.shape) != (256, 3) or not palette.is_contiguous():
+        raise RuntimeError("render_overlay: palette must be contiguous uint8 [256, 3]")
+    if (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 4 or tuple(out.shape[1:]) != (Ho, Wo, 3) or f_off < 0
+            or f_off + F > out.shape[0] or not out.is_contiguous()):
+        raise RuntimeError("render_overlay: out must be contiguous CUDA uint8 [>= f_off + F = %d, Ho, Wo, 3]" % (f_off + F))
+    h0 = w0 = stride = 0
+    if frames is not None:
+        if (not torch.is_tensor(frames) or frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4
+                or int(frames.shape[0]) != F or int(frames.shape[1]) != 3 or frames.shape[2] < 1 or frames.shape[3] < 1):
+            raise RuntimeError("render_overlay: frames must be uint8 or float32 [F = %d, 3, h0, w0] or None" % F)
+        h0, w0 = int(frames.shape[2]), int(frames.shape[3])
+        stride = int(frames.stride(0)) if F > 1 else 3 * h0 * w0
+        if tuple(frames.stride()[1:]) != (h0 * w0, w0, 1) or stride < 3 * h0 * w0 or h0 * Ho >= 2 ** 31 or w0 * Wo >= 2 ** 31:
+            raise RuntimeError("render_overlay: every frame must be contiguous and the frames a stride >= 3*h0*w0 apart, got strides %s"
+                               % (tuple(frames.stride()),))
+    for t, name in ((labels, "labels"), (palette, "palette"), (out, "out"), (frames, "frames")):
+        if t is not None and (not t.is_cuda or t.device != out.device):
+            raise RuntimeError("render_overlay: %s must be a CUDA tensor on out's device, got %s" % (name, t.device))
+    check(lib.mdqe_render_overlay_u8(ptr(frames) if frames is not None else None, int(frames is not None and frames.dtype == torch.uint8),
+                                     stride, h0, w0, ptr(labels), F, Ho, Wo, ptr(palette), a256, contour, ptr(out), f_off, cur_stream()),
+          "render_overlay")
+    return out
+
+
 def layernorm_post(x, gamma, beta, post, eps=1e-5, out=None):
     """out = LN(x)*gamma + beta + post."""
     _chk(x, "x"); _chk(post, "post")

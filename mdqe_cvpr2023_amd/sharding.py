@@ -555,6 +555,9 @@ class _Job:
         self.halo_dims = (geo.N, cfg.hidden_dim, mask_hw[0], mask_hw[1], cfg.mask_dim) if halo_exchange else None
         self.halo_pg = halo_group(dist, world) if halo_exchange and not local_halo else None
         self.merger = self.replay = None
+        if getattr(model, "overlay_output", False):
+            raise ValueError("overlay_output is not offered by the sharded driver: rank 0 does not hold every frame of the video (paint "
+                             "from pred_label_map on the host, or run the video on one device)")
         if not root_only or rank == 0:
             self.merger = ClipMerger(model, (h, w), out_size, mask_hw, n_frames=max(c[2] for c in plan), emit_masks=emit_masks)
             if getattr(model, "merge_on_cpu", None) is None and hasattr(self.merger, "merge_on_cpu"):
