@@ -468,6 +468,25 @@ int mdqe_final_masks_rle_geom(const float* logits, int n_sel, const int* inst_id
 int mdqe_final_label_map_u8(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
                             int h, int w, int Ho, int Wo, unsigned char* out, int f_off, int* geom, void* stream);
 
+/* A window's final masks scored against ground truth without leaving the device: the integers behind the video IoU of the YTVIS
+ * evaluator (mdqe/data/pycocotools/ytvoseval.py:173-219).  logits, n_sel, inst_idx_dev, Fw, Hm, Wm, factor, h, w, Ho, Wo are exactly
+ * mdqe_final_masks_u8's, and b_k(f, Y, X), the bit of selected row k at window frame f and output pixel (Y, X), is that entry point's
+ * bit (the same device expression: one definition).  gt_bits: uint32 [>= f_off + Fw, Ho, Wo]; bit g (0 <= g < G <= 32) of the word at
+ * (f_off + f, Y, X) says that ground-truth track g holds the pixel.  Ground-truth tracks may overlap; bit 31 is an ordinary bit.
+ *   inter[k * inter_row_stride + g]  is INCREASED by the number of (f, Y, X), 0 <= f < Fw, with b_k set and bit g set.  The caller
+ *                                    zeroes it once per video; consecutive windows add up; 64-bit, since a long 640p video passes
+ *                                    2^31 pixels.  Columns g >= G of a row are not touched.
+ *   area[k * Fw + f]                 is OVERWRITTEN with the number of (Y, X) with b_k set: column 0 of mdqe_final_masks_u8_geom's
+ *                                    table (int32 [n_sel * Fw]).
+ * Integer counters only (ballots, popcounts, integer LDS and global atomics): exact, identical from run to run.  (long)Ho*Wo < 2^31,
+ * Hm*Wm < 2^31, n_sel*Fw < 2^31, 1 <= G <= 32, inter_row_stride >= G and f_off >= 0 are checked before any pointer is looked at
+ * (MDQE_EINVAL); n_sel == 0 or Fw == 0 returns OK and launches nothing (inter and area stay as they are).  Any n_sel (rows go in
+ * chunks of 256 per block; at most 34 KB of LDS).  Never allocates, never synchronises. */
+int mdqe_final_masks_overlap(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
+                             int h, int w, int Ho, int Wo,
+                             const uint32_t* gt_bits, int G, int f_off,
+                             unsigned long long* inter, long inter_row_stride, int* area, void* stream);
+
 /* The picture a viewer paints from that map: out[f_off + f, Y, X, c] (uint8, pixel-interleaved, [>= f_off + F, Ho, Wo, 3]) from labels
  * (uint8 [F, Ho, Wo], what mdqe_final_label_map_u8 writes), the frames the caller handed in (frames: [F, 3, h0, w0] planar, uint8 if
  * is_u8 else float32, consecutive frames frame_stride ELEMENTS apart -- a view into a larger store works -- or NULL) and palette (uint8

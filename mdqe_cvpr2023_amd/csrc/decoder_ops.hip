@@ -1,6 +1,7 @@
 // Decoder-side kernels of the MDQE path for gfx950: small-sequence multi-head attention, grid-guided
 // query selection, multi-level content sampling, and the fused final-mask kernel.
 #include "common.h"
+#include "final_mask.h"
 #include <cstdlib>
 
 // ------------------------------------------------------------------------------------------------
@@ -339,39 +340,7 @@ extern "C" int mdqe_sample_levels_mean_f32(const float* tokens, int NI, long N, 
 // aligned_bilinear (util/misc.py:485-507) in closed form: pixel p reads source (max(p - f/2, 0))/f, clamped to the map.
 // logits [n, F, Hm, Wm] (mean logits of one tracker window); out uint8 [n, F_total, Ho, Wo] written at frame f_off.
 // ------------------------------------------------------------------------------------------------
-// one output pixel of the final mask (shared by the dense, the RLE and the label-map form: identical arithmetic, identical bits), in
-// three steps: where the pixel reads (the same for every map of a window), the up-sampled logit there, and the threshold on it
-struct MaskTaps { int y0, y1, x0, x1; float ly, lx; };
-
-__device__ __forceinline__ MaskTaps final_mask_taps(int Hm, int Wm, int factor, int h, int w, float sy_scale, float sx_scale, int Y, int X) {
-  const int sy = min((int)floorf(Y * sy_scale), h - 1), sx = min((int)floorf(X * sx_scale), w - 1);
-  const float fy = (float)max(sy - factor / 2, 0) / (float)factor, fx = (float)max(sx - factor / 2, 0) / (float)factor;
-  const int y0 = min((int)fy, Hm - 1), x0 = min((int)fx, Wm - 1);
-  const int y1 = min(y0 + 1, Hm - 1), x1 = min(x0 + 1, Wm - 1);
-  return MaskTaps{y0, y1, x0, x1, fy - y0, fx - x0};
-}
-
-// (m: row 0 of the rows t.y0 / t.y1 count from, Wm floats apart)
-__device__ __forceinline__ float final_mask_value_at(const float* __restrict__ m, int Wm, const MaskTaps& t) {
-  const float top = m[t.y0 * Wm + t.x0] * (1.f - t.lx) + m[t.y0 * Wm + t.x1] * t.lx;
-  const float bot = m[t.y1 * Wm + t.x0] * (1.f - t.lx) + m[t.y1 * Wm + t.x1] * t.lx;
-  return top * (1.f - t.ly) + bot * t.ly;
-}
-
-__device__ __forceinline__ float final_mask_value(const float* __restrict__ m, int Hm, int Wm, int factor, int h, int w, float sy_scale,
-                                                  float sx_scale, int Y, int X) {
-  return final_mask_value_at(m, Wm, final_mask_taps(Hm, Wm, factor, h, w, sy_scale, sx_scale, Y, X));
-}
-
-__device__ __forceinline__ int final_mask_bit(float v) {
-  const float p = 1.0f / (1.0f + expf(-v));
-  return p > 0.5f ? 1 : 0;
-}
-
-__device__ __forceinline__ int final_mask_pixel(const float* __restrict__ m, int Hm, int Wm, int factor, int h, int w, float sy_scale,
-                                                float sx_scale, int Y, int X) {
-  return final_mask_bit(final_mask_value(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, Y, X));
-}
+// (the pixel itself -- final_mask_taps / _value_at / _value / _bit / _pixel -- is in final_mask.h, shared with score_ops.hip)
 
 __global__ void __launch_bounds__(256)
 final_mask_kernel(const float* __restrict__ lg, int Fw, int Hm, int Wm, int factor, int h, int w, int Ho, int Wo,

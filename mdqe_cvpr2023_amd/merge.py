@@ -5,7 +5,9 @@ windows in one pass at the end (`video_result`).  What the three share is writte
 -> masks / run boundaries, with or without geometry), `to_host` (the hop on the copy stream), `rle.positions_to_rles`, `stitch`.
 `label_maps` is the third output form (model.label_output, online "labels"): one uint8 plane per frame that names the track owning each
 pixel, from the same three places; its frames are disjoint between windows, so it needs no `stitch`.  `overlay_frames` is the fourth
-(model.overlay_output, online "overlay"): that map painted over the frames the caller handed in (`FrameStore`), uint8 [F, Ho, Wo, 3]."""
+(model.overlay_output, online "overlay"): that map painted over the frames the caller handed in (`FrameStore`), uint8 [F, Ho, Wo, 3].
+`OverlapTables` is not an output form but a score: with a ground truth handed in (vis_score.GroundTruth), every flushed window's final
+masks are counted against it where they are decided (ops.final_masks_overlap) -- "pred_gt", beside whatever form the masks take."""
 import contextlib
 import dataclasses
 import os
@@ -38,6 +40,76 @@ def label_maps(m, stride, frame_hw, out_size, geometry, out, f_off):
     idx = torch.arange(n, dtype=torch.int32, device=m.device)
     geom = ops.final_label_map(m, idx, stride, fh, fw, Ho, Wo, out, f_off, geom=True if geometry else None)[1]
     return geom.view(n, int(m.shape[1]), 5) if geometry else None
+
+
+class OverlapTables:
+    """A video's overlap counts against its ground truth (vis_score.GroundTruth `gt`), gathered window by window for ALL tracker rows
+    (idx = arange(n), as `label_maps` does: every path then agrees bit for bit, and the end only selects rows).  On the device: `inter`
+    int64 [rows, 32 * groups] (column g = ground-truth track g; one kernel call per group of 32 per window) and, per window, the
+    per-frame areas int32 [n, F]; frames before a track's first window count 0.  `result` reads both back once."""
+
+    def __init__(self, gt, device, out_size, rows):
+        if (int(out_size[0]), int(out_size[1])) != tuple(gt.size):
+            raise ValueError("ground_truth: its size %s is not the output size (height, width) = %s" % (tuple(gt.size), (int(out_size[0]), int(out_size[1]))))
+        self.gt, self.device, self.out_size = gt, device, (int(out_size[0]), int(out_size[1]))
+        # (a ground truth without tracks still yields the predictions' areas: one all-zero word, one column that stays 0)
+        self.words = gt.on(device) or [torch.zeros((gt.length,) + tuple(gt.size), dtype=torch.int32, device=device).view(torch.uint32)]
+        self.inter = torch.zeros(max(int(rows), 1), 32 * len(self.words), dtype=torch.int64, device=device)
+        # the words' upload and the table's zero-fill are queued on this stream, the windows' kernels on another: they wait for this
+        self.ready = torch.cuda.Event()
+        self.ready.record(torch.cuda.current_stream(device))
+        self.areas = []                                                # (f_off, frames, rows, int32 [rows, frames])
+
+    def window(self, m, stride, frame_hw, f_off):
+        """Window logits m [n, F, Hm, Wm] covering video frames [f_off, f_off + F), on the current stream."""
+        from . import ops
+        n, nf = int(m.shape[0]), int(m.shape[1])
+        if f_off + nf > self.gt.length:
+            raise RuntimeError("ground_truth: it holds %d frames, the video has reached frame %d" % (self.gt.length, f_off + nf))
+        if not n:
+            return
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(self.ready)
+        if n > self.inter.shape[0]:
+            self.inter = torch.cat([self.inter, self.inter.new_zeros(n - self.inter.shape[0], self.inter.shape[1])])
+        self.inter.record_stream(cur)
+        idx = torch.arange(n, dtype=torch.int32, device=self.device)
+        area = None
+        for j, w in enumerate(self.words):                             # (every group's call writes the same areas)
+            w.record_stream(cur)
+            area = ops.final_masks_overlap(m, idx, stride, frame_hw[0], frame_hw[1], self.out_size[0], self.out_size[1], w,
+                                           max(1, min(32, self.gt.G - 32 * j)), f_off, self.inter[:, 32 * j:], area)[1]
+        self.areas.append((f_off, nf, n, area.view(n, nf)))
+
+    def result(self, inst, n_frames, copy=None):
+        """res["pred_gt"] for the outputs whose tracker rows are `inst`: "inter" int64 [n_out, G], "pred_area" int64 [n_out, L], "gt_area"
+        int64 [G, L], "iou" float64 [n_out, G] (vis_score.iou_table).  One small read-back, on stream `copy` when the path has one."""
+        from .vis_score import iou_table
+        if int(n_frames) != self.gt.length:
+            raise ValueError("ground_truth: it holds %d frames, the video %d" % (self.gt.length, int(n_frames)))
+        G, n_out = self.gt.G, len(inst)
+        cur = torch.cuda.current_stream(self.device)
+        rows = max([n for _, _, n, _ in self.areas] + [max(inst) + 1 if n_out else 0, self.inter.shape[0]])
+        area = torch.zeros(rows, int(n_frames), dtype=torch.int32, device=self.device)
+        for f_off, nf, n, a in self.areas:
+            a.record_stream(cur)
+            area[:n, f_off:f_off + nf] = a
+        self.inter.record_stream(cur)
+        inter = self.inter
+        if rows > inter.shape[0]:
+            inter = torch.cat([inter, inter.new_zeros(rows - inter.shape[0], inter.shape[1])])
+        sel = torch.tensor(list(inst), dtype=torch.int64, device=self.device)
+        dev = torch.cat([inter[sel, :G], area[sel].to(torch.int64)], 1)
+        host = torch.empty(dev.shape, dtype=torch.int64, pin_memory=True)
+        side = copy if copy is not None else cur
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            host.copy_(dev, non_blocking=True)
+            dev.record_stream(side)
+        side.synchronize()
+        inter, pa = host[:, :G].clone(), host[:, G:].clone()
+        return {"inter": inter, "pred_area": pa, "gt_area": self.gt.gt_area.clone(),
+                "iou": torch.from_numpy(iou_table(inter.numpy(), pa.numpy(), self.gt.gt_area.numpy()))}
 
 
 class FrameStore:
@@ -209,16 +281,19 @@ class EarlyMasks:
     overlay: object = None                                            # overlay: ONE pinned uint8 [L, Ho, Wo, 3] per video (model.overlay_output)
 
 
-def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True, frame_source=None):
+def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True, frame_source=None, score=None):
     """mdqe/mdqe.py:430-471.  The x4 aligned-bilinear up-sampling, sigmoid, crop (:357-358), nearest resize to the original size and
     the 0.5 threshold (:458-462) run as ONE kernel per window; windows in which an instance did not exist yet stay zero (:442).
     `early` (EarlyMasks): the masks of every tracked instance are on the host already, only the selection is left.  Without it
-    (`windows`: (f_off, mean logits) per flushed window) the selected tracks' masks are produced here, in one pass and one copy."""
+    (`windows`: (f_off, mean logits) per flushed window) the selected tracks' masks are produced here, in one pass and one copy.
+    `score` (OverlapTables): the video's overlap counts against its ground truth, gathered at every flush on any path -> "pred_gt"."""
     sc, labels, inst = model.select_tracks(cls_clips)
     Ho, Wo = int(image_size[0]), int(image_size[1])
     res = {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels}
     if not emit_masks:
         return dict(res, pred_masks=[])
+    if score is not None:                                          # (OverlapTables: the counts of every window are in; select rows, read back)
+        res.update(pred_gt=score.result(inst, n_frames, model._copy_stream), pred_track_ids=list(inst))
     geometry = bool(model.geometry_output)
     labels = getattr(model, "label_output", False)
     overlay = (frame_source, model.overlay_style) if frame_source is not None and getattr(model, "overlay_output", False) else None
@@ -310,7 +385,7 @@ class ClipMerger:
     EARLY_TRACKS = 48                       # tracks per video the early-mask path budgets pinned memory for
 
     def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True, online=None, geometry=None, frame_source=None,
-                 style=None):
+                 style=None, ground_truth=None):
         self.model, self.frame_hw, self.out_size, self.mask_hw = model, frame_hw, out_size, mask_hw
         self.emit_masks = emit_masks                # False: scores / labels only (ranks > 0 of a sharded video)
         # boxes and areas of the final masks from the kernels that produce them (None: model.geometry_output; online sessions pass theirs)
@@ -328,6 +403,16 @@ class ClipMerger:
         if self.overlay and frame_source is None:
             raise ValueError("overlay output needs the frames of the whole video on this device; this path does not hold them (the sharded "
                              "driver does not offer it: rank 0 does not hold every frame)")
+        # a vis_score.GroundTruth: every flushed window's final masks are counted against it (OverlapTables); None: nothing is
+        self.score = None
+        if ground_truth is not None:
+            if n_frames is not None and int(n_frames) != ground_truth.length:
+                raise ValueError("ground_truth: it holds %d frames, the video %d" % (ground_truth.length, int(n_frames)))
+            if not emit_masks:
+                raise ValueError("ground_truth: a merger that emits no masks cannot score them")
+            if torch.device(model.device).type != "cuda":
+                raise ValueError("ground_truth: the overlap counts are a device kernel's; the model is on %s (the product has no CPU path)" % (model.device,))
+            self.score = OverlapTables(ground_truth, model.device, out_size, model.cfg.n_max_inst)
         self.emitted = []
         self.n_frames = n_frames                    # total frames of the video when known: enables the early mask path
         self.early = None                           # EarlyMasks, from the first window the early path takes
@@ -406,6 +491,8 @@ class ClipMerger:
                 c, m = self.tracker.get_result(is_last_clip=last)   # m: mean logits [n, F, Hm, Wm] of this window
                 self.cls_clips.append(c)
                 m = m.contiguous()
+                if self.score is not None:                          # on every path, at the flush: the counts do not wait for the masks' form
+                    self.score.window(m, cfg.match_stride, self.frame_hw, self.f_off)
                 # only the late path keeps the window's stride-4 logits for the rest of the video (under either MERGE_ON_CPU setting)
                 if not self.emit_masks:
                     pass
@@ -526,5 +613,7 @@ class ClipMerger:
             for _, m in self.windows:
                 m.record_stream(self.main)
         kw = {"frame_source": self.frame_source} if self.overlay else {}
+        if self.score is not None:
+            kw["score"] = self.score
         return self.model.inference_video(self.out_size, self.cls_clips, self.windows, self.frame_hw, self.f_off, early=self.early,
                                           emit_masks=self.emit_masks, **kw)

@@ -789,10 +789,11 @@ class MDQE(nn.Module):
             raise RuntimeError("halo exchange: the chunk has no full-length group for its straddling clips (chunk_plan(..., halo_exchange=True) "
                                "merges a short last chunk into its neighbour)")
 
-    def merge_clips(self, results, frame_hw, out_size, mask_hw, n_frames=None, frame_source=None):
+    def merge_clips(self, results, frame_hw, out_size, mask_hw, n_frames=None, frame_source=None, ground_truth=None):
         """Tracker + window flushes + video merge (mdqe/mdqe.py:337-366) over clip results in global order.  frame_source: the video's
-        frames as handed in (merge.FrameStore), what `overlay_output` paints on."""
-        m = ClipMerger(self, frame_hw, out_size, mask_hw, n_frames, frame_source=frame_source)
+        frames as handed in (merge.FrameStore), what `overlay_output` paints on.  ground_truth: the video's vis_score.GroundTruth or None
+        (`_ground_truth`): the final masks are counted against it, "pred_gt"."""
+        m = ClipMerger(self, frame_hw, out_size, mask_hw, n_frames, frame_source=frame_source, ground_truth=ground_truth)
         buf = []
         for item in results:                       # the clips of one decoder batch go to the tracker together
             buf.append(item)
@@ -880,6 +881,22 @@ class MDQE(nn.Module):
             frames_dev = resize_shortest_edge(frames_dev, self.cfg.min_size_test, self.cfg.max_size_test)
         return frames_dev, h2d, h0, w0, src, src_ready, uploaded
 
+    @staticmethod
+    def _ground_truth(video, out_size=None, n_frames=None):
+        """The "ground_truth" of an input dict (a vis_score.GroundTruth; the video is then scored against it: res["pred_gt"]) or None,
+        checked against the output size and the video's length where given."""
+        gt = video.get("ground_truth")
+        if gt is None:
+            return None
+        from .vis_score import GroundTruth
+        if not isinstance(gt, GroundTruth):
+            raise ValueError("ground_truth must be a vis_score.GroundTruth, got %s" % type(gt).__name__)
+        if out_size is not None and tuple(gt.size) != (int(out_size[0]), int(out_size[1])):
+            raise ValueError("ground_truth: its size %s is not the output size (height, width) = %s" % (tuple(gt.size), (int(out_size[0]), int(out_size[1]))))
+        if n_frames is not None and gt.length != int(n_frames):
+            raise ValueError("ground_truth: it holds %d frames, the video %d" % (gt.length, int(n_frames)))
+        return gt
+
     def _frame_source(self, src, src_ready):
         """The whole video as the frame source of an overlay (merge.FrameStore), or None with overlay_output off."""
         if not self.overlay_output:
@@ -898,8 +915,9 @@ class MDQE(nn.Module):
         geo = self.engine.geometry(h, w)
         ms = cfg.match_stride
         clips = self.clip_schedule(L, cfg.n_frames_test, cfg.clip_stride)
+        gt = self._ground_truth(video, out_size, L)
         return self.merge_clips(self.iter_clip_results(frames_dev, clips, 0, trace, h2d=h2d), (h, w), out_size,
-                                (geo.Hp // ms, geo.Wp // ms), n_frames=L, frame_source=self._frame_source(src, src_ready))
+                                (geo.Hp // ms, geo.Wp // ms), n_frames=L, frame_source=self._frame_source(src, src_ready), ground_truth=gt)
 
     def forward_stream(self, batches):
         """An eval loop over videos: yields `forward(b)` for every b of the iterable `batches`, in order, bit-identical to
@@ -920,6 +938,7 @@ class MDQE(nn.Module):
             L, h, w = frames_dev.shape[0], int(frames_dev.shape[-2]), int(frames_dev.shape[-1])
             st = {"done_frames": False, "out_size": (video.get("height", h0), video.get("width", w0)), "hw": (h, w), "L": L,
                   "source": self._frame_source(src, src_ready)}
+            st["gt"] = self._ground_truth(video, st["out_size"], L)
             geo = self.engine.geometry(h, w)
             st["mask_hw"] = (geo.Hp // cfg.match_stride, geo.Wp // cfg.match_stride)
             clips = self.clip_schedule(L, cfg.n_frames_test, cfg.clip_stride)
@@ -964,7 +983,8 @@ class MDQE(nn.Module):
                 raise st["error"]
             if st["done_frames"]:
                 look_ahead(st)
-            out = self.merge_clips(st["gen"], st["hw"], st["out_size"], st["mask_hw"], n_frames=st["L"], frame_source=st["source"])
+            out = self.merge_clips(st["gen"], st["hw"], st["out_size"], st["mask_hw"], n_frames=st["L"], frame_source=st["source"],
+                                   ground_truth=st["gt"])
             if state["next"] is None:
                 look_ahead(st)                             # (the generator ends only after its callback; belt and braces)
             state["cur"], state["next"] = state["next"], None
@@ -974,7 +994,7 @@ class MDQE(nn.Module):
         while state["cur"] is not None:
             yield guarded(step)
 
-    def online_video(self, height=None, width=None, emit="masks", keep=False, geometry=False, style=None):
+    def online_video(self, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None):
         """An online session over ONE video whose frames arrive in pushes (a camera, a stream, a video too long to hold): push()
         returns each tracker window as soon as it is final, close() the rest, result() the video-level scores / labels / tracks.
         height / width: output mask size (default: the frame size); emit: "masks" (bool [n, F, H, W] per window), "rle" or "labels" (one
@@ -982,9 +1002,10 @@ class MDQE(nn.Module):
         over the frames pushed, one uint8 [F, H, W, 3] picture per window in `style`, a render.Style; `overlay_output`'s picture); keep:
         result() also carries forward()'s "pred_masks" / "pred_rles" / "pred_label_map" / "pred_overlay", bit-identical; geometry: every
         window carries `boxes` / `areas` of its final masks and result() "pred_boxes" / "pred_areas" (with or without keep), equal to
-        forward()'s with geometry_output.  See online.py."""
+        forward()'s with geometry_output; ground_truth (vis_score.GroundTruth): result() carries "pred_gt", forward()'s with the input's
+        "ground_truth" (a push past its length raises).  See online.py."""
         from .online import OnlineVideo
-        return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep, geometry=geometry, style=style)
+        return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep, geometry=geometry, style=style, ground_truth=ground_truth)
 
     def inference_image(self, batched_inputs):
         """COCO single-image branch: MDQE.forward :213-236 -> mdqe.forward (models/mdqe.py:62-70) -> decoder
@@ -996,6 +1017,8 @@ class MDQE(nn.Module):
         from .d2_compat import Boxes, Instances
         cfg, eng = self.cfg, self.engine
         item = batched_inputs[0]
+        if item.get("ground_truth") is not None:
+            raise ValueError("ground_truth: the COCO image branch is not scored (video IoU and the YTVIS table are for videos)")
         frames = self.to_device_frames(item["image"])
         T, h, w = int(frames.shape[0]), int(frames.shape[-2]), int(frames.shape[-1])
         geo = eng.geometry(h, w)
@@ -1053,10 +1076,10 @@ class MDQE(nn.Module):
 
     track_geometry = staticmethod(merge.track_geometry)
 
-    def inference_video(self, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True, frame_source=None):
+    def inference_video(self, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True, frame_source=None, score=None):
         """mdqe/mdqe.py:430-471: the video's result from its flushed windows (merge.video_result)."""
         return merge.video_result(self, image_size, cls_clips, windows, frame_hw, n_frames, early=early, emit_masks=emit_masks,
-                                  frame_source=frame_source)
+                                  frame_source=frame_source, score=score)
 
 
 class MDQE_MI355X(MDQE):

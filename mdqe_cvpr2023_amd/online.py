@@ -9,6 +9,9 @@
         ...
     res = ov.result()                      # {"image_size", "pred_scores", "pred_labels", "pred_track_ids"} (+ "pred_masks" / "pred_rles" if keep)
 
+ground_truth=gt (a vis_score.GroundTruth, to `online_video`): every window's final masks are also counted against it on the device and
+result() carries "pred_gt", equal to forward()'s with the input's "ground_truth"; a push past its length raises at that push.
+
 Same clips in the same order and the same window flushes as `MDQE.forward` on the whole video (mdqe/mdqe.py:308-366), so with
 keep=True the result equals forward()'s bit for bit.  A push runs every clip whose frames are all present (the schedule's last clip,
 `end > L`, can only run at close(), when L is known); each frame goes through the per-frame stages once -- a clip that straddles two
@@ -137,7 +140,7 @@ class Window:
 
 
 class OnlineVideo:
-    def __init__(self, model, height=None, width=None, emit="masks", keep=False, geometry=False, style=None):
+    def __init__(self, model, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None):
         if emit not in ("masks", "rle", "labels", "overlay"):
             raise ValueError("online_video: emit must be 'masks', 'rle', 'labels' or 'overlay'")
         if emit in ("labels", "overlay"):
@@ -146,6 +149,11 @@ class OnlineVideo:
         if style is not None and (emit != "overlay" or not isinstance(style, Style)):
             raise ValueError("online_video: style must be a render.Style and goes with emit='overlay'")
         self.style = (style if style is not None else Style()) if emit == "overlay" else None
+        if ground_truth is not None:
+            from .vis_score import GroundTruth
+            if not isinstance(ground_truth, GroundTruth):
+                raise ValueError("online_video: ground_truth must be a vis_score.GroundTruth, got %s" % type(ground_truth).__name__)
+        self.ground_truth = ground_truth          # the session's video is scored against it: result()["pred_gt"] (forward()'s)
         self.store = None                         # emit="overlay": the frames pushed and not yet painted (merge.FrameStore)
         if model.cfg.is_coco:
             raise RuntimeError("online_video: a COCO image config takes the single-image branch; online inference is for videos")
@@ -194,7 +202,7 @@ class OnlineVideo:
             from .merge import FrameStore
             self.store = FrameStore()
         self.merger = ClipMerger(model, self.hw, self.out_size, self.mask_hw, n_frames=None, online=self.emit,
-                                 geometry=self.geometry, frame_source=self.store, style=self.style)
+                                 geometry=self.geometry, frame_source=self.store, style=self.style, ground_truth=self.ground_truth)
         shapes = model.engine.cache_shapes(self.geo)
         per_frame = 4 * sum(int(np.prod(sh)) for sh in shapes.values())
         forced = int(os.environ.get("MDQE_CACHE_FRAMES", "0"))
@@ -251,6 +259,9 @@ class OnlineVideo:
         n = int(frames.shape[0]) if torch.is_tensor(frames) else len(frames)
         if n == 0:
             return []
+        if self.ground_truth is not None and self.received + n > self.ground_truth.length:
+            raise RuntimeError("online_video: this push brings the video to %d frames, the ground truth holds %d"
+                               % (self.received + n, self.ground_truth.length))
         hw0 = self._hw(frames)
         if self.in_hw is not None and hw0 != self.in_hw:
             raise RuntimeError("online_video: frame size %s differs from the first push's %s" % (hw0, self.in_hw))
@@ -305,6 +316,9 @@ class OnlineVideo:
         sc, labels, inst = self.model.select_tracks(self.merger.cls_clips)
         Ho, Wo = self.out_size
         res = {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels, "pred_track_ids": list(inst)}
+        if self.merger.score is not None:
+            with self._ctx():
+                res["pred_gt"] = self.merger.score.result(list(inst), self.received, self.model._copy_stream)
         if self.geometry:
             geo = self.model.track_geometry(list(inst), self.received, (Ho, Wo), self.geoms)
             if self.emit in ("labels", "overlay"):                 # (the windows' tables describe the labels' visible regions, not the full masks)

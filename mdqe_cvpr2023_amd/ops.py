@@ -600,6 +600,41 @@ def final_label_map(logits, inst_idx, factor, h, w, Ho, Wo, out, f_off, geom=Non
     return out, geom
 
 
+def final_masks_overlap(logits, inst_idx, factor, h, w, Ho, Wo, gt_bits, G, f_off, inter, area=None):
+    """A window's final masks scored against ground truth on the device (vis_score.py): for the rows `inst_idx` (int32 CUDA [n_sel]) of
+    logits [n, Fw, Hm, Wm], with b_k the final-mask bit of row k (ops.final_masks' own bit), inter[k, g] (int64 CUDA [>= n_sel, >= G],
+    rows inter.stride(0) apart) is INCREASED by the number of window pixels where b_k and bit g of gt_bits[f_off + f] (uint32 CUDA
+    [>= f_off + Fw, Ho, Wo], contiguous; G <= 32 ground-truth tracks, one bit each) are both set -- zero it once per video, the windows
+    add up -- and area (int32 CUDA [n_sel * Fw], allocated when None) is OVERWRITTEN with the set pixels of (row k, frame f), column 0
+    of ops.final_masks_geom's table.  Integers only: exact, identical from run to run.  -> (inter, area)."""
+    # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
+    if not torch.is_tensor(logits) or logits.dim() != 4:
+        raise RuntimeError("final_masks_overlap: logits must be [n, Fw, Hm, Wm], got %s" % (tuple(getattr(logits, "shape", ())),))
+    if not torch.is_tensor(inst_idx) or inst_idx.dtype != torch.int32 or inst_idx.dim() != 1:
+        raise RuntimeError("final_masks_overlap: inst_idx must be int32 [n_sel]")
+    k, Fw = int(inst_idx.numel()), int(logits.shape[1])
+    if (not torch.is_tensor(gt_bits) or gt_bits.dtype != torch.uint32 or gt_bits.dim() != 3 or tuple(gt_bits.shape[1:]) != (Ho, Wo)
+            or not gt_bits.is_contiguous()):
+        raise RuntimeError("final_masks_overlap: gt_bits must be contiguous uint32 [frames, Ho = %d, Wo = %d]" % (Ho, Wo))
+    if f_off < 0 or f_off + Fw > gt_bits.shape[0]:
+        raise RuntimeError("final_masks_overlap: gt_bits holds %d frames, the window needs f_off + Fw = %d" % (gt_bits.shape[0], f_off + Fw))
+    if (not torch.is_tensor(inter) or inter.dtype != torch.int64 or inter.dim() != 2 or inter.shape[0] < k or inter.shape[1] < G
+            or inter.stride(1) != 1 or (inter.shape[0] > 1 and inter.stride(0) < G)):
+        raise RuntimeError("final_masks_overlap: inter must be int64 [>= n_sel = %d, >= G = %d] with unit column stride" % (k, G))
+    if area is not None and (not torch.is_tensor(area) or area.dtype != torch.int32 or area.numel() != k * Fw or not area.is_contiguous()):
+        raise RuntimeError("final_masks_overlap: area must be contiguous int32 [n_sel * Fw = %d]" % (k * Fw))
+    for name, t in (("gt_bits", gt_bits), ("inter", inter), ("area", area)):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("final_masks_overlap: %s must be a CUDA tensor" % name)
+    k, Fw, Hm, Wm = _final_mask_args(logits, inst_idx, True)
+    if area is None:
+        area = torch.empty(k * Fw, dtype=torch.int32, device=logits.device)
+    check(lib.mdqe_final_masks_overlap(ptr(logits), k, ptr(inst_idx), Fw, Hm, Wm, factor, h, w, Ho, Wo, ptr(gt_bits), G, f_off,
+                                       ptr(inter), inter.stride(0) if inter.shape[0] > 1 else max(int(inter.shape[1]), G), ptr(area),
+                                       cur_stream()), "final_masks_overlap")
+    return inter, area
+
+
 def render_overlay(labels, frames, palette, out, f_off=0, a256=128, contour=1):
     """The picture of a label map: out[f_off + f] (uint8 [>= f_off + F, Ho, Wo, 3], CUDA, contiguous, pixel-interleaved) painted from
     labels (uint8 [F, Ho, Wo], ops.final_label_map's output), frames ([F, 3, h0, w0] uint8 or float32, each frame contiguous, the frames

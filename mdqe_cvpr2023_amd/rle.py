@@ -211,6 +211,18 @@ def encode_dense(mask):
     return {"size": [int(m.shape[0]), int(m.shape[1])], "counts": counts_to_strings(counts, lengths)[0].decode("utf-8")}
 
 
+def decode_dense(rle):
+    """Inverse of `encode_dense` (pycocotools `decode`): {"size": [H, W], "counts": str / bytes or a list of run lengths (the
+    uncompressed form)} -> uint8 [H, W]; runs alternate 0, 1, ... in column-major order."""
+    H, W = int(rle["size"][0]), int(rle["size"][1])
+    c = rle["counts"]
+    counts = strings_to_counts([c])[0] if isinstance(c, (str, bytes)) else np.asarray(c, dtype=np.int64)
+    if int(counts.sum()) != H * W or (counts < 0).any():
+        raise ValueError("decode_dense: the runs cover %d pixels, the mask has %d" % (int(counts.sum()), H * W))
+    v = np.repeat((np.arange(counts.shape[0]) % 2).astype(np.uint8), counts)
+    return v.reshape((H, W), order="F")
+
+
 # ---- label maps (model.label_output / online emit="labels"): uint8 [L, H, W], label t + 1 = track t, 0 = background ----------------------
 def labels_to_masks(label_map, track_ids):
     """The exclusive region of each track of `track_ids` as a bool plane -> [len(track_ids), L, H, W] (tensor in, tensor out; else numpy)."""

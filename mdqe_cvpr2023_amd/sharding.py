@@ -413,16 +413,17 @@ def owned_chunks(plan, world, rank):
 
 
 def run_round_robin(model, chunk_frames, plan, rank, world, dist, out_size, emit_masks=True, root_only=False, halo_exchange=False, like=None,
-                    stats=None, vworld=None, as_rank=0, rest_until_ms=0.0):
+                    stats=None, vworld=None, as_rank=0, rest_until_ms=0.0, ground_truth=None):
     """chunk_frames: {g: device tensor of frames plan[g].f0 .. plan[g].f1} for the chunks this rank owns.
     Default: every rank all-gathers each round and replays the tracker (all ranks return the video result;
     emit_masks=False skips the mask production on ranks that only keep the tracker in step).
     root_only=True (bench.py): the rounds are gathered to rank 0 only, which replays the tracker on a worker thread while
     its main thread goes on with the next round; the other ranks only compute and send, and return None.
-    `like`: any [.., h, w] tensor on the frames' device -- needed by a rank that owns NO chunk of this video (more ranks than chunks)."""
+    `like`: any [.., h, w] tensor on the frames' device -- needed by a rank that owns NO chunk of this video (more ranks than chunks).
+    ground_truth: refused with a ValueError (the sharded driver does not score a video; see `_Job`)."""
     return next(run_round_robin_stream(model, [(chunk_frames, plan, like) if like is not None else (chunk_frames, plan)], rank, world, dist, out_size,
                                        emit_masks=emit_masks, root_only=root_only, halo_exchange=halo_exchange, stats=stats, vworld=vworld,
-                                       as_rank=as_rank, rest_until_ms=rest_until_ms))
+                                       as_rank=as_rank, rest_until_ms=rest_until_ms, ground_truth=ground_truth))
 
 
 _HALO_GROUPS = {}
@@ -533,7 +534,7 @@ class _Job:
     """One video of the round-robin schedule on this rank: its chunks, its merger and (root-only form) its replay thread."""
 
     def __init__(self, model, chunk_frames, plan, rank, world, out_size, emit_masks, root_only, like=None, dist=None,
-                 halo_exchange=False, local_halo=False):
+                 halo_exchange=False, local_halo=False, ground_truth=None):
         from .meta_arch import ClipMerger
         cfg = model.cfg
         self.model, self.chunk_frames, self.plan, self.rank, self.world = model, chunk_frames, plan, rank, world
@@ -558,6 +559,9 @@ class _Job:
         if getattr(model, "overlay_output", False):
             raise ValueError("overlay_output is not offered by the sharded driver: rank 0 does not hold every frame of the video (paint "
                              "from pred_label_map on the host, or run the video on one device)")
+        if ground_truth is not None:
+            raise ValueError("ground_truth is not offered by the sharded driver: the overlap counts would have to follow the tracker replay on "
+                             "rank 0 with the whole video's ground truth there (score the video on one device: model([{..., 'ground_truth': gt}]))")
         if not root_only or rank == 0:
             self.merger = ClipMerger(model, (h, w), out_size, mask_hw, n_frames=max(c[2] for c in plan), emit_masks=emit_masks)
             if getattr(model, "merge_on_cpu", None) is None and hasattr(self.merger, "merge_on_cpu"):
@@ -662,7 +666,7 @@ def halo_recompute_frac(plan, L):
 
 
 def run_round_robin_stream(model, jobs, rank, world, dist, out_size, emit_masks=True, root_only=False, halo_exchange=False, stats=None,
-                           vworld=None, as_rank=0, rest_until_ms=0.0):
+                           vworld=None, as_rank=0, rest_until_ms=0.0, ground_truth=None):
     """Videos as a stream through the round-robin schedule.  jobs: iterable of (chunk_frames, plan[, like]) as for
     run_round_robin (`like`: any [.., h, w] tensor on the device, for a rank that owns no chunk of a short video); yields each video's result in order (None on the ranks that do not replay).  Within a video the next round's per-frame
     work is queued before this round's clip work; ACROSS videos the first round of video k+1 is queued before the last round's
@@ -695,7 +699,7 @@ def run_round_robin_stream(model, jobs, rank, world, dist, out_size, emit_masks=
         j = next(it, None)
         return None if j is None else _Job(model, j[0], j[1], prank, pworld, out_size, emit_masks, root_only,
                                            like=j[2] if len(j) > 2 else None, dist=dist, halo_exchange=halo_exchange,
-                                           local_halo=halo_exchange and vworld is not None)
+                                           local_halo=halo_exchange and vworld is not None, ground_truth=ground_truth)
 
     def finish(j):
         t0 = time.perf_counter()
