@@ -237,6 +237,43 @@ int mdqe_resize_pil_bilinear_u8(const unsigned char* in, long in_img_stride, int
                                 const int* xmin, const int* xcnt, const int* xk, int kxs, const int* ymin, const int* ycnt,
                                 const int* yk, int kys, unsigned char* out, void* stream);
 
+/* ---- decoder surfaces as video input: semi-planar YUV 4:2:0 (NV12, P010) -> planar uint8 RGB, the tensor the entry above and the stem
+ * take (csrc/yuv.hip).  What a hardware decoder or a capture device hands out: a luma plane of H rows and a chroma plane of ceil(H/2)
+ * rows of interleaved U, V pairs, ceil(W/2) pairs per row; rows y_pitch / uv_pitch BYTES apart, surfaces y_stride / uv_stride BYTES
+ * apart, the two planes independent of each other (views into one decoder allocation: chroma at pitch * aligned_height).  Any H >= 1,
+ * W >= 1.  ONE definition, integers only:
+ *   samples   Y = luma[r][c], U = chroma[r >> 1][2 * (c >> 1)], V = chroma[r >> 1][2 * (c >> 1) + 1]: chroma is replicated (nearest),
+ *             what libyuv's and most decoders' default NV12 conversion does;
+ *   fmt 0     NV12: samples are bytes;
+ *   fmt 1     P010: samples are little-endian 16-bit words, the value is word >> 6 (10 bits, 0..1023; the low 6 bits are ignored);
+ *   rule      y = (Y - yo) * cy, u = U - co, v = V - co in int32, >> the arithmetic shift (floor):
+ *               R = clamp((y          + rv * v + 32768) >> 16, 0, 255)
+ *               G = clamp((y + gu * u + gv * v + 32768) >> 16, 0, 255)
+ *               B = clamp((y + bu * u          + 32768) >> 16, 0, 255)
+ *   constants rint(x * 65536) of the standard matrices: luma gain 255/219 (limited, 8 bit), 255/876 (limited, 10 bit), 1 (full, 8 bit)
+ *             or 255/1023 (full, 10 bit); chroma gains 2(1-Kr), -2Kb(1-Kb)/Kg, -2Kr(1-Kr)/Kg, 2(1-Kb) times 255/224, 255/896, 1 or
+ *             255/1023; Kr, Kb = 0.299, 0.114 (BT.601) or 0.2126, 0.0722 (BT.709), Kg = 1 - Kr - Kb.  MDQE_YUV_COEFFS below holds them,
+ *             row = 4 * fmt + 2 * matrix + full_range, columns yo, co, cy, rv, gu, gv, bu.  |accumulator| < 3.7e7: int32 is safe.  Every
+ *             output lies within 1 level of clamp(rint(the float64 matrix)).
+ * out: [NI, 3, H, W] uint8, contiguous, planes R, G, B (bgr != 0: B, G, R).  MDQE_EINVAL, before any pointer is looked at, for H or W
+ * <= 0, NI < 0, fmt / matrix outside {0, 1}, a pitch smaller than a row (W samples of luma, 2 * ceil(W/2) of chroma), a negative
+ * stride, odd P010 pitches or strides, and NI * 3 * H * W >= 2^31; NI == 0 returns OK and launches nothing; odd P010 plane pointers are
+ * MDQE_EINVAL.  Nothing else needs to be aligned: where every plane pointer, pitch, stride and W are multiples of 16 (or of 4) bytes
+ * the launch moves 16 (4) bytes per access, otherwise single samples.  Reads stay inside W samples of a luma row, 2 * ceil(W/2) of a
+ * chroma row, H luma rows and ceil(H/2) chroma rows: padding is never touched.  Never allocates, never synchronises. */
+#define MDQE_YUV_COEFFS { \
+  {16, 128, 76309, 104597, -25675, -53279, 132201}, /* nv12 bt601 limited */ \
+  {0, 128, 65536, 91881, -22553, -46802, 116130},   /* nv12 bt601 full    */ \
+  {16, 128, 76309, 117489, -13975, -34925, 138438}, /* nv12 bt709 limited */ \
+  {0, 128, 65536, 103206, -12276, -30679, 121609},  /* nv12 bt709 full    */ \
+  {64, 512, 19077, 26149, -6419, -13320, 33050},    /* p010 bt601 limited */ \
+  {0, 512, 16336, 22903, -5622, -11666, 28947},     /* p010 bt601 full    */ \
+  {64, 512, 19077, 29372, -3494, -8731, 34610},     /* p010 bt709 limited */ \
+  {0, 512, 16336, 25726, -3060, -7647, 30313}       /* p010 bt709 full    */ }
+int mdqe_yuv420sp_to_rgb_u8(const void* y, long y_pitch, long y_stride, const void* uv, long uv_pitch, long uv_stride,
+                            int NI, int H, int W, int fmt /*0 nv12, 1 p010*/, int matrix /*0 bt601, 1 bt709*/, int full_range,
+                            int bgr, unsigned char* out /* [NI, 3, H, W] contiguous */, void* stream);
+
 /* ---- LayerNorm over the last dim: y = LN(x + res) * gamma + beta (res may be NULL) -----------------
  * nn.LayerNorm call sites transformer_enc.py:103-108,136; transformer_dec.py:345-358,394-408,466,492. */
 int mdqe_layernorm_f32(const float* x, const float* res, const float* gamma, const float* beta, float* y,

@@ -855,6 +855,28 @@ class MDQE(nn.Module):
                 events.append((b, ev))
         return dev, events
 
+    def convert_surfaces(self, yuv):
+        """Decoder surfaces (preprocess.YuvFrames) -> uint8 [n, 3, height, width] on the model's device, visible to the current stream.
+        Host planes go up as they are -- the rows the picture uses at their pitch: for NV12 at a tight pitch half an RGB upload -- on the copy
+        stream; the current stream waits for them and converts (preprocess.yuv_to_rgb: one launch)."""
+        from .preprocess import yuv_to_rgb
+        if len(yuv) == 0:
+            raise RuntimeError("MDQE: a video needs at least one frame")
+        if self.device.type != "cuda":
+            return yuv_to_rgb(yuv).to(self.device)
+        if not yuv.y.is_cuda:
+            if self._copy_stream is None:
+                self._copy_stream = torch.cuda.Stream(self.device)
+            cs, cur = self._copy_stream, torch.cuda.current_stream(self.device)
+            with torch.cuda.stream(cs):
+                yuv = yuv.to(self.device, non_blocking=True)
+            for t in (yuv.y, yuv.uv):                              # allocated under the copy stream, read by the kernel on this one
+                t.record_stream(cur)
+            cur.wait_stream(cs)
+        elif yuv.device != self.device:
+            yuv = yuv.to(self.device)
+        return yuv_to_rgb(yuv)
+
     def to_device_frames(self, imgs):
         """All frames on the device, visible to the current stream."""
         dev, events = self.upload_frames(imgs)
@@ -870,8 +892,14 @@ class MDQE(nn.Module):
     def _frames_and_source(self, video):
         """`_frames_for` and, behind it, the frames as uploaded -- before the device-side resize, what an overlay is painted on -- with
         the event behind their upload (None: nothing was in flight) and whether an upload made them (else they may be the caller's tensor)."""
-        frames_dev, h2d = self.upload_frames(video["image"])
-        src, src_ready, uploaded = frames_dev, (h2d[-1][1] if h2d else None), bool(h2d)
+        from .preprocess import YuvFrames
+        if isinstance(video["image"], YuvFrames):
+            # decoder surfaces: from here the converted tensor is what an uploaded uint8 RGB tensor would have been (and the model's own)
+            frames_dev, h2d = self.convert_surfaces(video["image"]), None
+            src, src_ready, uploaded = frames_dev, None, True
+        else:
+            frames_dev, h2d = self.upload_frames(video["image"])
+            src, src_ready, uploaded = frames_dev, (h2d[-1][1] if h2d else None), bool(h2d)
         h0, w0 = int(frames_dev.shape[-2]), int(frames_dev.shape[-1])
         if self.resize_on_device and frames_dev.dtype == torch.uint8:
             from .preprocess import resize_shortest_edge
@@ -1019,6 +1047,10 @@ class MDQE(nn.Module):
         item = batched_inputs[0]
         if item.get("ground_truth") is not None:
             raise ValueError("ground_truth: the COCO image branch is not scored (video IoU and the YTVIS table are for videos)")
+        from .preprocess import YuvFrames
+        if isinstance(item["image"], YuvFrames):
+            raise ValueError("YuvFrames: the COCO image branch takes RGB tensors (decoder surfaces are a video input; convert one with "
+                             "preprocess.yuv_to_rgb)")
         frames = self.to_device_frames(item["image"])
         T, h, w = int(frames.shape[0]), int(frames.shape[-2]), int(frames.shape[-1])
         geo = eng.geometry(h, w)

@@ -1,7 +1,8 @@
 """Online video inference: frames arrive in pushes of any size, tracker windows come back as soon as they are final.
 
     ov = model.online_video(height=H, width=W, emit="masks", keep=False, geometry=False)
-    for chunk in source:                   # [n, 3, h, w] uint8 / float32, host or device, n >= 1 (n == 0: no-op)
+    for chunk in source:                   # [n, 3, h, w] uint8 / float32, host or device, n >= 1 (n == 0: no-op),
+                                           # or n NV12 / P010 decoder surfaces: preprocess.YuvFrames (converted on the device)
         for win in ov.push(chunk):         # the windows this push completed, in order
             win.frames, win.track_ids, win.cls_probs, win.masks   # (or win.rles with emit="rle", win.labels with emit="labels")
             win.boxes, win.areas           # geometry=True: XYXY_ABS float32 [n, F, 4] and pixel counts int64 [n, F] of those masks
@@ -187,6 +188,9 @@ class OnlineVideo:
 
     @staticmethod
     def _hw(frames):
+        from .preprocess import YuvFrames
+        if isinstance(frames, YuvFrames):
+            return frames.height, frames.width
         f = frames if torch.is_tensor(frames) else frames[0]
         return int(f.shape[-2]), int(f.shape[-1])
 
@@ -252,8 +256,9 @@ class OnlineVideo:
         return out
 
     def push(self, frames):
-        """Frames [n, 3, h, w] (uint8 or float32, host or device) of the video, in order.  Runs every clip whose frames are all
-        present now and returns the windows that completed, in order."""
+        """Frames [n, 3, h, w] (uint8 or float32, host or device) of the video, in order, or n decoder surfaces (a
+        preprocess.YuvFrames, host or device: converted on the device, the picture of an overlay is painted on the converted frames in
+        their `order`).  Runs every clip whose frames are all present now and returns the windows that completed, in order."""
         if self.closed:
             raise RuntimeError("online_video: push() after close()")
         n = int(frames.shape[0]) if torch.is_tensor(frames) else len(frames)

@@ -539,6 +539,10 @@ class _Job:
         cfg = model.cfg
         self.model, self.chunk_frames, self.plan, self.rank, self.world = model, chunk_frames, plan, rank, world
         self.T = cfg.n_frames_test
+        from .preprocess import YuvFrames
+        if any(isinstance(f, YuvFrames) for f in list(chunk_frames.values()) + [like]):
+            raise ValueError("YuvFrames is not offered by the sharded driver: its chunks are cut from RGB tensors (convert the surfaces "
+                             "with preprocess.yuv_to_rgb first, or run the video on one device)")
         any_fr = next(iter(chunk_frames.values()), like)
         if any_fr is None:
             raise ValueError("a rank that owns no chunk of a video must pass `like` (any [.., h, w] tensor on the frames' device)")
