@@ -1,5 +1,5 @@
-// One output pixel of the final mask (mdqe/mdqe.py:357-358 + 458-462; the formula is stated above the entry points in decoder_ops.hip),
-// shared by every form built on it -- dense, RLE, geometry, label map (decoder_ops.hip) and the overlap counts (score_ops.hip): identical
+// One output pixel of the final mask (mdqe/mdqe.py:357-358 + 458-462; the formula is stated above the entry points in final_mask.hip),
+// shared by every form built on it -- dense, RLE, geometry, label map (final_mask.hip) and the overlap counts (score_ops.hip): identical
 // arithmetic, identical bits.  Three steps: where the pixel reads (the same for every map of a window), the up-sampled logit there, and
 // the threshold on it.
 #pragma once
@@ -35,4 +35,25 @@ __device__ __forceinline__ int final_mask_bit(float v) {
 __device__ __forceinline__ int final_mask_pixel(const float* __restrict__ m, int Hm, int Wm, int factor, int h, int w, float sy_scale,
                                                 float sx_scale, int Y, int X) {
   return final_mask_bit(final_mask_value(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, Y, X));
+}
+
+// ---- host only: what the six entry points of the family share (final_mask.hip, score_ops.hip) ------------------------------------------
+#define MDQE_TRY(e) do { const int rc_ = (e); if (rc_ != MDQE_OK) return rc_; } while (0)
+
+// The arguments every entry point leads with; each keeps the conditions that are its own, its MDQE_OK for nothing to do, its pointers.
+static inline int final_mask_args(int n_sel, int Fw, int Hm, int Wm, int factor, int h, int w, int Ho, int Wo) {
+  MDQE_REQUIRE(n_sel >= 0 && Fw >= 0 && Hm > 0 && Wm > 0 && factor >= 1 && h > 0 && w > 0 && Ho > 0 && Wo > 0);
+  MDQE_REQUIRE(h <= Hm * factor && w <= Wm * factor);
+  return MDQE_OK;
+}
+
+// Output rows a block takes when `units` masks or frames share about `blocks` blocks of 256 threads (4096: ~16 per CU; 2048: ~8), at
+// least ~1024 pixels (4 per thread) a block so that reduction and atomics stay a small part of its work.  n_bands = ceil(Ho / band).
+static inline int final_mask_band(long blocks, long units, int Ho, int Wo) {
+  long want = (blocks + units - 1) / units;
+  const long most = ((long)Ho * Wo + 1023) / 1024;
+  if (want > most) want = most;
+  if (want > Ho) want = Ho;
+  if (want < 1) want = 1;
+  return (int)((Ho + want - 1) / want);
 }

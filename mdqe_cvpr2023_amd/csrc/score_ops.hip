@@ -74,19 +74,14 @@ final_mask_overlap_kernel(const float* __restrict__ lg, int n_sel, int Fw, int H
 extern "C" int mdqe_final_masks_overlap(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
                                         int h, int w, int Ho, int Wo, const uint32_t* gt_bits, int G, int f_off,
                                         unsigned long long* inter, long inter_row_stride, int* area, void* stream) {
-  MDQE_REQUIRE(n_sel >= 0 && Fw >= 0 && Hm > 0 && Wm > 0 && factor >= 1 && h > 0 && w > 0 && Ho > 0 && Wo > 0 && f_off >= 0);
-  MDQE_REQUIRE(h <= Hm * factor && w <= Wm * factor && (long)Ho * Wo < 0x7FFFFFFFL && (long)Hm * Wm < 0x7FFFFFFFL);
+  MDQE_TRY(final_mask_args(n_sel, Fw, Hm, Wm, factor, h, w, Ho, Wo));
+  MDQE_REQUIRE(f_off >= 0 && (long)Ho * Wo < 0x7FFFFFFFL && (long)Hm * Wm < 0x7FFFFFFFL);
   MDQE_REQUIRE(G >= 1 && G <= 32 && inter_row_stride >= G && (long)n_sel * Fw < 0x7FFFFFFFL);
   if (n_sel == 0 || Fw == 0) return MDQE_OK;
   MDQE_CHECK_PTR(logits); MDQE_CHECK_PTR(inst_idx_dev); MDQE_CHECK_PTR(gt_bits); MDQE_CHECK_PTR(inter); MDQE_CHECK_PTR(area);
-  // bands per frame as in mdqe_final_label_map_u8: about 8 blocks of 256 threads per CU over the window, at least ~1024 pixels a block
+  // bands per frame as in mdqe_final_label_map_u8
   const int chunks = (n_sel + OVERLAP_ROWS - 1) / OVERLAP_ROWS;
-  long want = (2048 + (long)Fw * chunks - 1) / ((long)Fw * chunks);
-  const long most = ((long)Ho * Wo + 1023) / 1024;
-  if (want > most) want = most;
-  if (want > Ho) want = Ho;
-  if (want < 1) want = 1;
-  const int band = (int)((Ho + want - 1) / want);
+  const int band = final_mask_band(2048, (long)Fw * chunks, Ho, Wo);
   const int n_bands = (Ho + band - 1) / band;
   MDQE_REQUIRE((long)Fw * n_bands < 0x7FFFFFFFL && chunks <= 65535);
   const int kc = n_sel < OVERLAP_ROWS ? n_sel : OVERLAP_ROWS;

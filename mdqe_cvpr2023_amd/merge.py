@@ -1,11 +1,12 @@
 """The second half of the clip loop (mdqe/mdqe.py:337-366, 430-471): `ClipMerger` (tracker update per clip, window flushes) and
-`video_result` (the video's result from the flushed windows); `meta_arch.MDQE` keeps its entry points as delegates.  A flushed window
-becomes final masks per window into pinned memory (`_early_masks`), per window as a record (`_online_window`, online.OnlineVideo) or all
-windows in one pass at the end (`video_result`).  What the three share is written once: `dense_masks` / `rle_positions` (window logits
--> masks / run boundaries, with or without geometry), `to_host` (the hop on the copy stream), `rle.positions_to_rles`, `stitch`.
-`label_maps` is the third output form (model.label_output, online "labels"): one uint8 plane per frame that names the track owning each
-pixel, from the same three places; its frames are disjoint between windows, so it needs no `stitch`.  `overlay_frames` is the fourth
-(model.overlay_output, online "overlay"): that map painted over the frames the caller handed in (`FrameStore`), uint8 [F, Ho, Wo, 3].
+`video_result` (the video's result from the flushed windows); `meta_arch.MDQE` keeps its entry points as delegates.
+Which forms a video produces is resolved ONCE, into a `Forms` record (from the model's flags offline, from `emit` online): per-track
+planes (dense or run boundaries), the label map (one uint8 plane per frame that names the track owning each pixel; its frames are
+disjoint between windows, so it needs no `stitch`), its overlay (that map painted over the frames the caller handed in, `FrameStore`,
+uint8 [F, Ho, Wo, 3]) and whose geometry.  A flushed window becomes those forms in ONE function, `build_window`; the three paths differ
+in the destination only: per window into per-video pinned memory (`_early_masks`), per window as a record (`_online_window`), or all
+windows into whole-video device buffers with one copy at the end (`video_result`).  Shared beside it: `to_host` (the hop on the copy
+stream), `rle.positions_to_rles`, `stitch`, `result_head` / `track_geometry` (a result's keys).
 `OverlapTables` is not an output form but a score: with a ground truth handed in (vis_score.GroundTruth), every flushed window's final
 masks are counted against it where they are decided (ops.final_masks_overlap) -- "pred_gt", beside whatever form the masks take."""
 import contextlib
@@ -16,6 +17,37 @@ import torch
 
 from . import rle as R
 from .tracking import Clips, OverTracker
+
+
+@dataclasses.dataclass(frozen=True)
+class Forms:
+    """Which output forms a video produces, resolved ONCE and read by every path; the only reader of the model's output flags here."""
+    planes: object = None                 # "dense" | "rle" | None: the per-track planes
+    labels: bool = False                  # the label map is RETURNED (an overlay without it keeps the map as a device scratch)
+    overlay: bool = False                 # the label map painted over the frames
+    plane_geometry: bool = False          # boxes and areas of the planes ...
+    label_geometry: bool = False          # ... and of the labels' visible regions
+    early_always: bool = False            # model.rle_output: the early path even with model.early_masks off, with or without planes
+
+    @classmethod
+    def _of(cls, model, geometry, planes, labels, overlay, early_always=False):
+        """geometry None: the model's flag.  It describes the planes where there are planes, and the labels' regions where the map is returned."""
+        g = bool(getattr(model, "geometry_output", False) if geometry is None else geometry)
+        return cls(planes, labels, overlay, g and planes is not None, g and labels, early_always)
+
+    @classmethod
+    def of_model(cls, model, emit_masks=True, geometry=None):
+        """Offline.  emit_masks=False (ranks > 0 of a sharded video): nothing.  Stand-in models may lack the newer flags."""
+        if not emit_masks:
+            return cls()
+        lab, rle = getattr(model, "label_output", False), bool(getattr(model, "rle_output", False))
+        return cls._of(model, geometry, None if lab == "only" else "rle" if rle else "dense", bool(lab), bool(getattr(model, "overlay_output", False)), rle)
+
+    @classmethod
+    def of_emit(cls, emit, geometry=False, model=None):
+        """Online ("masks" | "rle" | "labels" | "overlay")."""
+        lab = emit in ("labels", "overlay")
+        return cls._of(model, geometry, None if lab else {"masks": "dense", "rle": "rle"}[emit], lab, emit == "overlay")
 
 
 def dense_masks(m, idx, stride, frame_hw, out_size, geometry, out, f_off):
@@ -200,6 +232,30 @@ def rle_positions(m, idx, stride, frame_hw, out_size, geometry):
     return pos[:, :max(mx, 1)].cpu().numpy(), n_pos.cpu().numpy(), geom.view(int(idx.numel()), int(m.shape[1]), 5).cpu() if geometry else None
 
 
+def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels=None, picture=None, paint=None,
+                 hop=lambda stage, geom: geom):
+    """What `forms` asks for of ONE flushed window (logits m [n, F, Hm, Wm]), on the current stream, for every path; the only caller
+    of `overlay_frames`, `label_maps`, `dense_masks` and `rle_positions`.  First the label map of ALL n rows into labels = (device
+    buffer, frame offset) and, with picture = (buffer, offset), its overlay, painted from paint = (FrameStore, first video frame,
+    render.Style).  Then the planes of `rows` (int32 device; None or empty: none): dense into planes = (buffer, offset) when given,
+    else, with forms.planes == "rle", their run boundaries on the host.  `hop(stage, geom) -> geom` runs behind each stage ("labels" |
+    "planes") that filled device buffers: the early and the online path send them to the host there, the map under the planes' kernel.
+    -> (labels' geometry table [n, F, 5] or None, planes' table [len(rows), F, 5] or None, (pos, n_pos) of `rle_positions` or None)."""
+    lgeom = pgeom = runs = None
+    if labels is not None:
+        if picture is not None:
+            lgeom = overlay_frames(m, stride, frame_hw, out_size, forms.label_geometry, *labels, *paint, *picture)
+        else:
+            lgeom = label_maps(m, stride, frame_hw, out_size, forms.label_geometry, *labels)
+        lgeom = hop("labels", lgeom)
+    if rows is not None and int(rows.numel()):
+        if planes is not None:
+            pgeom = hop("planes", dense_masks(m, rows, stride, frame_hw, out_size, forms.plane_geometry, *planes))
+        elif forms.planes == "rle":
+            *runs, pgeom = rle_positions(m, rows, stride, frame_hw, out_size, forms.plane_geometry)
+    return lgeom, pgeom, runs
+
+
 def copy_stream(model):
     """The model's copy stream, created at the first call (the order streams are first used in decides their queues: `MDQE._make_streams`)."""
     if model._copy_stream is None:
@@ -207,16 +263,18 @@ def copy_stream(model):
     return model._copy_stream
 
 
-def to_host(cs, side, masks, copies, geom, event):
-    """A window's dense masks (device, produced on stream `side`) to pinned host memory on the copy stream `cs`: `copies` = (pinned
-    destination, part of `masks`) pairs.  The geometry table (or None) rides on the same stream; `event` is recorded behind both.
-    -> the table in pinned memory (valid once `event` has fired), or None."""
+def to_host(cs, side, copies, geom, event):
+    """A window's device buffers (produced on stream `side`) to pinned host memory on the copy stream `cs`: `copies` = (pinned
+    destination, device source) pairs; every source is `record_stream`ed there (sources that are views of one buffer: once).  The
+    geometry table (or None) rides on the same stream; `event` is recorded behind both.  -> the table in pinned memory (valid once
+    `event` has fired), or None."""
     hgeom = None if geom is None else torch.empty(geom.shape, dtype=torch.int32, pin_memory=True)
     cs.wait_stream(side)
     with torch.cuda.stream(cs):
         for dst, src in copies:
             dst.copy_(src, non_blocking=True)
-        masks.record_stream(cs)
+        for src in {src.untyped_storage().data_ptr(): src for _, src in copies}.values():
+            src.record_stream(cs)
         if geom is not None:
             hgeom.copy_(geom, non_blocking=True)
             geom.record_stream(cs)
@@ -248,14 +306,16 @@ def stitch_rles(rows, n_frames, out_size, windows):
     return stitch(rows, n_frames, windows, lambda k: [R.empty_rle(out_size) for _ in range(k)], lambda parts: sum(parts, []))
 
 
-def track_geometry(rows, n_frames, out_size, windows):
+def track_geometry(rows, n_frames, out_size, windows, labels=False):
     """Per output j the [n_frames] geometry of row rows[j] from the windows' geom tables: `windows` = (f_off, nf, n rows this window
-    holds, geom int32 [n, nf, 5] on the host).  -> {"pred_boxes": [float32 [n_frames, 4]], "pred_areas": [int64 [n_frames]]}."""
+    holds, geom int32 [n, nf, 5] on the host).  -> {"pred_boxes": [float32 [n_frames, 4]], "pred_areas": [int64 [n_frames]]}; labels:
+    the tables are those of the labels' visible regions, the keys "pred_label_boxes" / "pred_label_areas"."""
     Ho, Wo = int(out_size[0]), int(out_size[1])
     none = torch.tensor([[0, Wo, Ho, -1, -1]], dtype=torch.int32)
     wins = [(f, nf, n, torch.as_tensor(g)) for f, nf, n, g in windows]
     geo = [R.geom_to_boxes(t) for t in stitch(rows, int(n_frames), wins, lambda k: none.repeat(k, 1), torch.cat)]   # (fresh tensors per output)
-    return {"pred_boxes": [b for b, _ in geo], "pred_areas": [a for _, a in geo]}
+    pre = "pred_label_" if labels else "pred_"
+    return {pre + "boxes": [b for b, _ in geo], pre + "areas": [a for _, a in geo]}
 
 
 def select_tracks(cls_clips, num_classes):
@@ -281,98 +341,91 @@ class EarlyMasks:
     overlay: object = None                                            # overlay: ONE pinned uint8 [L, Ho, Wo, 3] per video (model.overlay_output)
 
 
-def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True, frame_source=None, score=None):
+def result_head(model, cls_clips, out_size, n_frames, score=None, track_ids=True):
+    """The head of a video's result, offline and online: the video-level top-k (`select_tracks`), "pred_track_ids" (the tracker row
+    behind output j; `track_ids`, and always beside a score) and, with `score` (OverlapTables), "pred_gt".  -> (res, those rows)."""
+    sc, labels, inst = model.select_tracks(cls_clips)
+    res = {"image_size": (int(out_size[0]), int(out_size[1])), "pred_scores": sc.tolist(), "pred_labels": labels}
+    if track_ids:
+        res["pred_track_ids"] = list(inst)
+    if score is not None:                                          # (the counts of every window are in; select rows, read back)
+        res["pred_gt"] = score.result(list(inst), n_frames, model._copy_stream)
+        res.setdefault("pred_track_ids", list(inst))
+    return res, list(inst)
+
+
+def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True, frame_source=None, score=None,
+                 forms=None):
     """mdqe/mdqe.py:430-471.  The x4 aligned-bilinear up-sampling, sigmoid, crop (:357-358), nearest resize to the original size and
     the 0.5 threshold (:458-462) run as ONE kernel per window; windows in which an instance did not exist yet stay zero (:442).
-    `early` (EarlyMasks): the masks of every tracked instance are on the host already, only the selection is left.  Without it
-    (`windows`: (f_off, mean logits) per flushed window) the selected tracks' masks are produced here, in one pass and one copy.
-    `score` (OverlapTables): the video's overlap counts against its ground truth, gathered at every flush on any path -> "pred_gt"."""
-    sc, labels, inst = model.select_tracks(cls_clips)
-    Ho, Wo = int(image_size[0]), int(image_size[1])
-    res = {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels}
-    if not emit_masks:
-        return dict(res, pred_masks=[])
-    if score is not None:                                          # (OverlapTables: the counts of every window are in; select rows, read back)
-        res.update(pred_gt=score.result(inst, n_frames, model._copy_stream), pred_track_ids=list(inst))
-    geometry = bool(model.geometry_output)
-    labels = getattr(model, "label_output", False)
-    overlay = (frame_source, model.overlay_style) if frame_source is not None and getattr(model, "overlay_output", False) else None
-    if labels or overlay:
-        res.update(label_result(model, inst, windows, frame_hw, n_frames, (Ho, Wo), early, geometry and bool(labels), bool(labels), overlay))
-        if labels == "only":                                       # no per-track planes in either form
-            return dict(res, pred_masks=[])
-    rows, geoms = inst, early.geom if early is not None else []
-    if early is not None and model.rle_output:
-        res["pred_rles"] = stitch_rles(inst, n_frames, (Ho, Wo), [(f, nf, n, R.positions_to_rles(pos, n_pos, (Ho, Wo), nf))
-                                                                  for f, nf, n, pos, n_pos in early.rle])
-    elif early is not None:
-        early.done.synchronize()                                   # (the geom tables ride on the mask copies' stream)
-        res["pred_masks"] = [early.hosts[i].view(torch.bool)[:n_frames] for i in inst]
+    `forms`: the merger's record (ClipMerger.finish); None: resolved from the model here.  `early` (EarlyMasks): every form is on the
+    host already, only the selection is left.  Without it (`windows`: (f_off, mean logits) per flushed window) the forms are built here
+    (`build_window`; planes: the selected tracks only) into whole-video device buffers, one copy at the end; model.rle_output: the
+    planes are then encoded on the host.  `score` (OverlapTables): the counts gathered at every flush on any path -> "pred_gt".
+    "pred_label_map": uint8 [L, Ho, Wo], host; label t + 1 = tracker row t, 0 = background, so pred_label_map == pred_track_ids[j] + 1
+    is output j's exclusive region.  "pred_overlay": uint8 [L, Ho, Wo, 3], pinned host."""
+    if forms is None:
+        forms = Forms.of_model(model, emit_masks)
+        forms = dataclasses.replace(forms, overlay=forms.overlay and frame_source is not None)
+    out_size = Ho, Wo = int(image_size[0]), int(image_size[1])
+    res, inst = result_head(model, cls_clips, out_size, n_frames, score, track_ids=False)
+    rows, host, planes_res = inst, {}, {"pred_masks": []}          # ([]: no per-track planes in either form)
+    if forms == Forms():                                           # (emit_masks=False: nothing to build, nothing to wait for)
+        return dict(res, **planes_res)
+    if early is not None:
+        early.done.synchronize()                                   # (the geom tables ride on the copies' stream)
+        plane_geoms, label_geoms = early.geom, early.label_geom
+        if forms.planes == "rle":
+            planes_res = {"pred_rles": stitch_rles(inst, n_frames, out_size, [(f, nf, n, R.positions_to_rles(pos, n_pos, out_size, nf))
+                                                                              for f, nf, n, pos, n_pos in early.rle])}
+        elif forms.planes:
+            planes_res = {"pred_masks": [early.hosts[i].view(torch.bool)[:n_frames] for i in inst]}
+        host = {"labels": early.labels, "overlay": early.overlay}
     else:
         sel = sorted(set(inst))
-        rows = [sel.index(i) for i in inst]                        # rows of `out` = positions in sel
-        out = torch.zeros(len(sel), n_frames, Ho, Wo, dtype=torch.uint8, device=model.device)
-        sel_dev = torch.tensor(sel, dtype=torch.int32, device=model.device)
+        rows = [sel.index(i) for i in inst]                        # rows of the planes' buffer = positions in sel
+        plane_geoms, label_geoms, u8 = [], [], dict(dtype=torch.uint8, device=model.device)
+        # (the windows tile [0, n_frames): every row of the map and the picture is written; a track's planes start at its first window)
+        d_lab = torch.empty(n_frames, Ho, Wo, **u8) if forms.labels or forms.overlay else None
+        d_pic = torch.empty(n_frames, Ho, Wo, 3, **u8) if forms.overlay else None
+        d_planes = torch.zeros(len(sel), n_frames, Ho, Wo, **u8) if forms.planes else None
+        sel_dev = torch.tensor(sel, dtype=torch.int32, device=model.device) if forms.planes else None
         for f_off, m in windows:
-            cnt = sum(1 for i in sel if i < m.shape[0])           # sel is ascending: these are its first `cnt` entries
+            n, nf = int(m.shape[0]), int(m.shape[1])
+            cnt = sum(1 for i in sel if i < n)                     # sel is ascending: these are its first `cnt` entries
+            at = [None if t is None else (t, f_off) for t in (d_planes, d_lab, d_pic)]
+            lg, pg, _ = build_window(m, forms, sel_dev[:cnt] if forms.planes else None, model.cfg.match_stride, frame_hw, out_size, *at,
+                                     paint=(frame_source, f_off, model.overlay_style) if forms.overlay else None)
+            label_geoms.append((f_off, nf, n, lg))
             if cnt:
-                geoms.append((f_off, int(m.shape[1]), cnt,
-                              dense_masks(m, sel_dev[:cnt], model.cfg.match_stride, frame_hw, (Ho, Wo), geometry, out, f_off)))
-        hbuf = torch.empty(out.shape, dtype=torch.uint8, pin_memory=True)   # one D2H into pinned memory (pageable copies run at a fraction of PCIe)
-        hbuf.copy_(out, non_blocking=True)
+                plane_geoms.append((f_off, nf, cnt, pg))
+        # one D2H each into pinned memory (pageable copies run at a fraction of PCIe), one sync behind them
+        for k, t in (("overlay", d_pic), ("labels", d_lab if forms.labels else None), ("planes", d_planes)):
+            if t is not None:
+                host[k] = torch.empty(t.shape, dtype=torch.uint8, pin_memory=True)
+                host[k].copy_(t, non_blocking=True)
         torch.cuda.current_stream(model.device).synchronize()
-        host = hbuf.view(torch.bool)
-        if geometry:                                               # (the copies follow the masks' sync)
-            geoms = [(f, nf, cnt, g.cpu()) for f, nf, cnt, g in geoms]
-        if model.rle_output:                                       # no early path (unknown length): encode on the host
-            enc = [[R.encode_dense(fm.numpy()) for fm in host[p]] for p in range(len(sel))]
-            res["pred_rles"] = [enc[p] for p in rows]
-        else:
-            res["pred_masks"] = [host[p] for p in rows]
-    if geometry:
-        res.update(track_geometry(rows, n_frames, (Ho, Wo), geoms))
-    return res
-
-
-def label_result(model, inst, windows, frame_hw, n_frames, out_size, early, geometry, labels=True, overlay=None):
-    """The label-map keys of a video's result: "pred_label_map" (uint8 [L, Ho, Wo], host; label t + 1 = tracker row t, 0 = background),
-    "pred_track_ids" (the row behind output j, so pred_label_map == pred_track_ids[j] + 1 is output j's exclusive region) and, with
-    geometry, "pred_label_boxes" / "pred_label_areas" of those regions.  `early`: the map is on the host already (EarlyMasks.labels);
-    else it is produced here from `windows`, the same kernel over all rows of each window, in one pass and one copy.
-    `overlay` = (FrameStore, render.Style): also "pred_overlay" (uint8 [L, Ho, Wo, 3], pinned host), that map painted over the frames
-    (`overlay_frames`); with labels=False the map itself stays a device scratch and is not returned."""
-    Ho, Wo = out_size
-    host = pic = None
-    if early is not None:
-        early.done.synchronize()
-        geoms = early.label_geom
-        host = early.labels[:n_frames] if labels else None
-        pic = early.overlay[:n_frames] if overlay else None
-    else:
-        dev = torch.empty(n_frames, Ho, Wo, dtype=torch.uint8, device=model.device)    # (the windows tile [0, n_frames): every row is written)
-        if overlay:
-            dpic = torch.empty(n_frames, Ho, Wo, 3, dtype=torch.uint8, device=model.device)
-            geoms = [(f_off, int(m.shape[1]), int(m.shape[0]), overlay_frames(m, model.cfg.match_stride, frame_hw, (Ho, Wo), geometry, dev, f_off,
-                                                                              overlay[0], f_off, overlay[1], dpic, f_off)) for f_off, m in windows]
-            pic = torch.empty(dpic.shape, dtype=torch.uint8, pin_memory=True)
-            pic.copy_(dpic, non_blocking=True)
-        else:
-            geoms = [(f_off, int(m.shape[1]), int(m.shape[0]), label_maps(m, model.cfg.match_stride, frame_hw, (Ho, Wo), geometry, dev, f_off))
-                     for f_off, m in windows]
-        if labels:
-            host = torch.empty(dev.shape, dtype=torch.uint8, pin_memory=True)
-            host.copy_(dev, non_blocking=True)
-        torch.cuda.current_stream(model.device).synchronize()
-        if geometry:
-            geoms = [(f, nf, n, g.cpu()) for f, nf, n, g in geoms]
-    res = {"pred_track_ids": list(inst)}
-    if labels:
-        res["pred_label_map"] = host
-    if overlay:
-        res["pred_overlay"] = pic
-    if geometry:
-        geo = track_geometry(inst, n_frames, (Ho, Wo), geoms)
-        res.update(pred_label_boxes=geo["pred_boxes"], pred_label_areas=geo["pred_areas"])
+        # (the tables' copies follow the buffers' sync)
+        plane_geoms, label_geoms = ([(f, nf, n, g.cpu() if on else g) for f, nf, n, g in gs]
+                                    for on, gs in ((forms.plane_geometry, plane_geoms), (forms.label_geometry, label_geoms)))
+        if forms.planes:
+            planes = host["planes"].view(torch.bool)
+            if forms.planes == "rle":                              # no early path (unknown length): encode on the host
+                enc = [[R.encode_dense(fm.numpy()) for fm in planes[p]] for p in range(len(sel))]
+                planes_res = {"pred_rles": [enc[p] for p in rows]}
+            else:
+                planes_res = {"pred_masks": [planes[p] for p in rows]}
+    if forms.labels or forms.overlay:
+        res.setdefault("pred_track_ids", list(inst))
+    if forms.labels:
+        res["pred_label_map"] = host["labels"][:n_frames]
+    if forms.overlay:
+        res["pred_overlay"] = host["overlay"][:n_frames]
+    if forms.label_geometry:
+        res.update(track_geometry(inst, n_frames, out_size, label_geoms, labels=True))
+    res.update(planes_res)
+    if forms.plane_geometry:
+        res.update(track_geometry(rows, n_frames, out_size, plane_geoms))
     return res
 
 
@@ -388,19 +441,19 @@ class ClipMerger:
                  style=None, ground_truth=None):
         self.model, self.frame_hw, self.out_size, self.mask_hw = model, frame_hw, out_size, mask_hw
         self.emit_masks = emit_masks                # False: scores / labels only (ranks > 0 of a sharded video)
-        # boxes and areas of the final masks from the kernels that produce them (None: model.geometry_output; online sessions pass theirs)
-        self.geometry = bool(getattr(model, "geometry_output", False) if geometry is None else geometry)
         # online ("masks" | "rle" | "labels" | "overlay"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their
         # RLE, or their label map, or that map and its overlay -- of every current track are built and appended to `emitted`; neither the
         # logits nor a host buffer stay here (n_frames is unknown)
         self.online = online
+        # the forms of this video, for every path (geometry None: model.geometry_output; online sessions pass theirs)
+        self.forms = forms = Forms.of_emit(online, geometry, model) if online else Forms.of_model(model, emit_masks, geometry)
+        self.geometry = forms.plane_geometry or forms.label_geometry
         # False | True | "only" (model.label_output): the label map next to -- or, "only", instead of -- the per-track planes
-        self.labels = getattr(model, "label_output", False) if emit_masks and not online else False
-        # the overlay (model.overlay_output, online "overlay"): the label map painted over the frames of `frame_source` (a FrameStore)
-        self.overlay = bool(getattr(model, "overlay_output", False)) if emit_masks and not online else online == "overlay"
+        self.labels = False if online else forms.labels and ("only" if forms.planes is None else True)
+        # what an overlay paints on: the frames of `frame_source` (a FrameStore), in `style`
         self.frame_source = frame_source
         self.style = style if style is not None else getattr(model, "overlay_style", None)
-        if self.overlay and frame_source is None:
+        if forms.overlay and frame_source is None:
             raise ValueError("overlay output needs the frames of the whole video on this device; this path does not hold them (the sharded "
                              "driver does not offer it: rank 0 does not hold every frame)")
         # a vis_score.GroundTruth: every flushed window's final masks are counted against it (OverlapTables); None: nothing is
@@ -430,7 +483,7 @@ class ClipMerger:
         if self.early_on and n_frames is not None:
             per_track = int(n_frames) * int(out_size[0]) * int(out_size[1])
             # (the overlay's one pinned [n_frames, Ho, Wo, 3] buffer counts too)
-            if per_track * (self.EARLY_TRACKS + (3 if self.overlay else 0)) > float(os.environ.get("MDQE_EARLY_PINNED_GB", "24")) * 2 ** 30:
+            if per_track * (self.EARLY_TRACKS + (3 if forms.overlay else 0)) > float(os.environ.get("MDQE_EARLY_PINNED_GB", "24")) * 2 ** 30:
                 self.early_on = False
         self.dev = model.device
         self.use_side = self.dev.type == "cuda"
@@ -494,126 +547,110 @@ class ClipMerger:
                 if self.score is not None:                          # on every path, at the flush: the counts do not wait for the masks' form
                     self.score.window(m, cfg.match_stride, self.frame_hw, self.f_off)
                 # only the late path keeps the window's stride-4 logits for the rest of the video (under either MERGE_ON_CPU setting)
-                if not self.emit_masks:
-                    pass
-                elif self.online:
+                if self.online:
                     self.emitted.append(self._online_window(c, m))
-                elif self.use_side and self.n_frames is not None and (self.early_on or self.model.rle_output):
+                elif self.emit_masks and self.use_side and self.n_frames is not None and (self.early_on or self.forms.early_always):
                     self._early_masks(m)
-                else:
+                elif self.emit_masks:
                     self.windows.append((self.f_off, m))
                 self.f_off += m.shape[1]
                 self.saved += 1
         self.done = self.done or bool(last)
 
+    def _window_to_host(self, m, pairs, event):
+        """The early and the online path: the forms of ALL n rows of the window just flushed (m: [n, F, Hm, Wm] mean logits) into
+        per-window device scratch (`build_window`), each stage sent to the host behind it (`to_host`): pairs(kind, buffer) -> its (pinned
+        destination, source) pairs, kind = "labels" | "overlay" | "planes"; `event()` is recorded behind each hop.  -> build_window's."""
+        forms, u8 = self.forms, dict(dtype=torch.uint8, device=self.dev)
+        n, nf, Ho, Wo = int(m.shape[0]), int(m.shape[1]), int(self.out_size[0]), int(self.out_size[1])
+        lab = torch.empty(nf, Ho, Wo, **u8) if forms.labels or forms.overlay else None    # (an overlay alone: a scratch, not copied)
+        pic = torch.empty(nf, Ho, Wo, 3, **u8) if forms.overlay else None
+        rows = torch.arange(n, dtype=torch.int32, device=self.dev) if n and forms.planes else None
+        planes = torch.empty(n, nf, Ho, Wo, **u8) if rows is not None and forms.planes == "dense" else None
+        copies = {"labels": (pairs("labels", lab) if forms.labels else []) + (pairs("overlay", pic) if forms.overlay else []),
+                  "planes": pairs("planes", planes) if planes is not None else []}
+        # (the copy stream is created BEFORE the window's kernels are launched, and only by a window that copies, as ever: the order
+        # streams are first used in decides their queues)
+        cs = copy_stream(self.model) if copies["labels"] or copies["planes"] else None
+        at = [None if t is None else (t, 0) for t in (planes, lab, pic)]
+        return build_window(m, forms, rows, self.model.cfg.match_stride, self.frame_hw, self.out_size, *at,
+                            paint=(self.frame_source, self.f_off, self.style),
+                            hop=lambda stage, geom: to_host(cs, self.side, copies[stage], geom, event()))
+
     def _early_masks(self, m):
-        """Final masks of EVERY instance tracked so far for the window just flushed (m: [n, F, Hm, Wm] mean logits), copied to
-        pinned host memory on a copy stream while later windows compute; finish() then only selects rows.  A few rows may
-        be produced in vain (instances that miss the final top-k).  One pinned buffer per track (no re-allocation as tracks
-        appear; the caching host allocator recycles the blocks of the previous call).  model.rle_output: the run boundaries instead."""
-        model = self.model
-        n, nf = int(m.shape[0]), int(m.shape[1])
-        Ho, Wo = int(self.out_size[0]), int(self.out_size[1])
-        cs = copy_stream(model)
+        """Every form of EVERY instance tracked so far goes to pinned host memory while later windows compute; finish() then only
+        selects rows.  A few rows may be produced in vain (instances that miss the final top-k).  Planes: one pinned [L, Ho, Wo] buffer
+        per track (no re-allocation as tracks appear; the caching host allocator recycles the blocks of the previous call), or the run
+        boundaries.  Label map, overlay: one pinned [L, Ho, Wo(, 3)] buffer per video; a window without tracks is written too."""
+        model, forms = self.model, self.forms
+        n, nf, f0 = int(m.shape[0]), int(m.shape[1]), self.f_off
+        shape = (int(self.n_frames), int(self.out_size[0]), int(self.out_size[1]))
+        copy_stream(model)                          # (created here also when nothing is copied: the order of first use decides the queues)
         if self.early is None:
             self.early = EarlyMasks(done=torch.cuda.Event())
         early = self.early
-        if self.labels or self.overlay:
-            # one pinned [L, Ho, Wo] map per video, whatever the number of tracks; a window without tracks is written too (zeros).  The
-            # overlay: one pinned [L, Ho, Wo, 3] picture per video the same way; without label_output the map is a device scratch.
-            geometry = self.geometry and bool(self.labels)
-            dev = torch.empty(nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
-            copies, pic = [], None
-            if self.labels:
-                if early.labels is None:
-                    early.labels = model.pinned_mask_buffer((int(self.n_frames), Ho, Wo))
-                copies.append((early.labels[self.f_off:self.f_off + nf], dev))
-            if self.overlay:
-                if early.overlay is None:
-                    early.overlay = model.pinned_mask_buffer((int(self.n_frames), Ho, Wo, 3))
-                pic = torch.empty(nf, Ho, Wo, 3, dtype=torch.uint8, device=self.dev)
-                geom = overlay_frames(m, model.cfg.match_stride, self.frame_hw, self.out_size, geometry, dev, 0, self.frame_source, self.f_off,
-                                      self.style, pic, 0)
-                copies.append((early.overlay[self.f_off:self.f_off + nf], pic))
-            else:
-                geom = label_maps(m, model.cfg.match_stride, self.frame_hw, self.out_size, geometry, dev, 0)
-            geom = to_host(cs, self.side, dev, copies, geom, early.done)
-            if pic is not None:
-                pic.record_stream(cs)
-            if geometry:
-                early.label_geom.append((self.f_off, nf, n, geom))
-        if not n or self.labels == "only":
-            return
-        args = (m, torch.arange(n, dtype=torch.int32, device=self.dev), model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry)
-        if model.rle_output:
-            pos, n_pos, geom = rle_positions(*args)
-            early.rle.append((self.f_off, nf, n, pos, n_pos))
-        else:
-            while len(early.hosts) < n:             # a new track: its own pinned [L, Ho, Wo] buffer, zero before its first window (:442)
-                hbuf = model.pinned_mask_buffer((int(self.n_frames), Ho, Wo))
-                if self.f_off > 0:
-                    hbuf[:self.f_off].zero_()
-                early.hosts.append(hbuf)
-            dev = torch.empty(n, nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
-            geom = to_host(cs, self.side, dev, [(h[self.f_off:self.f_off + nf], d) for h, d in zip(early.hosts, dev)], dense_masks(*args, dev, 0),
-                           early.done)
-        if self.geometry:
-            early.geom.append((self.f_off, nf, n, geom))
+
+        def pairs(kind, buf):
+            if kind == "planes":
+                while len(early.hosts) < n:         # a new track: its own pinned buffer, zero before its first window (:442)
+                    early.hosts.append(model.pinned_mask_buffer(shape))
+                    if f0 > 0:
+                        early.hosts[-1][:f0].zero_()
+                return [(h[f0:f0 + nf], d) for h, d in zip(early.hosts, buf)]
+            if getattr(early, kind) is None:
+                setattr(early, kind, model.pinned_mask_buffer(shape + (3,) * (kind == "overlay")))
+            return [(getattr(early, kind)[f0:f0 + nf], buf)]
+        lgeom, pgeom, runs = self._window_to_host(m, pairs, lambda: early.done)
+        if forms.label_geometry:
+            early.label_geom.append((f0, nf, n, lgeom))
+        if runs is not None:
+            early.rle.append((f0, nf, n, *runs))
+        if n and forms.plane_geometry:
+            early.geom.append((f0, nf, n, pgeom))
 
     def _online_window(self, c, m):
-        """Online mode: the window just flushed (c: class rows [n, K] on the host, m: mean logits [n, F, Hm, Wm]) as a record --
-        frames, class rows, and the final masks of tracks 0..n-1: dense masks copied to a pinned host buffer on the copy stream
-        (`ready` fires when they and the geometry table are there), or their RLE dicts, or ("labels") their label map uint8 [F, Ho, Wo],
-        copied the same way, with the geometry of the labels' visible regions, or ("overlay") that map and its overlay uint8 [F, Ho, Wo, 3]."""
-        n, nf = int(m.shape[0]), int(m.shape[1])
-        Ho, Wo = int(self.out_size[0]), int(self.out_size[1])
+        """Online mode: the window just flushed (c: class rows [n, K] on the host) as a record -- frames, class rows, and the final masks
+        of tracks 0..n-1: "masks" in a pinned host buffer (`ready` fires when they and the geometry table "geom" are there), or their
+        "rles", or their label map "labels" uint8 [F, Ho, Wo], copied the same way, with the geometry of the labels' visible regions,
+        or that map and its "overlay" uint8 [F, Ho, Wo, 3] (a window without tracks: all background, the picture is the frames)."""
+        forms, n, nf, out_size = self.forms, int(m.shape[0]), int(m.shape[1]), (int(self.out_size[0]), int(self.out_size[1]))
         rec = {"frames": (self.f_off, self.f_off + nf), "cls_probs": c, "ready": None}
-        geom = torch.zeros((0, nf, 5), dtype=torch.int32) if self.geometry else None    # (the table of a window without tracks)
-        args = (m, torch.arange(n, dtype=torch.int32, device=self.dev), self.model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry)
-        if self.online in ("labels", "overlay"):                     # one plane per frame; a window without tracks is all background
-            cs = copy_stream(self.model)
-            dev = torch.empty(nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
-            host = self.model.pinned_mask_buffer((nf, Ho, Wo))
-            copies, pic = [(host, dev)], None
-            if self.overlay:                                         # ... and its picture over the frames pushed (a window without tracks: the frames)
-                pic = torch.empty(nf, Ho, Wo, 3, dtype=torch.uint8, device=self.dev)
-                geom = overlay_frames(m, self.model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry, dev, 0, self.frame_source,
-                                      self.f_off, self.style, pic, 0)
-                rec["overlay"] = self.model.pinned_mask_buffer((nf, Ho, Wo, 3))
-                copies.append((rec["overlay"], pic))
-            else:
-                geom = label_maps(m, self.model.cfg.match_stride, self.frame_hw, self.out_size, self.geometry, dev, 0)
-            rec["ready"] = torch.cuda.Event()
-            geom = to_host(cs, self.side, dev, copies, geom, rec["ready"])
-            if pic is not None:
-                pic.record_stream(cs)
-            rec["labels"] = host
-        elif self.online == "rle":
-            rec["rles"] = []
-            if n:
-                pos, n_pos, geom = rle_positions(*args)
-                rec["rles"] = R.positions_to_rles(pos, n_pos, (Ho, Wo), nf)
-        elif not n:
-            rec["masks"] = torch.zeros((0, nf, Ho, Wo), dtype=torch.bool)
-        else:
-            cs = copy_stream(self.model)
-            dev = torch.empty(n, nf, Ho, Wo, dtype=torch.uint8, device=self.dev)
-            geom = dense_masks(*args, dev, 0)
-            host = self.model.pinned_mask_buffer((n, nf, Ho, Wo))
-            rec["ready"] = torch.cuda.Event()
-            geom = to_host(cs, self.side, dev, [(host, dev)], geom, rec["ready"])
-            rec["masks"] = host.view(torch.bool)
-        if self.geometry:
-            rec["geom"] = geom
+        if forms.planes == "dense":
+            rec["masks"] = torch.zeros((0, nf) + out_size, dtype=torch.bool)
+
+        def pairs(kind, buf):                       # fresh pinned buffers, the record's
+            host = self.model.pinned_mask_buffer(tuple(buf.shape))
+            rec.update({"masks": host.view(torch.bool)} if kind == "planes" else {kind: host})
+            return [(host, buf)]
+
+        def event():                                # (None stays where nothing is copied: RLE, or a window without tracks)
+            rec["ready"] = rec["ready"] or torch.cuda.Event()
+            return rec["ready"]
+        lgeom, pgeom, runs = self._window_to_host(m, pairs, event)
+        if forms.planes == "rle":
+            rec["rles"] = R.positions_to_rles(*runs, out_size, nf) if n else []
+        if forms.label_geometry:
+            rec["geom"] = lgeom
+        elif forms.plane_geometry:                  # (a window without tracks: an empty table)
+            rec["geom"] = pgeom if n else torch.zeros((0, nf, 5), dtype=torch.int32)
         return rec
+
+    def feed_batches(self, results, to_the_end=False):
+        """Clip results in global order (`iter_clip_results`), fed to the tracker per decoder batch: the clips of one batch go together.
+        Stops behind the last clip, or (to_the_end) runs the iterator out.  Returns True once the last clip has been consumed."""
+        buf = []
+        for item in results:
+            buf.append(item)
+            if item[3].get("batch_end", True):
+                if self.feed_many(buf) and not to_the_end:
+                    return True
+                buf = []
+        return self.feed_many(buf)
 
     def finish(self):
         if self.use_side:
             self.main.wait_stream(self.side)
             for _, m in self.windows:
                 m.record_stream(self.main)
-        kw = {"frame_source": self.frame_source} if self.overlay else {}
-        if self.score is not None:
-            kw["score"] = self.score
         return self.model.inference_video(self.out_size, self.cls_clips, self.windows, self.frame_hw, self.f_off, early=self.early,
-                                          emit_masks=self.emit_masks, **kw)
+                                          emit_masks=self.emit_masks, frame_source=self.frame_source, score=self.score, forms=self.forms)

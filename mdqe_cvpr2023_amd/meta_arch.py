@@ -794,16 +794,7 @@ class MDQE(nn.Module):
         frames as handed in (merge.FrameStore), what `overlay_output` paints on.  ground_truth: the video's vis_score.GroundTruth or None
         (`_ground_truth`): the final masks are counted against it, "pred_gt"."""
         m = ClipMerger(self, frame_hw, out_size, mask_hw, n_frames, frame_source=frame_source, ground_truth=ground_truth)
-        buf = []
-        for item in results:                       # the clips of one decoder batch go to the tracker together
-            buf.append(item)
-            if item[3].get("batch_end", True):
-                done = m.feed_many(buf)
-                buf = []
-                if done:
-                    break
-        if buf:
-            m.feed_many(buf)
+        m.feed_batches(results)
         return m.finish()
 
     H2D_CHUNK = 10                                  # frames per host->device copy (one event each)
@@ -1108,10 +1099,9 @@ class MDQE(nn.Module):
 
     track_geometry = staticmethod(merge.track_geometry)
 
-    def inference_video(self, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True, frame_source=None, score=None):
-        """mdqe/mdqe.py:430-471: the video's result from its flushed windows (merge.video_result)."""
-        return merge.video_result(self, image_size, cls_clips, windows, frame_hw, n_frames, early=early, emit_masks=emit_masks,
-                                  frame_source=frame_source, score=score)
+    def inference_video(self, image_size, cls_clips, windows, frame_hw, n_frames, **kw):
+        """mdqe/mdqe.py:430-471: the video's result from its flushed windows (merge.video_result, its keywords)."""
+        return merge.video_result(self, image_size, cls_clips, windows, frame_hw, n_frames, **kw)
 
 
 class MDQE_MI355X(MDQE):

@@ -219,14 +219,8 @@ class OnlineVideo:
         model, m = self.model, self.merger
         self.carry.tail_sent = False
         self.carry.tail_from = carry_from(self.next_start, offset + int(frames_dev.shape[0]))
-        buf, n0 = [], len(m.emitted)
-        for item in model.iter_clip_results(frames_dev, clips, offset, h2d=h2d, carry=self.carry):
-            buf.append(item)
-            if item[3].get("batch_end", True):
-                m.feed_many(buf)
-                buf = []
-        if buf:
-            m.feed_many(buf)
+        n0 = len(m.emitted)
+        m.feed_batches(model.iter_clip_results(frames_dev, clips, offset, h2d=h2d, carry=self.carry), to_the_end=True)
         m.main.wait_stream(m.side)
         self.n_run += len(clips)
         return m.emitted[n0:]
@@ -318,27 +312,21 @@ class OnlineVideo:
             return self._result
         if not self.merger.cls_clips:
             raise RuntimeError("online_video: no tracker window was flushed (the schedule of this length has no last clip)")
-        sc, labels, inst = self.model.select_tracks(self.merger.cls_clips)
-        Ho, Wo = self.out_size
-        res = {"image_size": (Ho, Wo), "pred_scores": sc.tolist(), "pred_labels": labels, "pred_track_ids": list(inst)}
-        if self.merger.score is not None:
-            with self._ctx():
-                res["pred_gt"] = self.merger.score.result(list(inst), self.received, self.model._copy_stream)
-        if self.geometry:
-            geo = self.model.track_geometry(list(inst), self.received, (Ho, Wo), self.geoms)
-            if self.emit in ("labels", "overlay"):                 # (the windows' tables describe the labels' visible regions, not the full masks)
-                geo = {"pred_label_boxes": geo["pred_boxes"], "pred_label_areas": geo["pred_areas"]}
-            res.update(geo)
-        if self.keep and self.emit in ("labels", "overlay"):
+        from . import merge
+        forms, (Ho, Wo) = self.merger.forms, self.out_size
+        with self._ctx() if self.merger.score is not None else contextlib.nullcontext():
+            res, inst = merge.result_head(self.model, self.merger.cls_clips, self.out_size, self.received, self.merger.score)
+        if self.geometry:                         # (the windows' tables: the planes' or, for the label forms, the labels' visible regions')
+            res.update(merge.track_geometry(inst, self.received, self.out_size, self.geoms, labels=forms.labels))
+        if self.keep and forms.labels:
             res["pred_label_map"] = torch.cat([w.labels for w in self.kept])
-            if self.emit == "overlay":
+            if forms.overlay:
                 res["pred_overlay"] = torch.cat([w.overlay for w in self.kept])
         elif self.keep:
-            from . import merge
-            wins = [(w.frames[0], w.frames[1] - w.frames[0], len(w.track_ids), w.rles if self.emit == "rle" else w.masks) for w in self.kept]
-            if self.emit == "rle":
-                res["pred_rles"] = merge.stitch_rles(list(inst), self.received, (Ho, Wo), wins)
+            wins = [(w.frames[0], w.frames[1] - w.frames[0], len(w.track_ids), w.rles if forms.planes == "rle" else w.masks) for w in self.kept]
+            if forms.planes == "rle":
+                res["pred_rles"] = merge.stitch_rles(inst, self.received, (Ho, Wo), wins)
             else:
-                res["pred_masks"] = merge.stitch(list(inst), self.received, wins, lambda k: torch.zeros((k, Ho, Wo), dtype=torch.bool), torch.cat)
+                res["pred_masks"] = merge.stitch(inst, self.received, wins, lambda k: torch.zeros((k, Ho, Wo), dtype=torch.bool), torch.cat)
         self._result = res
         return res

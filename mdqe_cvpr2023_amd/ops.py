@@ -594,7 +594,7 @@ def final_label_map(logits, inst_idx, factor, h, w, Ho, Wo, out, f_off, geom=Non
         raise RuntimeError("final_label_map: out must be contiguous CUDA uint8 [>= f_off + Fw = %d, Ho, Wo]" % (f_off + Fw))
     k, Fw, Hm, Wm = _final_mask_args(logits, inst_idx, True)
     if geom is not None:
-        geom = _geom_rows(None if geom is True else geom, k * Fw, logits.device)
+        geom = _geom_rows(geom, k * Fw, logits.device)
     check(lib.mdqe_final_label_map_u8(ptr(logits), k, ptr(inst_idx), Fw, Hm, Wm, factor, h, w, Ho, Wo, ptr(out), f_off,
                                       ptr(geom) if geom is not None and k else None, cur_stream()), "final_label_map")
     return out, geom
@@ -778,7 +778,7 @@ def image_final_masks(logits, idx, factor, h, w, Ho, Wo):
 
 
 def _geom_rows(geom, rows, device):
-    if geom is None:
+    if geom is None or geom is True:                      # (allocate)
         return torch.empty(rows, 5, dtype=torch.int32, device=device)
     _chk(geom, "geom", torch.int32)
     if tuple(geom.shape) != (rows, 5):

@@ -159,7 +159,10 @@ def _model(**kw):
 
 L, OUT = 17, (90, 150)
 SETTINGS = {"off": {}, "lab": {"label_output": True}, "geo": {"label_output": True, "geometry_output": True}, "rle": {"rle_output": True},
-            "late": {"early_masks": False}, "late_lab": {"early_masks": False, "label_output": True}}
+            "late": {"early_masks": False}, "late_lab": {"early_masks": False, "label_output": True},
+            # every plane, label, overlay and geometry form together, through the early path and through the late one
+            "rle_lab_geo": {"rle_output": True, "label_output": True, "geometry_output": True},
+            "late_rle_lab_geo": {"rle_output": True, "label_output": True, "geometry_output": True, "early_masks": False}}
 
 
 def _forward(model, frames, **attrs):

@@ -1,6 +1,8 @@
 """Do two trees compute the same final masks on every output path?  One 17-frame synthetic video (96 x 160, output 90 x 150, windows of
-6 frames so that tracks appear in later windows) through forward() with every early_masks x rle_output x geometry_output and through
-online_video with every emit x geometry x keep in pushes of 1, 5 and all frames; everything returned is kept.
+6 frames so that tracks appear in later windows) through forward() with every early_masks x rle_output x geometry_output x
+label_output (False, True, "only") x overlay_output x ground truth (none, seeded random masks at the output size) and through
+online_video with every emit (masks, rle, labels, overlay) x geometry x keep in pushes of 1, 5 and all frames, once more with the
+ground truth; everything returned is kept.
 
     python tools/final_mask_paths_ab.py dump OUT.pt                 # in each tree (the tool is self-contained: copy it into the other one)
     python tools/final_mask_paths_ab.py compare A.pt B.pt [--out FILE]
@@ -65,20 +67,34 @@ def dump(path):
     model = MDQE(cfg, state_dict=random_state(cfg, seed=3)).eval()
     L, (Ho, Wo) = 17, (90, 150)
     frames = synth_video(0, L, seed=1, h=96, w=160, n_obj=4).cuda()
+    from mdqe_cvpr2023_amd.vis_score import GroundTruth
+    g = torch.Generator().manual_seed(11)
+    gt = GroundTruth(masks=torch.rand(3, L, Ho // 10, Wo // 10, generator=g).gt(0.6).repeat_interleave(10, 2).repeat_interleave(10, 3),
+                     category_ids=[1, 2, 3])
     out = {}
-    for early, rle, geo in itertools.product((True, False), repeat=3):
-        model.early_masks, model.rle_output, model.geometry_output = early, rle, geo
-        out["forward early=%d rle=%d geometry=%d" % (early, rle, geo)] = _plain(model([{"image": frames, "height": Ho, "width": Wo}]))
-    model.early_masks, model.rle_output, model.geometry_output = True, False, False
-    for emit, geo, keep in itertools.product(("masks", "rle"), (False, True), (False, True)):
+    flags = ("early_masks", "rle_output", "geometry_output", "label_output", "overlay_output")
+    saved = {k: getattr(model, k) for k in flags}
+    for lab, ov, scored in itertools.product((False, True, "only"), (False, True), (False, True)):
+        for early, rle, geo in itertools.product((True, False), repeat=3):
+            for k, v in zip(flags, (early, rle, geo, lab, ov)):
+                setattr(model, k, v)
+            name = "forward early=%d rle=%d geometry=%d" % (early, rle, geo)       # (the cases of before this list grew keep their names)
+            if lab or ov or scored:
+                name += " labels=%s overlay=%d gt=%d" % (lab, ov, scored)
+            item = {"image": frames, "height": Ho, "width": Wo}
+            out[name] = _plain(model([dict(item, ground_truth=gt) if scored else item]))
+    for k, v in saved.items():
+        setattr(model, k, v)
+    for emit, geo, keep, scored in itertools.product(("masks", "rle", "labels", "overlay"), (False, True), (False, True), (False, True)):
         for name, sizes in (("1", [1] * L), ("5", [min(5, L - a) for a in range(0, L, 5)]), ("all", [L])):
-            ov = model.online_video(height=Ho, width=Wo, emit=emit, keep=keep, geometry=geo)
+            ov = model.online_video(height=Ho, width=Wo, emit=emit, keep=keep, geometry=geo, **({"ground_truth": gt} if scored else {}))
             wins, a = [], 0
             for n in sizes:
                 wins += [_plain(w) for w in ov.push(frames[a:a + n])]
                 a += n
             wins += [_plain(w) for w in ov.close()]
-            out["online emit=%s geometry=%d keep=%d pushes=%s" % (emit, geo, keep, name)] = {"windows": wins, "result": _plain(ov.result())}
+            out["online emit=%s geometry=%d keep=%d pushes=%s%s" % (emit, geo, keep, name, " gt=1" if scored else "")] = {
+                "windows": wins, "result": _plain(ov.result())}
     torch.cuda.synchronize()
     torch.save(out, path)
     print("%d cases -> %s" % (len(out), path))
@@ -92,7 +108,7 @@ def compare(pa, pb):
     for k in a:
         same = k in b and _same(a[k], b[k])
         ok = ok and same
-        lines.append("%-52s %3d tensors %4d RLE strings  %s" % ((k,) + _count(a[k]) + ("identical" if same else "DIFFERENT",)))
+        lines.append("%-76s %3d tensors %4d RLE strings  %s" % ((k,) + _count(a[k]) + ("identical" if same else "DIFFERENT",)))
     return ok, lines
 
 
