@@ -544,6 +544,45 @@ int mdqe_render_overlay_u8(const void* frames, int is_u8, long frame_stride, int
                            const unsigned char* palette, int a256, int contour,
                            unsigned char* out, int f_off, void* stream);
 
+/* The same map painted straight onto decoder surfaces, in the YUV domain, for an encoder (csrc/render_yuv.hip): semi-planar YUV 4:2:0
+ * in, painted surfaces of the SAME format out.  y, y_pitch, y_stride, uv, uv_pitch, uv_stride, H, W, fmt (0 NV12, 1 P010) are exactly
+ * mdqe_yuv420sp_to_rgb_u8's: pitches and strides in BYTES, a P010 sample's value is word >> 6.  F surfaces; labels: uint8 [F, H, W],
+ * contiguous, at the surfaces' own size (nothing is resampled here); palette_yuv: uint16 [256, 3], rows (Y, U, V) in sample units, 0..255
+ * for NV12 and 0..1023 for P010 (only those 8 / 10 bits of an entry are used).  The output planes have the input planes' layout with
+ * their own pitches and strides; surface f is written at out_y + (f_off + f) * out_y_stride and out_uv + (f_off + f) * out_uv_stride.
+ * Integers only, ONE definition (>> acts on non-negative values only):
+ *   label     l = labels[f][r][c];
+ *   contour   edge = for some d in 1..contour and some direction (+-d, 0), (0, +-d) the neighbour lies INSIDE the picture and its
+ *             label differs from l: mdqe_render_overlay_u8's definition (contour = 0: no contours);
+ *   blend     blend(s, p) = (s * (256 - a256) + p * a256 + 128) >> 8;
+ *   pixel     px(s, p) = s if l == 0, else p if edge, else blend(s, p);
+ *   luma      Yout[r][c] = px(Y[r][c], palette_yuv[l][0]);
+ *   chroma    one (U, V) pair serves the in-picture pixels i of its 2 x 2 block, n = 1, 2 or 4 of them (odd right / bottom edges).  With
+ *             C the pair's U (k = 1) or V (k = 2) and l_i, edge_i the pixels' own labels and edges:
+ *               Cout = (sum_i px_i(C, palette_yuv[l_i][k]) + n / 2) >> log2(n),
+ *             so a block whose pixels all have label 0 keeps C;
+ *   P010      a word the rule leaves unchanged -- luma with l == 0, a chroma pair with every label of its block 0 -- is copied with all
+ *             16 of its bits; every other word is written as value << 6.
+ * A background pixel therefore keeps the decoder's bits exactly.  Writes cover W luma samples and 2 * ceil(W/2) chroma samples per row,
+ * H and ceil(H/2) rows per surface: output padding is never written, input padding never read.
+ * In and out: an output plane may BE its input plane -- the same address (after f_off), pitch and stride: painting in place; luma and
+ * chroma independently -- since every sample is read and written by the one thread that owns it.  Any other overlap is refused
+ * (MDQE_EINVAL): a surface of an output plane (its first to its last byte written, the rows' padding between them included) must not
+ * meet a surface of an input plane, of the other output plane, the labels or the palette.  Planes may interleave as a decoder's
+ * allocation does (luma 0, chroma 0, luma 1, ...).  Two surfaces of an output plane must not share bytes (F > 1: out strides >= the
+ * bytes a surface spans).
+ * MDQE_EINVAL, before any pointer is looked at, for a256 outside 0..256, contour outside 0..3, H or W <= 0, F < 0, f_off < 0, fmt outside
+ * {0, 1}, an input or output pitch smaller than a row (W samples of luma, 2 * ceil(W/2) of chroma), a negative stride, odd P010 pitches
+ * or strides, and F * H * W >= 2^31 - 1; F == 0 returns OK and launches nothing; odd P010 plane pointers and an odd palette pointer are
+ * MDQE_EINVAL.  Nothing else needs to be aligned: where every plane pointer (in, out, labels), pitch, stride and W are multiples of 4
+ * bytes the launch moves 4 bytes per access (16 where they are multiples of 16 and contour == 0), otherwise single samples.  One
+ * launch, no atomics: identical from run to run.  Never allocates, never synchronises. */
+int mdqe_render_overlay_yuv420sp(const void* y, long y_pitch, long y_stride, const void* uv, long uv_pitch, long uv_stride,
+                                 int F, int H, int W, int fmt /*0 nv12, 1 p010*/, const unsigned char* labels,
+                                 const unsigned short* palette_yuv, int a256, int contour,
+                                 void* out_y, long out_y_pitch, long out_y_stride,
+                                 void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream);
+
 /* ---- COCO single-image branch, after the decoder (MDQE.inference_image, mdqe/mdqe.py:486-556), on the centre frame's
  * low-resolution logits [n,Hm,Wm]; aligned_bilinear x`factor` in closed form, crop [:h,:w].
  * stats[k] = {sum(sigmoid*[sigmoid>0.5]), count(sigmoid>0.5), xmin, ymin, xmax, ymax of (logit > 0)} (:512-516, :526;

@@ -1,0 +1,348 @@
+// Overlays painted straight onto decoder surfaces: semi-planar YUV 4:2:0 (NV12, P010) in, painted surfaces of the same format out, for
+// an encoder.  ONE definition, integers only (include/mdqe_hip.h has the rule); tests/_overlay_yuv_ref.py restates it in numpy and every
+// comparison is exact.  A background pixel keeps the decoder's bits (P010: all 16 of a word).
+//
+// A pure streaming pass: 1 label byte + 1.5 surface bytes in and 1.5 out per pixel for NV12 (P010: 1 + 3 in, 3 out).  A thread owns a
+// block of 2 rows by PX pixels -- the two rows that share a chroma row, as in yuv.hip: every chroma pair has ONE writer, which holds the
+// four labels that decide it -- and the whole batch is one launch of one thread per block.  PX is a per-launch decision of the entry:
+//   PX = 16  every plane pointer (in, out, labels), pitch, stride and W are multiples of 16 bytes AND contour == 0: 16-byte accesses;
+//   PX = 4   the same with multiples of 4, any contour: 4-byte accesses;
+//   PX = 2   anything else: single samples, one 2 x 2 block per thread.
+// Why a contour launch stays at PX = 4 (profiles/overlay_surface_ab.txt): with the neighbour rows in registers a PX = 16 thread is a
+// long chain over 32 pixels and a window is only some 3 waves per SIMD of them; measured on 30 NV12 surfaces, contour 1, the 4-byte
+// form takes 21.5 us against 38.0 (360 x 640) and 102 against 151 (1080 x 1920), contour 3 half the time at both sizes.  Without a
+// contour the 16-byte form is the faster one at 1080p (46.9 us against 63.0) and no slower at 360p.
+// In a wide launch a block whose contour neighbours lie inside its row (c0 >= R and c0 + PX + R <= W) and whose second row exists takes
+// the wide path: the label rows r0 - R .. r0 + 1 + R of its columns are 2 + 2R aligned chunk reads (the rows outside the picture are not
+// read and never count), the horizontal neighbours are the chunk shifted by d bytes against the dwords to its left and right, all read
+// straight from the map -- they are the bytes the neighbouring lanes and row pairs read anyway, so they hit L1 (what render.hip found);
+// there is no LDS tile.  Everything else -- the blocks at a row's ends, the odd last row, every block of a PX = 2 launch -- goes through the
+// per-sample path, the rule as written with every bound checked.  The 256 palette rows sit in LDS, one packed dword each.  No atomics;
+// a thread reads the surface samples it owns and nothing else of the surfaces, then writes the same samples of the output: the output
+// is a function of the inputs, also when the output planes ARE the input planes (the only overlap the entry accepts).
+//
+// No clamp is needed anywhere: a blend lies between its two operands and a rounded mean between its smallest and largest term.  The
+// shifts are plain shifts of non-negative 32-bit values, each followed by a mask or a select, never a shift-then-clamp pair (see the
+// note above clamp8 in yuv.hip); the exact comparisons of tests/test_overlay_yuv_gpu.py are the guard.
+#include "common.h"
+
+namespace {
+
+struct RenderYuvArgs {
+  const unsigned char* y;
+  const unsigned char* uv;
+  const unsigned char* labels;                   // [F, H, W]
+  const unsigned short* palette;                 // [256, 3]: Y, U, V in sample units
+  unsigned char* oy;                             // at frame f_off already
+  unsigned char* ouv;
+  long y_pitch, y_stride, uv_pitch, uv_stride;   // bytes
+  long oy_pitch, oy_stride, ouv_pitch, ouv_stride;
+  int H, W;
+  unsigned XU, RP, n_units;                      // blocks per row pair, row pairs per surface, F * RP * XU
+  uint32_t a256;
+};
+
+template <int BYTES, int ALIGN>
+__device__ __forceinline__ void ld_chunk(uint32_t* dst, const unsigned char* p) {
+  __builtin_memcpy(dst, __builtin_assume_aligned(p, ALIGN), BYTES);
+}
+
+template <int BYTES, int ALIGN>
+__device__ __forceinline__ void st_chunk(unsigned char* p, const uint32_t* src) {
+  __builtin_memcpy(__builtin_assume_aligned(p, ALIGN), src, BYTES);
+}
+
+// stored sample i of a row chunk held in dwords, as it lies in memory: a byte (NV12) or a little-endian 16-bit word (P010)
+template <int FMT>
+__device__ __forceinline__ uint32_t chunk_raw(const uint32_t* w, int i) {
+  return FMT == 0 ? (w[i >> 2] >> (8 * (i & 3))) & 0xFFu : (w[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
+}
+
+template <int FMT>
+__device__ __forceinline__ void chunk_put(uint32_t* w, int i, uint32_t raw) {
+  if (FMT == 0) {
+    if ((i & 3) == 0) w[i >> 2] = raw; else w[i >> 2] |= raw << (8 * (i & 3));
+  } else {
+    if ((i & 1) == 0) w[i >> 1] = raw; else w[i >> 1] |= raw << 16;
+  }
+}
+
+// stored sample i of a plane row in memory, and its store
+template <int FMT>
+__device__ __forceinline__ uint32_t row_raw(const unsigned char* row, int i) {
+  return FMT == 0 ? (uint32_t)row[i] : (uint32_t)((const unsigned short*)row)[i];
+}
+
+template <int FMT>
+__device__ __forceinline__ void row_put(unsigned char* row, int i, uint32_t raw) {
+  if (FMT == 0) row[i] = (unsigned char)raw; else ((unsigned short*)row)[i] = (unsigned short)raw;
+}
+
+// the value of a stored sample, and the stored form of a value the rule produced
+template <int FMT> __device__ __forceinline__ uint32_t value_of(uint32_t raw) { return FMT == 0 ? raw : raw >> 6; }
+template <int FMT> __device__ __forceinline__ uint32_t stored(uint32_t v) { return FMT == 0 ? v : v << 6; }
+
+// px(s, p) of the rule: background keeps the sample, a contour pixel takes the palette component, the rest blends.  s, p <= 1023:
+// s * (256 - a) + p * a + 128 <= 1023 * 256 + 128 < 2^19.
+__device__ __forceinline__ uint32_t px(uint32_t s, uint32_t p, uint32_t l, bool edge, uint32_t a) {
+  const uint32_t b = (s * (256u - a) + p * a + 128u) >> 8;
+  const uint32_t o = edge ? p : b;
+  return l != 0u ? o : s;
+}
+
+template <int FMT> __device__ __forceinline__ uint32_t pal_y(uint32_t c) { return c & (FMT ? 0x3FFu : 0xFFu); }
+template <int FMT> __device__ __forceinline__ uint32_t pal_u(uint32_t c) { return (c >> 10) & (FMT ? 0x3FFu : 0xFFu); }
+template <int FMT> __device__ __forceinline__ uint32_t pal_v(uint32_t c) { return (c >> 20) & (FMT ? 0x3FFu : 0xFFu); }
+
+// One 2 x 2 block (columns c, c + 1 of rows r0, r0 + 1; c even, c < W, r0 < H) with every bound checked: the rule as written.  `lab` is
+// the label of (r0, c), yrow / oyrow row r0 of the luma planes, crow / ocrow the chroma row of the pair.
+template <int FMT, int R>
+__device__ __forceinline__ void paint_block(const RenderYuvArgs& a, const uint32_t* pal, const unsigned char* lab, int r0, int c,
+                                            const unsigned char* yrow, const unsigned char* crow, unsigned char* oyrow, unsigned char* ocrow) {
+  const uint32_t ru = row_raw<FMT>(crow, c), rv = row_raw<FMT>(crow, c + 1);
+  const uint32_t U = value_of<FMT>(ru), V = value_of<FMT>(rv);
+  uint32_t su = 0u, sv = 0u, any = 0u, n = 0u;
+  for (int row = 0; row < 2 && r0 + row < a.H; ++row) {
+    for (int k = 0; k < 2 && c + k < a.W; ++k) {
+      const int Y = r0 + row, X = c + k;
+      const unsigned char* q = lab + (long)row * a.W + k;
+      const uint32_t l = q[0];
+      bool edge = false;
+#pragma unroll
+      for (int d = 1; d <= R; ++d) {
+        if (X - d >= 0) edge |= q[-d] != l;
+        if (X + d < a.W) edge |= q[d] != l;
+        if (Y - d >= 0) edge |= q[-(long)d * a.W] != l;
+        if (Y + d < a.H) edge |= q[(long)d * a.W] != l;
+      }
+      const uint32_t col = pal[l];
+      const uint32_t ry = row_raw<FMT>(yrow + (long)row * a.y_pitch, X);
+      const uint32_t yo = px(value_of<FMT>(ry), pal_y<FMT>(col), l, edge, a.a256);
+      row_put<FMT>(oyrow + (long)row * a.oy_pitch, X, l != 0u ? stored<FMT>(yo) : ry);
+      su += px(U, pal_u<FMT>(col), l, edge, a.a256);
+      sv += px(V, pal_v<FMT>(col), l, edge, a.a256);
+      any |= l;
+      ++n;
+    }
+  }
+  // n is 1, 2 or 4: (sum + n / 2) >> log2(n)
+  const uint32_t sh = n >> 1;                                        // 0, 1, 2
+  const uint32_t uo = (su + sh) >> sh, vo = (sv + sh) >> sh;
+  row_put<FMT>(ocrow, c, any != 0u ? stored<FMT>(uo) : ru);
+  row_put<FMT>(ocrow, c + 1, any != 0u ? stored<FMT>(vo) : rv);
+}
+
+template <int FMT, int PX, int R>
+__global__ __launch_bounds__(256) void render_overlay_yuv_kernel(const RenderYuvArgs a) {
+  __shared__ uint32_t pal[256];
+  {
+    const unsigned short* q = a.palette + 3 * threadIdx.x;
+    pal[threadIdx.x] = ((uint32_t)q[0] & 0x3FFu) | ((uint32_t)q[1] & 0x3FFu) << 10 | ((uint32_t)q[2] & 0x3FFu) << 20;
+  }
+  __syncthreads();
+  const unsigned u = blockIdx.x * 256u + threadIdx.x;
+  if (u >= a.n_units) return;
+  const unsigned rpn = u / a.XU, xu = u - rpn * a.XU;              // row pair over the batch, block of the row pair
+  const unsigned n = rpn / a.RP, rp = rpn - n * a.RP;
+  const int r0 = 2 * (int)rp, c0 = PX * (int)xu;
+  constexpr int BPS = FMT ? 2 : 1;                                   // bytes per sample
+  const unsigned char* yrow = a.y + n * a.y_stride + (long)r0 * a.y_pitch;
+  const unsigned char* crow = a.uv + n * a.uv_stride + (long)rp * a.uv_pitch;
+  unsigned char* oyrow = a.oy + n * a.oy_stride + (long)r0 * a.oy_pitch;
+  unsigned char* ocrow = a.ouv + n * a.ouv_stride + (long)rp * a.ouv_pitch;
+  const unsigned char* lab = a.labels + ((long)n * a.H + r0) * a.W + c0;
+  if constexpr (PX > 2) if (r0 + 1 < a.H && c0 >= R && c0 + PX + R <= a.W) {
+    // the wide path: rows r0 and r0 + 1, pixels c0 .. c0 + PX - 1, every horizontal neighbour inside the row
+    constexpr int NL = PX / 4, NW = PX * BPS / 4;
+    uint32_t lr[2 * R + 2][NL];                                      // label rows r0 - R .. r0 + 1 + R (those inside the picture)
+#pragma unroll
+    for (int k = 0; k < 2 * R + 2; ++k) {
+      const int rr = r0 - R + k;
+      if (rr >= 0 && rr < a.H) {
+        ld_chunk<PX, PX>(lr[k], lab + (long)(k - R) * a.W);
+      } else {
+#pragma unroll
+        for (int j = 0; j < NL; ++j) lr[k][j] = 0u;
+      }
+    }
+    uint32_t diff[2][NL];                                            // byte i != 0: pixel i has a neighbour with another label
+#pragma unroll
+    for (int row = 0; row < 2; ++row) {
+      const uint32_t* c4 = lr[R + row];
+#pragma unroll
+      for (int j = 0; j < NL; ++j) diff[row][j] = 0u;
+      if (R > 0) {
+        uint32_t e[NL + 2];                                          // the dword to the left, the chunk, the dword to the right
+        ld_chunk<4, 4>(&e[0], lab + (long)row * a.W - 4);            // (c0 >= R > 0 and c0 a multiple of PX: c0 >= 4)
+        ld_chunk<4, 4>(&e[NL + 1], lab + (long)row * a.W + PX);      // (c0 + PX + R <= W, W a multiple of PX: c0 + PX + 4 <= W)
+#pragma unroll
+        for (int j = 0; j < NL; ++j) e[j + 1] = c4[j];
+#pragma unroll
+        for (int d = 1; d <= R; ++d) {
+#pragma unroll
+          for (int j = 0; j < NL; ++j) {
+            const uint64_t lo = (uint64_t)e[j + 1] << 32 | e[j], hi = (uint64_t)e[j + 2] << 32 | e[j + 1];
+            diff[row][j] |= c4[j] ^ (uint32_t)(lo >> (32 - 8 * d));  // the bytes d pixels to the left
+            diff[row][j] |= c4[j] ^ (uint32_t)(hi >> (8 * d));       // d pixels to the right
+          }
+          const int up = r0 + row - d, dn = r0 + row + d;
+          if (up >= 0) {
+#pragma unroll
+            for (int j = 0; j < NL; ++j) diff[row][j] |= c4[j] ^ lr[R + row - d][j];
+          }
+          if (dn < a.H) {
+#pragma unroll
+            for (int j = 0; j < NL; ++j) diff[row][j] |= c4[j] ^ lr[R + row + d][j];
+          }
+        }
+      }
+    }
+    uint32_t yw[2][NW], cw[NW], oyw[2][NW], ocw[NW];
+    ld_chunk<4 * NW, PX>(yw[0], yrow + (long)c0 * BPS);
+    ld_chunk<4 * NW, PX>(yw[1], yrow + a.y_pitch + (long)c0 * BPS);
+    ld_chunk<4 * NW, PX>(cw, crow + (long)c0 * BPS);               // c0 is even: pair c0 / 2 starts at sample c0
+#pragma unroll
+    for (int p = 0; p < PX / 2; ++p) {
+      const uint32_t ru = chunk_raw<FMT>(cw, 2 * p), rv = chunk_raw<FMT>(cw, 2 * p + 1);
+      const uint32_t U = value_of<FMT>(ru), V = value_of<FMT>(rv);
+      uint32_t su = 0u, sv = 0u, any = 0u;
+#pragma unroll
+      for (int row = 0; row < 2; ++row) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          const int i = 2 * p + k;
+          const uint32_t l = (lr[R + row][i >> 2] >> (8 * (i & 3))) & 0xFFu;
+          const bool edge = ((diff[row][i >> 2] >> (8 * (i & 3))) & 0xFFu) != 0u;
+          const uint32_t col = pal[l];
+          const uint32_t ry = chunk_raw<FMT>(yw[row], i);
+          const uint32_t yo = px(value_of<FMT>(ry), pal_y<FMT>(col), l, edge, a.a256);
+          chunk_put<FMT>(oyw[row], i, l != 0u ? stored<FMT>(yo) : ry);
+          su += px(U, pal_u<FMT>(col), l, edge, a.a256);
+          sv += px(V, pal_v<FMT>(col), l, edge, a.a256);
+          any |= l;
+        }
+      }
+      const uint32_t uo = (su + 2u) >> 2, vo = (sv + 2u) >> 2;
+      chunk_put<FMT>(ocw, 2 * p, any != 0u ? stored<FMT>(uo) : ru);
+      chunk_put<FMT>(ocw, 2 * p + 1, any != 0u ? stored<FMT>(vo) : rv);
+    }
+    st_chunk<4 * NW, PX>(oyrow + (long)c0 * BPS, oyw[0]);
+    st_chunk<4 * NW, PX>(oyrow + a.oy_pitch + (long)c0 * BPS, oyw[1]);
+    st_chunk<4 * NW, PX>(ocrow + (long)c0 * BPS, ocw);
+    return;
+  }
+  // the per-sample path
+  for (int p = 0; p < PX / 2; ++p) {
+    const int c = c0 + 2 * p;
+    if (c >= a.W) break;
+    paint_block<FMT, R>(a, pal, lab + 2 * p, r0, c, yrow, crow, oyrow, ocrow);
+  }
+}
+
+template <int FMT, int PX>
+void launch_r(int contour, dim3 grid, hipStream_t stream, const RenderYuvArgs& a) {
+  switch (contour) {
+    case 0: hipLaunchKernelGGL((render_overlay_yuv_kernel<FMT, PX, 0>), grid, dim3(256), 0, stream, a); break;
+    case 1: hipLaunchKernelGGL((render_overlay_yuv_kernel<FMT, PX, 1>), grid, dim3(256), 0, stream, a); break;
+    case 2: hipLaunchKernelGGL((render_overlay_yuv_kernel<FMT, PX, 2>), grid, dim3(256), 0, stream, a); break;
+    default: hipLaunchKernelGGL((render_overlay_yuv_kernel<FMT, PX, 3>), grid, dim3(256), 0, stream, a); break;
+  }
+}
+
+template <int FMT>
+void launch_render_yuv(int px, int contour, dim3 grid, hipStream_t stream, const RenderYuvArgs& a) {
+  switch (px) {
+    case 16: hipLaunchKernelGGL((render_overlay_yuv_kernel<FMT, 16, 0>), grid, dim3(256), 0, stream, a); break;   // (contour == 0 only)
+    case 4: launch_r<FMT, 4>(contour, grid, stream, a); break;
+    default: launch_r<FMT, 2>(contour, grid, stream, a); break;
+  }
+}
+
+// A plane of the call: n surfaces of `extent` bytes (first byte to last byte of a surface, the rows' padding included), `stride` bytes
+// apart.  Planes of one decoder allocation interleave (luma 0, chroma 0, luma 1, ...), so what must not meet are SURFACES, not spans.
+struct Plane { long lo, stride, extent; int n; };
+Plane plane_of(const void* p, long pitch, long stride, int n, long rows, long row_bytes) {
+  return {(long)(uintptr_t)p, n > 1 ? stride : 0, (rows - 1) * pitch + row_bytes, n};
+}
+bool apart(const Plane& s, const Plane& t) {
+  const long s_hi = s.lo + (s.n - 1) * s.stride + s.extent, t_hi = t.lo + (t.n - 1) * t.stride + t.extent;
+  if (s_hi <= t.lo || t_hi <= s.lo) return true;                     // the spans do not meet
+  if (s.n == t.n && s.stride == t.stride && s.stride > 0 && s.extent <= s.stride && t.extent <= s.stride) {
+    // one stride: surface j of t starts d + k * stride behind some surface of s, 0 <= d < stride; they meet iff d < s.extent (k = 0) or
+    // d + t.extent > stride (k = -1).  (Which k occur is not looked at: that only refuses more.)
+    const long m = (t.lo - s.lo) % s.stride, d = m < 0 ? m + s.stride : m;
+    return d >= s.extent && d + t.extent <= s.stride;
+  }
+  for (int i = 0; i < s.n; ++i)                                      // anything else: surface by surface
+    for (int j = 0; j < t.n; ++j) {
+      const long a = s.lo + i * s.stride, b = t.lo + j * t.stride;
+      if (a < b + t.extent && b < a + s.extent) return false;
+    }
+  return true;
+}
+
+}  // namespace
+
+extern "C" int mdqe_render_overlay_yuv420sp(const void* y, long y_pitch, long y_stride, const void* uv, long uv_pitch, long uv_stride,
+                                            int F, int H, int W, int fmt, const unsigned char* labels,
+                                            const unsigned short* palette_yuv, int a256, int contour,
+                                            void* out_y, long out_y_pitch, long out_y_stride,
+                                            void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream) {
+  MDQE_REQUIRE(a256 >= 0 && a256 <= 256 && contour >= 0 && contour <= 3);
+  MDQE_REQUIRE(F >= 0 && H > 0 && W > 0 && f_off >= 0 && (fmt == 0 || fmt == 1));
+  const long bps = fmt ? 2 : 1, yb = bps * W, cb = bps * 2 * ((W + 1L) / 2), CH = (H + 1L) / 2;
+  MDQE_REQUIRE(y_pitch >= yb && uv_pitch >= cb && y_stride >= 0 && uv_stride >= 0);
+  MDQE_REQUIRE(out_y_pitch >= yb && out_uv_pitch >= cb && out_y_stride >= 0 && out_uv_stride >= 0);
+  if (fmt == 1)
+    MDQE_REQUIRE(((y_pitch | y_stride | uv_pitch | uv_stride | out_y_pitch | out_y_stride | out_uv_pitch | out_uv_stride) & 1L) == 0);
+  // (two output surfaces that shared bytes would have two writers)
+  if (F > 1) MDQE_REQUIRE(out_y_stride >= (H - 1) * out_y_pitch + yb && out_uv_stride >= (CH - 1) * out_uv_pitch + cb);
+  MDQE_REQUIRE((long)F * H * W < 0x7FFFFFFFL);                       // the block index of one call is 32-bit
+  if (F == 0) return MDQE_OK;
+  MDQE_CHECK_PTR(y);
+  MDQE_CHECK_PTR(uv);
+  MDQE_CHECK_PTR(labels);
+  MDQE_CHECK_PTR(palette_yuv);
+  MDQE_CHECK_PTR(out_y);
+  MDQE_CHECK_PTR(out_uv);
+  MDQE_REQUIRE(((uintptr_t)palette_yuv & 1u) == 0);
+  if (fmt == 1) MDQE_REQUIRE((((uintptr_t)y | (uintptr_t)uv | (uintptr_t)out_y | (uintptr_t)out_uv) & 1u) == 0);
+  unsigned char* oy = (unsigned char*)out_y + (long)f_off * out_y_stride;
+  unsigned char* ouv = (unsigned char*)out_uv + (long)f_off * out_uv_stride;
+  {
+    // in place (an output plane IS its input plane: same address, pitch and stride) or apart; nothing else is a function of the inputs
+    const Plane sy = plane_of(y, y_pitch, y_stride, F, H, yb), sc = plane_of(uv, uv_pitch, uv_stride, F, CH, cb);
+    const Plane ty = plane_of(oy, out_y_pitch, out_y_stride, F, H, yb), tc = plane_of(ouv, out_uv_pitch, out_uv_stride, F, CH, cb);
+    const Plane sl = plane_of(labels, W, (long)H * W, F, H, W), sp = plane_of(palette_yuv, 6, 0, 1, 256, 6);
+    const bool same_y = oy == (const unsigned char*)y && out_y_pitch == y_pitch && (F == 1 || out_y_stride == y_stride);
+    const bool same_c = ouv == (const unsigned char*)uv && out_uv_pitch == uv_pitch && (F == 1 || out_uv_stride == uv_stride);
+    MDQE_REQUIRE(same_y || apart(sy, ty));
+    MDQE_REQUIRE(same_c || apart(sc, tc));
+    MDQE_REQUIRE(apart(sy, tc) && apart(sc, ty) && apart(ty, tc));
+    MDQE_REQUIRE(apart(sl, ty) && apart(sl, tc) && apart(sp, ty) && apart(sp, tc));
+  }
+  // the widest form every address of the launch is aligned for (strides matter only between surfaces)
+  uintptr_t m = (uintptr_t)y | (uintptr_t)uv | (uintptr_t)oy | (uintptr_t)ouv | (uintptr_t)labels | (uintptr_t)W
+              | (uintptr_t)y_pitch | (uintptr_t)uv_pitch | (uintptr_t)out_y_pitch | (uintptr_t)out_uv_pitch;
+  if (F > 1) m |= (uintptr_t)y_stride | (uintptr_t)uv_stride | (uintptr_t)out_y_stride | (uintptr_t)out_uv_stride | (uintptr_t)((long)H * W);
+  const int px = (m & 15u) == 0 && contour == 0 ? 16 : ((m & 3u) == 0 ? 4 : 2);
+  RenderYuvArgs a;
+  a.y = (const unsigned char*)y;
+  a.uv = (const unsigned char*)uv;
+  a.labels = labels;
+  a.palette = palette_yuv;
+  a.oy = oy;
+  a.ouv = ouv;
+  a.y_pitch = y_pitch; a.y_stride = y_stride; a.uv_pitch = uv_pitch; a.uv_stride = uv_stride;
+  a.oy_pitch = out_y_pitch; a.oy_stride = out_y_stride; a.ouv_pitch = out_uv_pitch; a.ouv_stride = out_uv_stride;
+  a.H = H; a.W = W;
+  a.XU = (unsigned)((W + px - 1) / px);
+  a.RP = (unsigned)CH;
+  a.n_units = (unsigned)F * a.RP * a.XU;                             // <= F * H * W < 2^31
+  a.a256 = (uint32_t)a256;
+  mdqe_clear_error();
+  const dim3 grid((a.n_units + 255u) / 256u);
+  if (fmt == 0) launch_render_yuv<0>(px, contour, grid, (hipStream_t)stream, a);
+  else launch_render_yuv<1>(px, contour, grid, (hipStream_t)stream, a);
+  return mdqe_launch_status();
+}

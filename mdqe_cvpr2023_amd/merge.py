@@ -28,12 +28,13 @@ class Forms:
     plane_geometry: bool = False          # boxes and areas of the planes ...
     label_geometry: bool = False          # ... and of the labels' visible regions
     early_always: bool = False            # model.rle_output: the early path even with model.early_masks off, with or without planes
+    surface: bool = False                 # the overlay is painted onto the decoder surfaces handed in: a YuvFrames, not RGB pixels
 
     @classmethod
-    def _of(cls, model, geometry, planes, labels, overlay, early_always=False):
+    def _of(cls, model, geometry, planes, labels, overlay, early_always=False, surface=False):
         """geometry None: the model's flag.  It describes the planes where there are planes, and the labels' regions where the map is returned."""
         g = bool(getattr(model, "geometry_output", False) if geometry is None else geometry)
-        return cls(planes, labels, overlay, g and planes is not None, g and labels, early_always)
+        return cls(planes, labels, overlay, g and planes is not None, g and labels, early_always, bool(overlay and surface))
 
     @classmethod
     def of_model(cls, model, emit_masks=True, geometry=None):
@@ -41,13 +42,14 @@ class Forms:
         if not emit_masks:
             return cls()
         lab, rle = getattr(model, "label_output", False), bool(getattr(model, "rle_output", False))
-        return cls._of(model, geometry, None if lab == "only" else "rle" if rle else "dense", bool(lab), bool(getattr(model, "overlay_output", False)), rle)
+        pic = getattr(model, "overlay_output", False)
+        return cls._of(model, geometry, None if lab == "only" else "rle" if rle else "dense", bool(lab), bool(pic), rle, pic == "surface")
 
     @classmethod
-    def of_emit(cls, emit, geometry=False, model=None):
-        """Online ("masks" | "rle" | "labels" | "overlay")."""
+    def of_emit(cls, emit, geometry=False, model=None, surface=False):
+        """Online ("masks" | "rle" | "labels" | "overlay"; surface: the overlay onto the surfaces pushed)."""
         lab = emit in ("labels", "overlay")
-        return cls._of(model, geometry, None if lab else {"masks": "dense", "rle": "rle"}[emit], lab, emit == "overlay")
+        return cls._of(model, geometry, None if lab else {"masks": "dense", "rle": "rle"}[emit], lab, emit == "overlay", surface=surface)
 
 
 def dense_masks(m, idx, stride, frame_hw, out_size, geometry, out, f_off):
@@ -149,16 +151,26 @@ class FrameStore:
     `resize_on_device`), on the device, as chunks in video order -- one per push of an online session, one for a whole offline video.
     `pieces(f0, f1)` answers "frames [f0, f1)" with a list of (tensor [k, 3, h0, w0], first frame) that tile the range; a range that
     spans two chunks comes back as two pieces.  `drop_before(f)` forgets the chunks that lie wholly before frame f, so what a session
-    holds is bounded by its schedule: the frames no window has emitted yet, plus less than one push."""
+    holds is bounded by its schedule: the frames no window has emitted yet, plus less than one push.
+    A chunk may also be a preprocess.YuvFrames, the decoder surfaces themselves (1.5 bytes per pixel for NV12 instead of 3): what a
+    surface overlay paints on.  A piece is then a YuvFrames of k surfaces; `surface` remembers the kind of the first such chunk
+    (YuvFrames.meta()) and every later one must be of that kind."""
 
     def __init__(self):
-        self.chunks = []                          # [first frame, tensor [n, 3, h0, w0], upload event or None, owned]
+        self.chunks = []                          # [first frame, tensor [n, 3, h0, w0] or YuvFrames, upload event or None, owned]
+        self.surface = None                       # (height, width, fmt, matrix, full_range, order) of the first YuvFrames chunk
 
     def add(self, first, frames, ready=None, owned=True):
         """`ready`: the event behind the chunk's upload (None: the frames are there for the current stream; an event is recorded on
         it).  owned=False: the tensor may be the CALLER's memory (frames that arrived on the device are not copied), which `own()`
         replaces by a copy if it is still held."""
-        if int(frames.shape[0]):
+        if not torch.is_tensor(frames):           # decoder surfaces
+            if self.surface is None:
+                self.surface = frames.meta()
+            elif frames.meta() != self.surface:
+                raise ValueError("overlay: surfaces of (height, width, fmt, matrix, full_range, order) = %s follow surfaces of %s; one "
+                                 "video's surfaces are of one kind (start another session for another stream)" % (frames.meta(), self.surface))
+        if len(frames):
             if ready is None and frames.is_cuda:
                 ready = torch.cuda.Event()
                 ready.record(torch.cuda.current_stream(frames.device))
@@ -166,10 +178,10 @@ class FrameStore:
 
     @property
     def frames_held(self):
-        return sum(int(c[1].shape[0]) for c in self.chunks)
+        return sum(len(c[1]) for c in self.chunks)
 
     def drop_before(self, f):
-        self.chunks = [c for c in self.chunks if c[0] + int(c[1].shape[0]) > f]
+        self.chunks = [c for c in self.chunks if c[0] + len(c[1]) > f]
 
     def own(self):
         """Before control returns to the caller: a chunk that stays and may alias the caller's buffer is copied (the caller may refill it)."""
@@ -187,14 +199,14 @@ class FrameStore:
         resize that replaced the tensor, which waited for the whole upload).  The explicit wait costs nothing and does not lean on that."""
         out = []
         for first, t, ready, _ in self.chunks:
-            a, b = max(f0, first), min(f1, first + int(t.shape[0]))
+            a, b = max(f0, first), min(f1, first + len(t))
             if a < b:
                 if stream is not None:
                     if ready is not None:
                         stream.wait_event(ready)
                     t.record_stream(stream)
                 out.append((t[a - first:b - first], a))
-        if sum(int(t.shape[0]) for t, _ in out) != f1 - f0:
+        if sum(len(t) for t, _ in out) != f1 - f0:
             raise RuntimeError("overlay: the frame store does not hold frames [%d, %d)" % (f0, f1))
         return out
 
@@ -203,15 +215,43 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
     """A window's overlay: the label map of window logits m [n, F, Hm, Wm] into labels[l_off:l_off + F] (`label_maps`: all n rows
     compete, as in every label path), then that map painted over video frames [f0, f0 + F) of `source` (a FrameStore) into
     out[o_off:o_off + F] (uint8 [>= o_off + F, Ho, Wo, 3], device) in `style` (render.Style) -- one ops.render_overlay launch per
-    contiguous piece of source frames, on the stream the label map runs on (the current one).  -> `label_maps`' geometry table or None."""
+    contiguous piece of source frames, on the stream the label map runs on (the current one).  A surface picture (`out` a device
+    YuvFrames; the pieces are then the surfaces handed in, of the output size): painted in the YUV domain, one
+    ops.render_overlay_yuv launch per piece, with the palette in the surfaces' samples.  -> `label_maps`' geometry table or None."""
     from . import ops
     geom = label_maps(m, stride, frame_hw, out_size, geometry, labels, l_off)
     nf = int(m.shape[1])
-    pal = style.palette_on(m.device)
+    surface = not torch.is_tensor(out)
+    pal = style.palette_yuv_on(m.device, *out.meta()[2:]) if surface else style.palette_on(m.device)
     for t, first in source.pieces(int(f0), int(f0) + nf, stream=torch.cuda.current_stream(m.device)):
-        k, d = int(t.shape[0]), first - int(f0)
-        ops.render_overlay(labels[l_off + d:l_off + d + k], t, pal, out, o_off + d, style.a256, style.contour)
+        k, d = len(t), first - int(f0)
+        if surface:
+            ops.render_overlay_yuv(labels[l_off + d:l_off + d + k], t, pal, out, o_off + d, style.a256, style.contour)
+        else:
+            ops.render_overlay(labels[l_off + d:l_off + d + k], t, pal, out, o_off + d, style.a256, style.contour)
     return geom
+
+
+def surface_kind(source, out_size):
+    """What a surface overlay paints on: the kind (YuvFrames.meta()) of the surfaces `source` (a FrameStore) holds, which must be of the
+    output size (None: not looked at) -- the painting kernel does not resample.  Raises the two refusals of the form."""
+    if source is None or source.surface is None:
+        raise ValueError("surface overlay: the video's frames are RGB tensors; it paints onto decoder surfaces -- hand the video in as a "
+                         "preprocess.YuvFrames, or ask for the RGB picture (overlay_output = True, online: surface=False)")
+    h, w, fmt, matrix, full_range, order = source.surface
+    if out_size is not None and (h, w) != (int(out_size[0]), int(out_size[1])):
+        raise ValueError("surface overlay: the output size (height, width) = %s is not the surfaces' %s, and surfaces are painted at their "
+                         "own size; ask for height=%d, width=%d (to run the model below that size, hand in full-size surfaces and set "
+                         "model.resize_on_device)" % ((int(out_size[0]), int(out_size[1])), (h, w), h, w))
+    return source.surface
+
+
+def surface_picture(source, n, out_size, device, pitch_align=1, pin_memory=False):
+    """The buffer of a surface overlay: n fresh surfaces of `surface_kind(source, out_size)`."""
+    from .preprocess import YuvFrames
+    h, w, fmt, matrix, full_range, order = surface_kind(source, out_size)
+    return YuvFrames.empty(n, h, w, fmt=fmt, device=device, pitch_align=pitch_align, pin_memory=pin_memory, matrix=matrix,
+                           full_range=full_range, order=order)
 
 
 def rle_positions(m, idx, stride, frame_hw, out_size, geometry):
@@ -363,7 +403,8 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
     (`build_window`; planes: the selected tracks only) into whole-video device buffers, one copy at the end; model.rle_output: the
     planes are then encoded on the host.  `score` (OverlapTables): the counts gathered at every flush on any path -> "pred_gt".
     "pred_label_map": uint8 [L, Ho, Wo], host; label t + 1 = tracker row t, 0 = background, so pred_label_map == pred_track_ids[j] + 1
-    is output j's exclusive region.  "pred_overlay": uint8 [L, Ho, Wo, 3], pinned host."""
+    is output j's exclusive region.  "pred_overlay": uint8 [L, Ho, Wo, 3], pinned host; with forms.surface a YuvFrames of
+    L painted surfaces (pinned host, tight pitch)."""
     if forms is None:
         forms = Forms.of_model(model, emit_masks)
         forms = dataclasses.replace(forms, overlay=forms.overlay and frame_source is not None)
@@ -387,7 +428,9 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
         plane_geoms, label_geoms, u8 = [], [], dict(dtype=torch.uint8, device=model.device)
         # (the windows tile [0, n_frames): every row of the map and the picture is written; a track's planes start at its first window)
         d_lab = torch.empty(n_frames, Ho, Wo, **u8) if forms.labels or forms.overlay else None
-        d_pic = torch.empty(n_frames, Ho, Wo, 3, **u8) if forms.overlay else None
+        d_pic = torch.empty(n_frames, Ho, Wo, 3, **u8) if forms.overlay and not forms.surface else None
+        if forms.surface:
+            d_pic = surface_picture(frame_source, n_frames, out_size, model.device)
         d_planes = torch.zeros(len(sel), n_frames, Ho, Wo, **u8) if forms.planes else None
         sel_dev = torch.tensor(sel, dtype=torch.int32, device=model.device) if forms.planes else None
         for f_off, m in windows:
@@ -401,7 +444,11 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
                 plane_geoms.append((f_off, nf, cnt, pg))
         # one D2H each into pinned memory (pageable copies run at a fraction of PCIe), one sync behind them
         for k, t in (("overlay", d_pic), ("labels", d_lab if forms.labels else None), ("planes", d_planes)):
-            if t is not None:
+            if t is not None and not torch.is_tensor(t):           # a surface picture: both planes
+                host[k] = surface_picture(frame_source, n_frames, out_size, "cpu", pin_memory=True)
+                host[k].y.copy_(t.y, non_blocking=True)
+                host[k].uv.copy_(t.uv, non_blocking=True)
+            elif t is not None:
                 host[k] = torch.empty(t.shape, dtype=torch.uint8, pin_memory=True)
                 host[k].copy_(t, non_blocking=True)
         torch.cuda.current_stream(model.device).synchronize()
@@ -438,7 +485,7 @@ class ClipMerger:
     EARLY_TRACKS = 48                       # tracks per video the early-mask path budgets pinned memory for
 
     def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True, online=None, geometry=None, frame_source=None,
-                 style=None, ground_truth=None):
+                 style=None, ground_truth=None, surface=False, surface_pitch_align=1):
         self.model, self.frame_hw, self.out_size, self.mask_hw = model, frame_hw, out_size, mask_hw
         self.emit_masks = emit_masks                # False: scores / labels only (ranks > 0 of a sharded video)
         # online ("masks" | "rle" | "labels" | "overlay"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their
@@ -446,7 +493,9 @@ class ClipMerger:
         # logits nor a host buffer stay here (n_frames is unknown)
         self.online = online
         # the forms of this video, for every path (geometry None: model.geometry_output; online sessions pass theirs)
-        self.forms = forms = Forms.of_emit(online, geometry, model) if online else Forms.of_model(model, emit_masks, geometry)
+        # (surface, surface_pitch_align: an online session's; offline the model's overlay_output == "surface", at a tight pitch)
+        self.forms = forms = Forms.of_emit(online, geometry, model, surface) if online else Forms.of_model(model, emit_masks, geometry)
+        self.surface_pitch_align = surface_pitch_align
         self.geometry = forms.plane_geometry or forms.label_geometry
         # False | True | "only" (model.label_output): the label map next to -- or, "only", instead of -- the per-track planes
         self.labels = False if online else forms.labels and ("only" if forms.planes is None else True)
@@ -564,7 +613,9 @@ class ClipMerger:
         forms, u8 = self.forms, dict(dtype=torch.uint8, device=self.dev)
         n, nf, Ho, Wo = int(m.shape[0]), int(m.shape[1]), int(self.out_size[0]), int(self.out_size[1])
         lab = torch.empty(nf, Ho, Wo, **u8) if forms.labels or forms.overlay else None    # (an overlay alone: a scratch, not copied)
-        pic = torch.empty(nf, Ho, Wo, 3, **u8) if forms.overlay else None
+        pic = torch.empty(nf, Ho, Wo, 3, **u8) if forms.overlay and not forms.surface else None
+        if forms.surface:                           # (the host's pitch: the window copy is then two plain copies, padding and all)
+            pic = surface_picture(self.frame_source, nf, self.out_size, self.dev, self.surface_pitch_align)
         rows = torch.arange(n, dtype=torch.int32, device=self.dev) if n and forms.planes else None
         planes = torch.empty(n, nf, Ho, Wo, **u8) if rows is not None and forms.planes == "dense" else None
         copies = {"labels": (pairs("labels", lab) if forms.labels else []) + (pairs("overlay", pic) if forms.overlay else []),
@@ -597,6 +648,10 @@ class ClipMerger:
                     if f0 > 0:
                         early.hosts[-1][:f0].zero_()
                 return [(h[f0:f0 + nf], d) for h, d in zip(early.hosts, buf)]
+            if not torch.is_tensor(buf):            # a surface picture: ONE pinned YuvFrames of L surfaces per video, both planes
+                if early.overlay is None:
+                    early.overlay = surface_picture(self.frame_source, shape[0], self.out_size, "cpu", pin_memory=True)
+                return [(early.overlay.y[f0:f0 + nf], buf.y), (early.overlay.uv[f0:f0 + nf], buf.uv)]
             if getattr(early, kind) is None:
                 setattr(early, kind, model.pinned_mask_buffer(shape + (3,) * (kind == "overlay")))
             return [(getattr(early, kind)[f0:f0 + nf], buf)]
@@ -619,6 +674,9 @@ class ClipMerger:
             rec["masks"] = torch.zeros((0, nf) + out_size, dtype=torch.bool)
 
         def pairs(kind, buf):                       # fresh pinned buffers, the record's
+            if not torch.is_tensor(buf):            # a surface picture: pinned surfaces of the same pitch, both planes
+                host = rec["overlay"] = surface_picture(self.frame_source, nf, out_size, "cpu", self.surface_pitch_align, pin_memory=True)
+                return [(host.y, buf.y), (host.uv, buf.uv)]
             host = self.model.pinned_mask_buffer(tuple(buf.shape))
             rec.update({"masks": host.view(torch.bool)} if kind == "planes" else {kind: host})
             return [(host, buf)]

@@ -113,6 +113,10 @@ class MDQE(nn.Module):
         # the frames'; ops.render_overlay behind ops.final_label_map, 3 bytes per pixel however many tracks) and "pred_track_ids".  The map
         # itself is returned only with label_output.  `overlay_style` (render.Style): alpha, contour reach, palette.  Videos only (the COCO
         # image branch has no overlay), one device (sharding.py refuses it).  False: nothing changes.  (Properties: see below.)
+        # "surface": for a video handed in as decoder surfaces (preprocess.YuvFrames) "pred_overlay" is a YuvFrames of L PAINTED SURFACES
+        # of the same format (pinned host, tight pitch), painted in the YUV domain (ops.render_overlay_yuv): a background pixel keeps the
+        # decoder's bits, 1.5 bytes per pixel are kept and read back instead of 3, and the result goes to an encoder as it is.  The
+        # output size must be the surfaces' (nothing is resampled); RGB frames are refused.
         self.overlay_output = False
         self.merge_on_cpu = None                    # None: cfg.merge_on_cpu (MODEL.MDQE.MERGE_ON_CPU); True / False override it
         # Final masks of a tracker window leave the device when the window is flushed (pinned host buffers, copied under the later
@@ -279,8 +283,8 @@ class MDQE(nn.Module):
 
     @overlay_output.setter
     def overlay_output(self, value):
-        if value is not False and value is not True:
-            raise ValueError("overlay_output must be False or True, got %r" % (value,))
+        if value is not False and value is not True and not (isinstance(value, str) and value == "surface"):
+            raise ValueError("overlay_output must be False, True or 'surface', got %r" % (value,))
         if value:
             self.check_label_capacity()
         self.__dict__["_overlay_output"] = value
@@ -846,15 +850,18 @@ class MDQE(nn.Module):
                 events.append((b, ev))
         return dev, events
 
-    def convert_surfaces(self, yuv):
+    def convert_surfaces(self, yuv, keep=False):
         """Decoder surfaces (preprocess.YuvFrames) -> uint8 [n, 3, height, width] on the model's device, visible to the current stream.
         Host planes go up as they are -- the rows the picture uses at their pitch: for NV12 at a tight pitch half an RGB upload -- on the copy
-        stream; the current stream waits for them and converts (preprocess.yuv_to_rgb: one launch)."""
+        stream; the current stream waits for them and converts (preprocess.yuv_to_rgb: one launch).  keep: -> (that tensor, the
+        surfaces on the device -- what a surface overlay paints on --, whether an upload made them: else they are the caller's planes)."""
         from .preprocess import yuv_to_rgb
         if len(yuv) == 0:
             raise RuntimeError("MDQE: a video needs at least one frame")
         if self.device.type != "cuda":
-            return yuv_to_rgb(yuv).to(self.device)
+            rgb = yuv_to_rgb(yuv).to(self.device)
+            return (rgb, yuv, False) if keep else rgb
+        uploaded = yuv.device != self.device
         if not yuv.y.is_cuda:
             if self._copy_stream is None:
                 self._copy_stream = torch.cuda.Stream(self.device)
@@ -866,7 +873,7 @@ class MDQE(nn.Module):
             cur.wait_stream(cs)
         elif yuv.device != self.device:
             yuv = yuv.to(self.device)
-        return yuv_to_rgb(yuv)
+        return (yuv_to_rgb(yuv), yuv, uploaded) if keep else yuv_to_rgb(yuv)
 
     def to_device_frames(self, imgs):
         """All frames on the device, visible to the current stream."""
@@ -880,11 +887,18 @@ class MDQE(nn.Module):
         (the mapper's eval augmentation) needs the whole upload."""
         return self._frames_and_source(video)[:4]
 
-    def _frames_and_source(self, video):
+    def _frames_and_source(self, video, surface=None):
         """`_frames_for` and, behind it, the frames as uploaded -- before the device-side resize, what an overlay is painted on -- with
-        the event behind their upload (None: nothing was in flight) and whether an upload made them (else they may be the caller's tensor)."""
+        the event behind their upload (None: nothing was in flight) and whether an upload made them (else they may be the caller's tensor).
+        surface (None: overlay_output == "surface"): the source of decoder surfaces is the surfaces themselves on the device, not the
+        converted frames (those are then nobody's to keep once the per-frame stages have read them)."""
         from .preprocess import YuvFrames
-        if isinstance(video["image"], YuvFrames):
+        if surface is None:
+            surface = self.overlay_output == "surface"
+        if isinstance(video["image"], YuvFrames) and surface:
+            frames_dev, src, uploaded = self.convert_surfaces(video["image"], keep=True)
+            h2d = src_ready = None
+        elif isinstance(video["image"], YuvFrames):
             # decoder surfaces: from here the converted tensor is what an uploaded uint8 RGB tensor would have been (and the model's own)
             frames_dev, h2d = self.convert_surfaces(video["image"]), None
             src, src_ready, uploaded = frames_dev, None, True
@@ -916,12 +930,15 @@ class MDQE(nn.Module):
             raise ValueError("ground_truth: it holds %d frames, the video %d" % (gt.length, int(n_frames)))
         return gt
 
-    def _frame_source(self, src, src_ready):
-        """The whole video as the frame source of an overlay (merge.FrameStore), or None with overlay_output off."""
+    def _frame_source(self, src, src_ready, out_size=None):
+        """The whole video as the frame source of an overlay (merge.FrameStore), or None with overlay_output off.  overlay_output =
+        "surface": refused here, before anything of the video runs, for RGB frames and for an output size that is not the surfaces'."""
         if not self.overlay_output:
             return None
         store = merge.FrameStore()
         store.add(0, src, src_ready)
+        if self.overlay_output == "surface":
+            merge.surface_kind(store, out_size)
         return store
 
     def inference_vis(self, batched_inputs, trace=None):
@@ -936,7 +953,7 @@ class MDQE(nn.Module):
         clips = self.clip_schedule(L, cfg.n_frames_test, cfg.clip_stride)
         gt = self._ground_truth(video, out_size, L)
         return self.merge_clips(self.iter_clip_results(frames_dev, clips, 0, trace, h2d=h2d), (h, w), out_size,
-                                (geo.Hp // ms, geo.Wp // ms), n_frames=L, frame_source=self._frame_source(src, src_ready), ground_truth=gt)
+                                (geo.Hp // ms, geo.Wp // ms), n_frames=L, frame_source=self._frame_source(src, src_ready, out_size), ground_truth=gt)
 
     def forward_stream(self, batches):
         """An eval loop over videos: yields `forward(b)` for every b of the iterable `batches`, in order, bit-identical to
@@ -955,8 +972,8 @@ class MDQE(nn.Module):
             video = b[0]
             frames_dev, h2d, h0, w0, src, src_ready, _ = self._frames_and_source(video)
             L, h, w = frames_dev.shape[0], int(frames_dev.shape[-2]), int(frames_dev.shape[-1])
-            st = {"done_frames": False, "out_size": (video.get("height", h0), video.get("width", w0)), "hw": (h, w), "L": L,
-                  "source": self._frame_source(src, src_ready)}
+            st = {"done_frames": False, "out_size": (video.get("height", h0), video.get("width", w0)), "hw": (h, w), "L": L}
+            st["source"] = self._frame_source(src, src_ready, st["out_size"])
             st["gt"] = self._ground_truth(video, st["out_size"], L)
             geo = self.engine.geometry(h, w)
             st["mask_hw"] = (geo.Hp // cfg.match_stride, geo.Wp // cfg.match_stride)
@@ -1013,7 +1030,8 @@ class MDQE(nn.Module):
         while state["cur"] is not None:
             yield guarded(step)
 
-    def online_video(self, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None):
+    def online_video(self, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None,
+                     surface=False, surface_pitch_align=1):
         """An online session over ONE video whose frames arrive in pushes (a camera, a stream, a video too long to hold): push()
         returns each tracker window as soon as it is final, close() the rest, result() the video-level scores / labels / tracks.
         height / width: output mask size (default: the frame size); emit: "masks" (bool [n, F, H, W] per window), "rle" or "labels" (one
@@ -1022,9 +1040,12 @@ class MDQE(nn.Module):
         result() also carries forward()'s "pred_masks" / "pred_rles" / "pred_label_map" / "pred_overlay", bit-identical; geometry: every
         window carries `boxes` / `areas` of its final masks and result() "pred_boxes" / "pred_areas" (with or without keep), equal to
         forward()'s with geometry_output; ground_truth (vis_score.GroundTruth): result() carries "pred_gt", forward()'s with the input's
-        "ground_truth" (a push past its length raises).  See online.py."""
+        "ground_truth" (a push past its length raises); surface (with emit="overlay", pushes of preprocess.YuvFrames): `win.overlay` is
+        a YuvFrames of painted surfaces of the pushed format instead of RGB pixels (surface_pitch_align: its row pitch in bytes is
+        rounded up to a multiple of it).  See online.py."""
         from .online import OnlineVideo
-        return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep, geometry=geometry, style=style, ground_truth=ground_truth)
+        return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep, geometry=geometry, style=style, ground_truth=ground_truth,
+                           surface=surface, surface_pitch_align=surface_pitch_align)
 
     def inference_image(self, batched_inputs):
         """COCO single-image branch: MDQE.forward :213-236 -> mdqe.forward (models/mdqe.py:62-70) -> decoder
@@ -1038,6 +1059,9 @@ class MDQE(nn.Module):
         item = batched_inputs[0]
         if item.get("ground_truth") is not None:
             raise ValueError("ground_truth: the COCO image branch is not scored (video IoU and the YTVIS table are for videos)")
+        if getattr(self, "overlay_output", False) == "surface":
+            raise ValueError("overlay_output = 'surface': the COCO image branch has no overlay (painted surfaces are a video output: use a "
+                             "video config, or set overlay_output = False)")
         from .preprocess import YuvFrames
         if isinstance(item["image"], YuvFrames):
             raise ValueError("YuvFrames: the COCO image branch takes RGB tensors (decoder surfaces are a video input; convert one with "

@@ -37,6 +37,16 @@ up-sample of them -- for a sharp picture push original-size uint8 frames and set
 frames on the device until the windows they belong to are out: after any push `ov.frames_held <= frames not yet emitted + the largest
 push - 1` (whole pushes are dropped), so the store does not grow with the video.  keep=True adds "pred_overlay" [L, H, W, 3] and
 "pred_label_map" to result(), equal to forward()'s with model.overlay_output / label_output.
+
+emit="overlay", surface=True (pushes of preprocess.YuvFrames only): the two ends of a streaming pipeline meet -- decoder surfaces in,
+PAINTED SURFACES of the same format out, painted in the YUV domain on the device (ops.render_overlay_yuv; the rule is in
+include/mdqe_hip.h).  `win.overlay` is a preprocess.YuvFrames on the host (pinned) with f1 - f0 surfaces, carrying the fmt, matrix, range
+and order of the first push; its pitch is tight (width / 2*ceil(width/2) samples) unless surface_pitch_align=k rounds it up to a multiple
+of k bytes, and padding bytes are zero.  A background pixel keeps the decoder's bits exactly (no YUV -> RGB -> YUV round trip), the
+session keeps the pushed surfaces themselves -- 1.5 bytes per pixel for NV12 instead of 3, never the converted RGB frames -- under the
+same `frames_held` bound, and reads 1.5 bytes per pixel back.  The output size must be the surfaces' size (nothing is resampled: to run
+the model below it, push full-size surfaces and set model.resize_on_device).  win.labels is what it is without `surface`; keep=True
+makes result()["pred_overlay"] one YuvFrames of L surfaces, equal to forward()'s with model.overlay_output = "surface".
 """
 import contextlib
 import dataclasses
@@ -123,7 +133,7 @@ class Window:
     ymax+1] in output pixels, zeros for an empty mask) and areas int64 [n, f1-f0] of those masks.  With emit="labels": `labels`, uint8
     [f1-f0, H, W] on the host (track_ids[i] + 1 where track i owns the pixel, 0 = background), masks and rles None, boxes / areas those
     of the labels' visible regions.  With emit="overlay": `labels` as above and `overlay`, uint8 [f1-f0, H, W, 3] on the host, the
-    frames with that map painted on.  (`labels` and `overlay` are init-only pseudo-fields stored as plain attributes:
+    frames with that map painted on -- or, in a surface=True session, a preprocess.YuvFrames of f1-f0 painted surfaces.  (`labels` and `overlay` are init-only pseudo-fields stored as plain attributes:
     dataclasses.fields(Window) is what it was.)"""
     frames: tuple
     track_ids: list
@@ -141,9 +151,20 @@ class Window:
 
 
 class OnlineVideo:
-    def __init__(self, model, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None):
+    def __init__(self, model, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None,
+                 surface=False, surface_pitch_align=1):
         if emit not in ("masks", "rle", "labels", "overlay"):
             raise ValueError("online_video: emit must be 'masks', 'rle', 'labels' or 'overlay'")
+        if not isinstance(surface, bool):
+            raise ValueError("online_video: surface must be a bool, got %r" % (surface,))
+        if surface and emit != "overlay":
+            raise ValueError("online_video: surface=True is the form of an overlay and goes with emit='overlay' (got emit=%r)" % (emit,))
+        k = surface_pitch_align
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or (k != 1 and not surface):
+            raise ValueError("online_video: surface_pitch_align must be an int >= 1 (bytes) and goes with surface=True, got %r" % (k,))
+        if surface and model.cfg.is_coco:
+            raise ValueError("online_video: surface=True with a COCO image config: painted surfaces are a video output (use a video config)")
+        self.surface, self.surface_pitch_align = surface, int(k)
         if emit in ("labels", "overlay"):
             model.check_label_capacity()
         from .render import Style
@@ -197,16 +218,21 @@ class OnlineVideo:
     def _start(self, frames_dev, h0, w0):
         from .meta_arch import ClipMerger
         model, cfg = self.model, self.model.cfg
+        self.out_size = (int(self.height if self.height is not None else h0), int(self.width if self.width is not None else w0))
+        if self.surface and self.out_size != (int(h0), int(w0)):
+            raise ValueError("online_video: surface=True paints the surfaces at their own size %s, the session's output size (height, "
+                             "width) is %s; ask for height=%d, width=%d (to run the model below that size, push full-size surfaces and "
+                             "set model.resize_on_device)" % ((int(h0), int(w0)), self.out_size, h0, w0))
         h, w = int(frames_dev.shape[-2]), int(frames_dev.shape[-1])
         self.hw = (h, w)
         self.geo = model.engine.geometry(h, w)
-        self.out_size = (int(self.height if self.height is not None else h0), int(self.width if self.width is not None else w0))
         self.mask_hw = (self.geo.Hp // cfg.match_stride, self.geo.Wp // cfg.match_stride)
         if self.emit == "overlay":
             from .merge import FrameStore
             self.store = FrameStore()
         self.merger = ClipMerger(model, self.hw, self.out_size, self.mask_hw, n_frames=None, online=self.emit,
-                                 geometry=self.geometry, frame_source=self.store, style=self.style, ground_truth=self.ground_truth)
+                                 geometry=self.geometry, frame_source=self.store, style=self.style, ground_truth=self.ground_truth,
+                                 surface=self.surface, surface_pitch_align=self.surface_pitch_align)
         shapes = model.engine.cache_shapes(self.geo)
         per_frame = 4 * sum(int(np.prod(sh)) for sh in shapes.values())
         forced = int(os.environ.get("MDQE_CACHE_FRAMES", "0"))
@@ -261,12 +287,20 @@ class OnlineVideo:
         if self.ground_truth is not None and self.received + n > self.ground_truth.length:
             raise RuntimeError("online_video: this push brings the video to %d frames, the ground truth holds %d"
                                % (self.received + n, self.ground_truth.length))
+        if self.surface:
+            from .preprocess import YuvFrames
+            if not isinstance(frames, YuvFrames):
+                raise ValueError("online_video: a surface=True session paints onto decoder surfaces and takes pushes of "
+                                 "preprocess.YuvFrames, got %s (for RGB frames open the session with surface=False)" % type(frames).__name__)
         hw0 = self._hw(frames)
         if self.in_hw is not None and hw0 != self.in_hw:
             raise RuntimeError("online_video: frame size %s differs from the first push's %s" % (hw0, self.in_hw))
+        if self.surface and self.store is not None and self.store.surface is not None and frames.meta() != self.store.surface:
+            raise ValueError("online_video: this push's surfaces are (height, width, fmt, matrix, full_range, order) = %s, the first "
+                             "push's %s; one session's surfaces are of one kind" % (frames.meta(), self.store.surface))
         with self._ctx():
             model = self.model
-            frames_dev, h2d, h0, w0, src, src_ready, uploaded = model._frames_and_source({"image": frames})
+            frames_dev, h2d, h0, w0, src, src_ready, uploaded = model._frames_and_source({"image": frames}, surface=self.surface)
             if self.merger is None:
                 self.in_hw = hw0
                 self._start(frames_dev, h0, w0)
@@ -321,7 +355,11 @@ class OnlineVideo:
         if self.keep and forms.labels:
             res["pred_label_map"] = torch.cat([w.labels for w in self.kept])
             if forms.overlay:
-                res["pred_overlay"] = torch.cat([w.overlay for w in self.kept])
+                if self.surface:
+                    from .preprocess import YuvFrames
+                    res["pred_overlay"] = YuvFrames.cat([w.overlay for w in self.kept])
+                else:
+                    res["pred_overlay"] = torch.cat([w.overlay for w in self.kept])
         elif self.keep:
             wins = [(w.frames[0], w.frames[1] - w.frames[0], len(w.track_ids), w.rles if forms.planes == "rle" else w.masks) for w in self.kept]
             if forms.planes == "rle":

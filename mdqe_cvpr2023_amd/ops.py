@@ -674,6 +674,89 @@ def render_overlay(labels, frames, palette, out, f_off=0, a256=128, contour=1):
     return out
 
 
+def render_overlay_yuv(labels, yuv, palette_yuv, out=None, f_off=0, a256=128, contour=1):
+    """A label map painted straight onto decoder surfaces: out[f_off + f] (a preprocess.YuvFrames of yuv's size and fmt with >= f_off
+    + F surfaces, its own pitches; None: F fresh surfaces at a tight pitch) from labels (uint8 [F, H, W], contiguous, at the surfaces'
+    own size), yuv (a YuvFrames of F surfaces) and palette_yuv (uint16 [256, 3], rows (Y, U, V) in sample units: render.palette_yuv).
+    Luma follows ops.render_overlay's rule per sample; a chroma pair is the rounded mean of its block's painted pixels; a background
+    pixel keeps the decoder's bits (P010: all 16 of a word): the integer rule of include/mdqe_hip.h, mdqe_render_overlay_yuv420sp.
+    `out` may be `yuv` itself (in place), nothing else that overlaps it.  On a HIP device one launch on the current stream; on host
+    planes the same rule in torch integers.  -> out."""
+    from .preprocess import YUV_FORMATS, YuvFrames, _pitch_stride
+    if not isinstance(yuv, YuvFrames):
+        raise RuntimeError("render_overlay_yuv: yuv must be a preprocess.YuvFrames, got %s" % type(yuv).__name__)
+    F, H, W = len(yuv), yuv.height, yuv.width
+    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or tuple(labels.shape) != (F, H, W) or not labels.is_contiguous():
+        raise RuntimeError("render_overlay_yuv: labels must be contiguous uint8 [F = %d, H = %d, W = %d] (the surfaces' own size)" % (F, H, W))
+    if not isinstance(a256, int) or not isinstance(contour, int) or not 0 <= a256 <= 256 or not 0 <= contour <= 3:
+        raise RuntimeError("render_overlay_yuv: a256 must be an int in 0..256 and contour an int in 0..3, got %r, %r" % (a256, contour))
+    if F * H * W >= 2 ** 31 - 1:
+        raise RuntimeError("render_overlay_yuv: F*H*W must stay below 2^31 - 1, got %s" % ((F, H, W),))
+    if (not torch.is_tensor(palette_yuv) or palette_yuv.dtype not in (torch.uint16, torch.int16) or tuple(palette_yuv.shape) != (256, 3)
+            or not palette_yuv.is_contiguous()):
+        raise RuntimeError("render_overlay_yuv: palette_yuv must be contiguous uint16 [256, 3] (render.palette_yuv)")
+    if out is None:
+        out = YuvFrames.empty(f_off + F, H, W, fmt=yuv.fmt, device=yuv.device, matrix=yuv.matrix, full_range=yuv.full_range, order=yuv.order)
+    if (not isinstance(out, YuvFrames) or (out.height, out.width, out.fmt) != (H, W, yuv.fmt) or not isinstance(f_off, int) or f_off < 0
+            or f_off + F > len(out)):
+        raise RuntimeError("render_overlay_yuv: out must be a YuvFrames of >= f_off + F = %d surfaces of %d x %d %s" % (f_off + F, H, W, yuv.fmt))
+    for t, name in ((labels, "labels"), (palette_yuv, "palette_yuv"), (out, "out")):
+        if t.device != yuv.device:
+            raise RuntimeError("render_overlay_yuv: %s must be on the surfaces' device %s, got %s" % (name, yuv.device, t.device))
+    if yuv.is_cuda:
+        (yp, ys), (cp, cs) = _pitch_stride(yuv.y), _pitch_stride(yuv.uv)
+        (oyp, oys), (ocp, ocs) = _pitch_stride(out.y), _pitch_stride(out.uv)
+        with torch.cuda.device(yuv.device):
+            check(lib.mdqe_render_overlay_yuv420sp(ptr(yuv.y), yp, ys, ptr(yuv.uv), cp, cs, F, H, W, YUV_FORMATS.index(yuv.fmt), ptr(labels),
+                                                   ptr(palette_yuv), a256, contour, ptr(out.y), oyp, oys, ptr(out.uv), ocp, ocs, f_off,
+                                                   cur_stream(yuv.device)), "render_overlay_yuv")
+        return out
+    if F == 0:
+        return out
+    # host planes: the rule of the header in torch integers
+    p010 = yuv.fmt == "p010"
+    ch, cw = (H + 1) // 2, (W + 1) // 2
+
+    def raw(t):
+        v = t.to(torch.int64)
+        return v & 0xFFFF if p010 else v
+
+    def store(dst, word):
+        dst.copy_(((word + 0x8000) & 0xFFFF) - 0x8000 if p010 else word)
+
+    lab = labels.to(torch.int64)
+    edge = torch.zeros(lab.shape, dtype=torch.bool)
+    for d in range(1, contour + 1):
+        if d < H:
+            edge[:, d:] |= lab[:, d:] != lab[:, :-d]
+            edge[:, :-d] |= lab[:, :-d] != lab[:, d:]
+        if d < W:
+            edge[:, :, d:] |= lab[:, :, d:] != lab[:, :, :-d]
+            edge[:, :, :-d] |= lab[:, :, :-d] != lab[:, :, d:]
+    col = (palette_yuv.view(torch.int16).to(torch.int64) & (0x3FF if p010 else 0xFF))[lab]          # [F, H, W, 3]
+    bg = lab == 0
+
+    def px(s, p):
+        return torch.where(bg, s, torch.where(edge, p, (s * (256 - a256) + p * a256 + 128) >> 8))
+    ry = raw(yuv.y[:, :H, :W])
+    yo = px(ry >> 6 if p010 else ry, col[..., 0])
+    store(out.y[f_off:f_off + F, :H, :W], torch.where(bg, ry, yo << 6 if p010 else yo))
+    rc = raw(yuv.uv[:, :ch, :2 * cw]).reshape(F, ch, cw, 2)
+    c = (rc >> 6 if p010 else rc).repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)[:, :H, :W]
+
+    def blocks(t):                                  # [F, H, W] -> the sum over each 2 x 2 block's in-picture pixels, [F, ch, cw]
+        full = torch.zeros((F, 2 * ch, 2 * cw), dtype=torch.int64)
+        full[:, :H, :W] = t
+        return full.reshape(F, ch, 2, cw, 2).sum((2, 4))
+    n = blocks(torch.ones((F, H, W), dtype=torch.int64))
+    sh = n >> 1                                     # n = 1, 2, 4: n / 2 = log2(n) = 0, 1, 2
+    keep = blocks((~bg).to(torch.int64)) == 0
+    oc = torch.stack([(blocks(px(c[..., k], col[..., k + 1])) + sh) >> sh for k in (0, 1)], -1)
+    word = torch.where(keep[..., None], rc, oc << 6 if p010 else oc)
+    store(out.uv[f_off:f_off + F, :ch, :2 * cw], word.reshape(F, ch, 2 * cw))
+    return out
+
+
 def layernorm_post(x, gamma, beta, post, eps=1e-5, out=None):
     """out = LN(x)*gamma + beta + post."""
     _chk(x, "x"); _chk(post, "post")

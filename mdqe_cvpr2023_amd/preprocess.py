@@ -155,12 +155,54 @@ class YuvFrames:
                              % (buf.shape[1], chroma_row, ch, chroma_row + ch))
         return cls(buf[:, :int(height)], buf[:, int(chroma_row):int(chroma_row) + ch], height, width, **kw)
 
+    @classmethod
+    def empty(cls, n, height, width, fmt="nv12", device="cpu", pitch_align=1, pin_memory=False, **kw):
+        """n fresh surfaces, each plane an allocation of its own: luma [n, height, pitch], chroma [n, ceil(height/2), pitch_uv], the
+        pitches tight (width and 2*ceil(width/2) samples) or, with pitch_align=k, rounded up to a multiple of k BYTES.  The samples
+        are uninitialised; where a pitch leaves padding the plane is zero-filled.  (k = 1: tight for either format.)"""
+        if fmt not in YUV_FORMATS:
+            raise ValueError("YuvFrames: fmt must be one of %s, got %r" % (YUV_FORMATS, fmt))
+        es = 1 if fmt == "nv12" else 2
+        k = pitch_align
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or (k > 1 and k % es):
+            raise ValueError("YuvFrames: pitch_align must be an int >= 1 in bytes%s, got %r" % (", even for p010" if es == 2 else "", k))
+        planes = []
+        for rows, samples in ((int(height), int(width)), ((int(height) + 1) // 2, 2 * ((int(width) + 1) // 2))):
+            pitch = (samples * es + k - 1) // k * k // es
+            make = torch.zeros if pitch > samples else torch.empty
+            planes.append(make((int(n), rows, pitch), dtype=torch.uint8 if es == 1 else torch.int16, device=device,
+                               pin_memory=bool(pin_memory)))
+        return cls(planes[0], planes[1], height, width, fmt=fmt, **kw)
+
+    @classmethod
+    def cat(cls, parts):
+        """Surfaces of one kind (size, fmt, matrix, range, order) in a row -> one YuvFrames (the planes are concatenated: a copy)."""
+        parts = list(parts)
+        if not parts or any(not isinstance(p, YuvFrames) or p.meta() != parts[0].meta() for p in parts):
+            raise ValueError("YuvFrames.cat: expected one or more YuvFrames of the same size, fmt, matrix, range and order")
+        return parts[0]._like(torch.cat([p.y for p in parts]), torch.cat([p.uv for p in parts]))
+
+    def meta(self):
+        """What the planes do not say: (height, width, fmt, matrix, full_range, order)."""
+        return (self.height, self.width, self.fmt, self.matrix, self.full_range, self.order)
+
     def __len__(self):
         return int(self.y.shape[0])
 
     @property
     def device(self):
         return self.y.device
+
+    @property
+    def is_cuda(self):
+        return self.y.is_cuda
+
+    def clone(self):
+        return self._like(self.y.clone(), self.uv.clone())
+
+    def record_stream(self, stream):
+        self.y.record_stream(stream)
+        self.uv.record_stream(stream)
 
     def __getitem__(self, s):
         if not isinstance(s, slice):

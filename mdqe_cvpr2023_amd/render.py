@@ -32,6 +32,42 @@ def default_palette():
     return torch.tensor([_label_colour(i) for i in range(256)], dtype=torch.uint8)
 
 
+# RGB (0..255) -> YUV samples, the table of `palette_yuv`: (fmt, matrix, full_range) -> (yo, co, (ar, ag, ab), (ur, ug, ub), (vr, vg, vb)).
+# rint(x * 65536) of the standard forward matrices, the inverses of the header's MDQE_YUV_COEFFS: luma row (Kr, Kg, Kb) times 219/255,
+# 876/255, 1 or 1023/255; chroma rows (-Kr, -Kg, 1 - Kb) / (2 (1 - Kb)) and (1 - Kr, -Kg, -Kb) / (2 (1 - Kr)) times 224/255, 896/255, 1
+# or 1023/255.  The G entry takes the rounding residue: a luma row sums to the rounded scale, a chroma row to 0, so a grey has exactly
+# neutral chroma and black / white land on the nominal codes.
+YUV_FORWARD = {
+    ("nv12", "bt601", False): (16, 128, (16829, 33039, 6416), (-9714, -19070, 28784), (28784, -24103, -4681)),
+    ("nv12", "bt601", True): (0, 128, (19595, 38470, 7471), (-11058, -21710, 32768), (32768, -27439, -5329)),
+    ("nv12", "bt709", False): (16, 128, (11966, 40254, 4064), (-6596, -22188, 28784), (28784, -26145, -2639)),
+    ("nv12", "bt709", True): (0, 128, (13933, 46871, 4732), (-7509, -25259, 32768), (32768, -29763, -3005)),
+    ("p010", "bt601", False): (64, 512, (67315, 132155, 25665), (-38856, -76282, 115138), (115138, -96414, -18724)),
+    ("p010", "bt601", True): (0, 512, (78612, 154331, 29972), (-44363, -87095, 131458), (131458, -110080, -21378)),
+    ("p010", "bt709", False): (64, 512, (47864, 161016, 16255), (-26383, -88755, 115138), (115138, -104581, -10557)),
+    ("p010", "bt709", True): (0, 512, (55896, 188037, 18982), (-30123, -101335, 131458), (131458, -119404, -12054)),
+}
+
+
+def palette_yuv(palette_rgb, fmt="nv12", matrix="bt709", full_range=False, order="rgb"):
+    """An overlay palette (uint8 [256, 3], rows in the frames' channel order `order`: "rgb" or "bgr") in the samples of a decoder
+    surface: uint16 [256, 3] on the host, rows (Y, U, V), 0..255 for "nv12" and 0..1023 for "p010" -- what ops.render_overlay_yuv
+    paints with.  Integers only: Y = yo + ((ar*R + ag*G + ab*B + 32768) >> 16); U, V = co + ((.. + 32768) >> 16) with the arithmetic
+    shift (floor), clamped to the sample range (YUV_FORWARD)."""
+    if not torch.is_tensor(palette_rgb) or palette_rgb.dtype != torch.uint8 or tuple(palette_rgb.shape) != (256, 3):
+        raise ValueError("palette_yuv: palette_rgb must be a uint8 [256, 3] tensor")
+    if (fmt, matrix, full_range) not in YUV_FORWARD or not isinstance(full_range, bool) or order not in ("rgb", "bgr"):
+        raise ValueError("palette_yuv: fmt 'nv12' / 'p010', matrix 'bt601' / 'bt709', full_range a bool, order 'rgb' / 'bgr'; got %r"
+                         % ((fmt, matrix, full_range, order),))
+    yo, co, ky, ku, kv = YUV_FORWARD[(fmt, matrix, full_range)]
+    top = 255 if fmt == "nv12" else 1023
+    p = palette_rgb.cpu().to(torch.int64)
+    r, g, b = (p[:, 0], p[:, 1], p[:, 2]) if order == "rgb" else (p[:, 2], p[:, 1], p[:, 0])
+    rows = [yo + ((ky[0] * r + ky[1] * g + ky[2] * b + 32768) >> 16)]
+    rows += [(co + ((k[0] * r + k[1] * g + k[2] * b + 32768) >> 16)).clamp(0, top) for k in (ku, kv)]
+    return torch.stack(rows, 1).to(torch.uint16)
+
+
 @dataclasses.dataclass
 class Style:
     """alpha: weight of the track colour inside a region, 0..1 (the kernel blends with a256 = round(alpha * 256) in 1/256 steps);
@@ -62,5 +98,16 @@ class Style:
             pal = default_palette() if self.palette is None else self.palette
             cache[key] = pal.contiguous().to(device)
             if cache[key].is_cuda:                 # later windows read it on other streams: the one upload is complete before it is handed out
+                torch.cuda.current_stream(cache[key].device).synchronize()
+        return cache[key]
+
+    def palette_yuv_on(self, device, fmt, matrix, full_range, order):
+        """`palette_yuv` of the palette on `device` (cached per device and kind of surface, as `palette_on` is)."""
+        cache = self.__dict__.setdefault("_yuv_on", {})
+        key = (str(device), fmt, matrix, bool(full_range), order)
+        if key not in cache:
+            pal = default_palette() if self.palette is None else self.palette
+            cache[key] = palette_yuv(pal, fmt, matrix, bool(full_range), order).contiguous().to(device)
+            if cache[key].is_cuda:
                 torch.cuda.current_stream(cache[key].device).synchronize()
         return cache[key]

@@ -1,0 +1,289 @@
+"""Overlays painted onto decoder surfaces on the device: the kernel (mdqe_render_overlay_yuv420sp through ops.render_overlay_yuv) against
+the numpy oracle (tests/_overlay_yuv_ref.py), its exact properties, and the model's surfaces above it -- an online surface=True session
+against the op applied to the pushed surfaces and the session's own label maps, against a plain overlay session, and against forward()
+with overlay_output = "surface".  Integers only: every comparison is exact, there is no tolerance.
+
+Kernel cases: per (shape, format) ONE content (P010 words with random low 6 bits), one label map (blobs that touch the row ends, the odd
+last row / column and the 16-pixel block borders, plus salt noise, labels 0..255), a random palette, and the 20 references (contour 0..3
+x a256 in {0, 1, 128, 255, 256}).  The content is packed into three layouts: the tight pitch with the chroma plane right behind the luma
+rows; a pitch padded to the next multiple of 16 bytes with surfaces two rows further apart than they need (F = 3 with strides larger than
+a surface); and that layout entered one sample late, which forces the per-sample form.  In the first two (16, 64) and (9, 96) take the
+16-byte form at contour 0 and the 4-byte form with a contour, (6, 36) the 4-byte form.  The output is an allocation of its own of
+F + 2 surfaces in the same layout, written at f_off = 1 and filled with a sentinel: padding, the two guard surfaces and the rows
+between the planes must come back untouched, and so must the input allocation."""
+import dataclasses
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import _overlay_yuv_ref as REF  # noqa: E402
+import _yuv_ref as YREF  # noqa: E402
+
+SHAPES = [(1, 1), (2, 2), (3, 5), (7, 9), (6, 36), (5, 37), (16, 64), (9, 96)]
+F = 3
+SENTINEL = 0xCD
+
+
+def _typed(a, fmt):
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    return t if fmt == "nv12" else t.view(torch.int16)
+
+
+def _raw(t, fmt):
+    a = t.cpu().contiguous().numpy()
+    return a if fmt == "nv12" else a.view(np.uint16)
+
+
+def _palette(seed, fmt):
+    rng = np.random.default_rng(seed)
+    pal = rng.integers(0, 256 if fmt == "nv12" else 1024, size=(256, 3)).astype(np.int64)
+    pal[255] = 255 if fmt == "nv12" else 1023                         # (the top of the range, on the blob that touches the last pixel)
+    return pal, torch.from_numpy(pal.astype(np.uint16))
+
+
+def _layouts(H, W, fmt):
+    """(pitch bytes, chroma_row, extra_rows, lead bytes)."""
+    tight, es = YREF.tight_pitch(W, fmt), 1 if fmt == "nv12" else 2
+    padded = (tight // 16 + 1) * 16
+    return [(tight, H, 0, 0), (padded, H + 1, 2, 0), (padded, H + 1, 2, es)]
+
+
+def _frames(flat, n, H, W, fmt, pitch, crow, rows, lead):
+    from mdqe_cvpr2023_amd.preprocess import YuvFrames
+    return YuvFrames(*YREF.plane_views(flat, n, H, W, fmt, pitch, crow, rows, lead), H, W, fmt=fmt)
+
+
+@pytest.mark.parametrize("fmt", ["nv12", "p010"])
+@pytest.mark.parametrize("H,W", SHAPES)
+def test_kernel_equals_the_reference(H, W, fmt):
+    from mdqe_cvpr2023_amd import ops
+    ys, cs = YREF.make_content(H * 1000 + W, F, H, W, fmt)
+    lab = REF.make_labels(H * 7 + W, F, H, W)
+    pal_np, pal = _palette(H + W, fmt)
+    want = {(r, a): REF.paint(ys, cs, lab, pal_np, fmt, a, r) for r in range(4) for a in (0, 1, 128, 255, 256)}
+    lab_dev, pal_dev = torch.from_numpy(lab).cuda(), pal.cuda()
+    launches = 0
+    for pitch, crow, extra, lead in _layouts(H, W, fmt):
+        flat, rows = YREF.pack(ys, cs, fmt, pitch, crow, extra, lead)
+        host = torch.from_numpy(flat)
+        dev = host.cuda()
+        src = _frames(dev, F, H, W, fmt, pitch, crow, rows, lead)
+        blank = torch.full((lead + (F + 2) * rows * pitch,), SENTINEL, dtype=torch.uint8)
+        for (r, a), (wy, wc) in want.items():
+            expect = blank.clone()
+            e = _frames(expect, F + 2, H, W, fmt, pitch, crow, rows, lead)
+            e.y[1:1 + F, :, :W] = _typed(wy, fmt)
+            e.uv[1:1 + F, :, :wc.shape[2]] = _typed(wc, fmt)
+            out_flat = blank.cuda()
+            out = _frames(out_flat, F + 2, H, W, fmt, pitch, crow, rows, lead)
+            got = ops.render_overlay_yuv(lab_dev, src, pal_dev, out, 1, a, r)
+            assert got is out
+            assert torch.equal(out_flat.cpu(), expect), (pitch, crow, extra, lead, r, a)
+            launches += 1
+        assert torch.equal(dev.cpu(), host), (pitch, crow, extra, lead)   # the input allocation, padding included, is unchanged
+    assert launches == 3 * 20
+    # the output the wrapper allocates itself (tight); one surface; no surface
+    wy, wc = want[(1, 128)]
+    got = ops.render_overlay_yuv(lab_dev, src, pal_dev)
+    assert got.is_cuda and len(got) == F and got.meta() == src.meta() and np.array_equal(_raw(got.y, fmt), wy) and np.array_equal(_raw(got.uv, fmt), wc)
+    one = ops.render_overlay_yuv(lab_dev[1:2], src[1:2], pal_dev)
+    assert np.array_equal(_raw(one.y, fmt), wy[1:2]) and np.array_equal(_raw(one.uv, fmt), wc[1:2])
+    assert len(ops.render_overlay_yuv(lab_dev[3:], src[3:], pal_dev)) == 0
+    # in place: the output planes ARE the input planes
+    mine = _frames(host.cuda(), F, H, W, fmt, pitch, crow, rows, lead)
+    assert ops.render_overlay_yuv(lab_dev, mine, pal_dev, mine, 0, 128, 1) is mine
+    assert np.array_equal(_raw(mine.y[:, :, :W], fmt), wy) and np.array_equal(_raw(mine.uv[:, :, :wc.shape[2]], fmt), wc)
+
+
+@pytest.mark.parametrize("fmt", ["nv12", "p010"])
+@pytest.mark.parametrize("H,W", [(7, 9), (16, 64), (9, 96)])
+def test_properties(H, W, fmt):
+    from mdqe_cvpr2023_amd import ops
+    from mdqe_cvpr2023_amd.preprocess import YuvFrames
+    ys, cs = YREF.make_content(H * 31 + W, F, H, W, fmt)
+    pal_np, pal = _palette(3, fmt)
+    pal_dev = pal.cuda()
+    src = YuvFrames(_typed(ys, fmt).cuda(), _typed(cs, fmt).cuda(), H, W, fmt=fmt)
+
+    def run(lab, a256, contour):
+        out = ops.render_overlay_yuv(torch.from_numpy(lab).cuda(), src, pal_dev, a256=a256, contour=contour)
+        return _raw(out.y, fmt), _raw(out.uv, fmt)
+    # an all-zero map returns the surfaces bit for bit, the low bits of P010 words included
+    zero = np.zeros((F, H, W), dtype=np.uint8)
+    for contour in range(4):
+        for a256 in (0, 128, 256):
+            oy, oc = run(zero, a256, contour)
+            assert np.array_equal(oy, ys) and np.array_equal(oc, cs), (contour, a256)
+    if fmt == "p010":
+        assert int((ys & 0x3F).max()) > 0 and int((cs & 0x3F).max()) > 0
+    # a map that is zero outside a box: luma outside the box and every chroma pair whose block lies outside it are unchanged
+    full = REF.make_labels(H + W, F, H, W)
+    full[full == 0] = 7
+    for r0, r1, c0, c1 in ((1, H - 2, 1, W - 3), (0, 3, W - 5, W), (H - 1, H, 0, W), (2, 5, 3, 4)):
+        lab = np.zeros_like(full)
+        lab[:, r0:r1, c0:c1] = full[:, r0:r1, c0:c1]
+        for contour in (0, 3):
+            oy, oc = run(lab, 200, contour)
+            outside = np.ones((H, W), dtype=bool)
+            outside[r0:r1, c0:c1] = False
+            assert np.array_equal(oy[:, outside], ys[:, outside])
+            assert not np.array_equal(oy, ys)
+            blocks = np.ones(((H + 1) // 2, (W + 1) // 2), dtype=bool)                # blocks without a pixel of the box
+            blocks[r0 // 2:(r1 + 1) // 2, c0 // 2:(c1 + 1) // 2] = False
+            pairs = np.repeat(blocks, 2, axis=1)
+            assert np.array_equal(oc[:, pairs], cs[:, pairs])
+            wy, wc = REF.paint(ys, cs, lab, pal_np, fmt, 200, contour)
+            assert np.array_equal(oy, wy) and np.array_equal(oc, wc)
+    # a256 = 0, contour = 0: the identity on NV12 whatever the labels (P010: on the values; painted words lose their low bits)
+    oy, oc = run(full, 0, 0)
+    if fmt == "nv12":
+        assert np.array_equal(oy, ys) and np.array_equal(oc, cs)
+    else:
+        assert np.array_equal(oy >> 6, ys >> 6) and np.array_equal(oc >> 6, cs >> 6) and not np.array_equal(oy, ys)
+
+
+# ---- the model -----------------------------------------------------------------------------------------------------------------------
+def _model(**kw):
+    from mdqe_cvpr2023_amd.config import PRESETS
+    from mdqe_cvpr2023_amd.meta_arch import MDQE
+    from mdqe_cvpr2023_amd.params import random_state
+    cfg = dataclasses.replace(PRESETS["R50_ovis_360"], **kw)
+    return cfg, MDQE(cfg, state_dict=random_state(cfg, seed=3)).eval()
+
+
+@pytest.fixture(scope="module")
+def small():
+    return _model(n_frames_window_test=6)
+
+
+L, SIZE = 17, (96, 160)
+
+
+def _surfaces(h, w, fmt, pitch, crow, device, **kw):
+    """The synthetic video as decoder surfaces (as tests/test_yuv_gpu.py makes them): luma from its green plane, chroma from its
+    sub-sampled red and blue planes, in ONE allocation of [L, crow + ceil(h/2) + 2, pitch] with poison padding."""
+    from bench import synth_video
+    from mdqe_cvpr2023_amd.preprocess import YuvFrames
+    v = synth_video(0, L, seed=1, h=h, w=w, n_obj=4).numpy().astype(np.int64)
+    ys = v[:, 1]
+    cs = np.stack([v[:, 0, ::2, ::2], v[:, 2, ::2, ::2]], -1).reshape(L, (h + 1) // 2, -1)
+    if fmt == "p010":
+        ys, cs = (ys << 8) | 0x2A, (cs << 8) | 0x15                 # (8-bit values in the top byte, something in the low 6 bits)
+    dt = np.uint8 if fmt == "nv12" else np.uint16
+    flat, rows = YREF.pack(ys.astype(dt), cs.astype(dt), fmt, pitch, crow, extra_rows=2)
+    t = torch.from_numpy(flat)
+    t = t if fmt == "nv12" else t.view(torch.int16)
+    buf = t.view(L, rows, -1).to(device)
+    return YuvFrames.from_surface(buf, h, w, crow, fmt=fmt, **kw)
+
+
+def _session(model, feed, pushes, **kw):
+    """-> (windows, result, worst frames_held - (frames not yet emitted + largest push - 1))."""
+    ov = model.online_video(emit="overlay", keep=True, **kw)
+    wins, at, emitted, slack = [], 0, 0, -10 ** 9
+    for n in pushes:
+        got = ov.push(feed[at:at + n])
+        at += n
+        wins += got
+        emitted = wins[-1].frames[1] if wins else 0
+        slack = max(slack, ov.frames_held - ((at - emitted) + max(pushes) - 1))
+    assert at == L
+    wins += ov.close()
+    assert ov.frames_held == 0
+    return wins, ov.result(), slack
+
+
+def _check_windows(model, wins, s, style, pitch_align=1):
+    """Every window's overlay is the op applied to the pushed surfaces and the window's own label map; -> painted pixels in all."""
+    from mdqe_cvpr2023_amd import ops
+    from mdqe_cvpr2023_amd.preprocess import YuvFrames
+    h, w = s.height, s.width
+    es = 1 if s.fmt == "nv12" else 2
+    pal = style.palette_yuv_on(model.device, s.fmt, s.matrix, s.full_range, s.order)
+    dev = s if s.is_cuda else s.to(model.device)
+    painted = 0
+    for win in wins:
+        f0, f1 = win.frames
+        pic = win.overlay
+        assert isinstance(pic, YuvFrames) and not pic.is_cuda and len(pic) == f1 - f0 and pic.meta() == s.meta()
+        assert pic.y.is_pinned() and pic.uv.is_pinned()
+        for t, samples in ((pic.y, w), (pic.uv, 2 * ((w + 1) // 2))):
+            assert t.shape[2] * es == (samples * es + pitch_align - 1) // pitch_align * pitch_align       # tight, or rounded up
+            assert not bool(t[:, :, samples:].any())                                                    # padding bytes are zero
+        assert tuple(win.labels.shape) == (f1 - f0, h, w) and win.labels.dtype == torch.uint8
+        want = ops.render_overlay_yuv(win.labels.to(model.device), dev[f0:f1], pal, None, 0, style.a256, style.contour)
+        assert torch.equal(pic.y[:, :, :w], want.y.cpu()) and torch.equal(pic.uv[:, :, :want.uv.shape[2]], want.uv.cpu()), win.frames
+        painted += int((win.labels != 0).sum())
+    return painted
+
+
+def test_online_surface_session_equals_the_op_a_plain_session_and_forward(small):
+    from mdqe_cvpr2023_amd.preprocess import YuvFrames
+    from mdqe_cvpr2023_amd.render import Style
+    cfg, model = small
+    s = _surfaces(96, 160, "nv12", 256, 128, "cuda", matrix="bt601", full_range=True, order="bgr")
+    before = s.y.clone(), s.uv.clone()
+    pushes = (5, 3, 7, 2)                                              # uneven pushes; windows of 6 span two and three of them
+    wy, ry, slack = _session(model, s, pushes, surface=True)
+    assert slack <= 0                                                 # frames_held <= frames not yet emitted + the largest push - 1
+    assert [w.frames for w in wy] == [(0, 6), (6, 12), (12, 17)]
+    assert _check_windows(model, wy, s, Style()) > 0
+    assert torch.equal(s.y, before[0]) and torch.equal(s.uv, before[1])                 # the caller's surfaces are not painted on
+    # a plain overlay session on the same surfaces: the same windows in everything but the picture's form
+    wr, rr, _ = _session(model, s, pushes)
+    assert len(wr) == len(wy)
+    for a, b in zip(wy, wr):
+        assert a.frames == b.frames and a.track_ids == b.track_ids and torch.equal(a.cls_probs, b.cls_probs) and torch.equal(a.labels, b.labels)
+        assert torch.is_tensor(b.overlay) and tuple(b.overlay.shape) == (a.frames[1] - a.frames[0],) + SIZE + (3,)
+    assert {k: v for k, v in ry.items() if k != "pred_overlay"}.keys() == {k: v for k, v in rr.items() if k != "pred_overlay"}.keys()
+    assert ry["pred_scores"] == rr["pred_scores"] and ry["pred_track_ids"] == rr["pred_track_ids"] and torch.equal(ry["pred_label_map"], rr["pred_label_map"])
+    # result() against forward() with overlay_output = "surface" (device surfaces, then host surfaces through forward_stream)
+    pic = ry["pred_overlay"]
+    assert isinstance(pic, YuvFrames) and len(pic) == L and pic.meta() == s.meta() and tuple(pic.y.shape) == (L,) + SIZE
+    model.overlay_output, model.label_output = "surface", True
+    try:
+        ref = model([{"image": s}])
+        sh = _surfaces(96, 160, "nv12", 160, 96, "cpu", matrix="bt601", full_range=True, order="bgr")
+        streamed = list(model.forward_stream([[{"image": sh}]]))[0]
+        model.early_masks = False                                     # the late path: whole-video device buffers, one copy at the end
+        late = model([{"image": s}])
+        with pytest.raises(ValueError, match="resize_on_device"):     # an output size that is not the surfaces'
+            model([{"image": s, "height": 90, "width": 150}])
+        with pytest.raises(ValueError, match="preprocess.YuvFrames"):   # a video of RGB tensors
+            model([{"image": torch.zeros(L, 3, 96, 160, dtype=torch.uint8)}])
+    finally:
+        model.overlay_output, model.label_output, model.early_masks = False, False, True
+    for other in (ref, streamed, late):
+        got = other["pred_overlay"]
+        assert isinstance(got, YuvFrames) and got.meta() == s.meta()
+        assert torch.equal(got.y, pic.y) and torch.equal(got.uv, pic.uv)
+        assert torch.equal(other["pred_label_map"], ry["pred_label_map"]) and other["pred_scores"] == ry["pred_scores"]
+    # refusals that need a session on the device
+    ov = model.online_video(height=90, width=150, emit="overlay", surface=True)
+    with pytest.raises(ValueError, match="resize_on_device"):
+        ov.push(s[:5])
+
+
+def test_online_surface_session_on_p010_host_surfaces_with_a_padded_pitch(small):
+    from mdqe_cvpr2023_amd.render import Style
+    cfg, model = small
+    s = _surfaces(96, 160, "p010", 512, 96, "cpu")
+    style = Style(alpha=0.25, contour=2)
+    wins, res, slack = _session(model, s, (4, 9, 4), surface=True, surface_pitch_align=256, style=style)
+    assert slack <= 0 and [w.frames for w in wins] == [(0, 6), (6, 12), (12, 17)]
+    assert _check_windows(model, wins, s, style, pitch_align=256) > 0
+    pic = res["pred_overlay"]
+    assert len(pic) == L and tuple(pic.y.shape) == (L, 96, 256) and tuple(pic.uv.shape) == (L, 48, 256)
+    # background words keep all 16 bits: the low bits this video carries in every word
+    bg = torch.cat([w.labels for w in wins]) == 0
+    assert bool(bg.any()) and torch.equal(pic.y[:, :, :160][bg], s.y[:, :96, :160][bg])
+    assert bool(((pic.y[:, :, :160][bg] & 0x3F) == 0x2A).all())
