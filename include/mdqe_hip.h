@@ -583,6 +583,47 @@ int mdqe_render_overlay_yuv420sp(const void* y, long y_pitch, long y_stride, con
                                  void* out_y, long out_y_pitch, long out_y_stride,
                                  void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream);
 
+/* The mosaic overlay (csrc/render_mosaic.hip): the two painters above with a PER-LABEL action, one of them a redaction mosaic.  Every
+ * argument the two entries share with mdqe_render_overlay_u8 / mdqe_render_overlay_yuv420sp means what it means there; new are
+ *   action  uint8 [256], device: action[l] is what happens to a pixel of label l -- 0 keep, 1 tint, 2 mosaic (any other value: undefined);
+ *           action[0] is the background's;
+ *   cell    the side of a mosaic cell in pixels, even, 2..64.
+ * Integers only, ONE definition:
+ *   edge    exactly mdqe_render_overlay_u8's definition on the LABELS, whatever the actions are;
+ *   cells   cell x cell squares of the output grid anchored at (0, 0): pixel (Y, X) lies in cell (Y / cell, X / cell); the cells at the
+ *           right and at the bottom are smaller.  mean_c(cell) = (sum s_c + n / 2) / n, integer division, the sum over ALL n in-picture
+ *           pixels of the cell whatever their labels (64 * 64 * 1023 < 2^31).  A mosaic pixel therefore carries nothing finer than its
+ *           cell, and a thin mask does not change what the cell shows;
+ *   RGB     s_c is mdqe_render_overlay_u8's source value (nearest-sampled, float32 by the rint / clamp / NaN rule, no frames: 0).  With l the
+ *           pixel's label:  action 0: out_c = s_c;
+ *                           action 1: out_c = palette[l][c] if edge, else (s_c*(256 - a256) + palette[l][c]*a256 + 128) >> 8;
+ *                           action 2: out_c = mean_c(cell of (Y, X));
+ *   YUV     (values: word >> 6 for P010.)  Luma follows the RGB rule with luma cells of cell x cell.  A chroma cell is the (cell/2) x (cell/2)
+ *           pairs under the same picture area -- chroma position (r, c) lies in cell (r / (cell/2), c / (cell/2)) -- and meanU, meanV are
+ *           taken over its in-picture pairs of the ceil(H/2) x ceil(W/2) chroma plane.  The chroma rule of mdqe_render_overlay_yuv420sp
+ *           stays: Cout = (sum_i px_i + n / 2) >> log2(n) over the n in-picture pixels i of the pair's 2 x 2 block, where px_i is C for
+ *           action 0, the palette or blend value for action 1 and the cell's meanC for action 2 (cell is even: a block never straddles
+ *           cells);
+ *   P010    a luma word whose label has action 0 is copied with all 16 bits, and so is a chroma pair whose block's labels all have
+ *           action 0; every other word is written as value << 6.
+ * With action = {0, 1, 1, ..., 1} both entries are, by this definition, bit-identical to the two entries above.
+ * MDQE_EINVAL for a cell that is odd or outside 2..64; every other check is that of the entry above, made before any pointer is looked
+ * at; F == 0 returns OK and launches nothing.  mdqe_render_mosaic_yuv420sp does NOT paint in place: a cell's mean reads samples that
+ * other threads write, so an output plane that meets an input plane in any way (or the other output plane, the labels, the palette,
+ * the action table) is MDQE_EINVAL.  Alignment: RGB as above (nothing needs to be aligned); surfaces move 4 bytes per access where every
+ * plane pointer (in, out, labels), pitch, stride and W are multiples of 4 bytes, otherwise single samples.  Only cells that hold a
+ * pixel of action 2 are reduced.  One launch, no atomics on global memory: identical from run to run.  Never allocates, never
+ * synchronises. */
+int mdqe_render_mosaic_u8(const void* frames, int is_u8, long frame_stride, int h0, int w0,
+                          const unsigned char* labels, int F, int Ho, int Wo,
+                          const unsigned char* palette, const unsigned char* action, int a256, int contour, int cell,
+                          unsigned char* out, int f_off, void* stream);
+int mdqe_render_mosaic_yuv420sp(const void* y, long y_pitch, long y_stride, const void* uv, long uv_pitch, long uv_stride,
+                                int F, int H, int W, int fmt /*0 nv12, 1 p010*/, const unsigned char* labels,
+                                const unsigned short* palette_yuv, const unsigned char* action, int a256, int contour, int cell,
+                                void* out_y, long out_y_pitch, long out_y_stride,
+                                void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream);
+
 /* ---- COCO single-image branch, after the decoder (MDQE.inference_image, mdqe/mdqe.py:486-556), on the centre frame's
  * low-resolution logits [n,Hm,Wm]; aligned_bilinear x`factor` in closed form, crop [:h,:w].
  * stats[k] = {sum(sigmoid*[sigmoid>0.5]), count(sigmoid>0.5), xmin, ymin, xmax, ymax of (logit > 0)} (:512-516, :526;

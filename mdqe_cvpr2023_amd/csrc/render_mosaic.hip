@@ -1,0 +1,662 @@
+// The mosaic overlay: a label map painted with a PER-LABEL action -- keep the source, tint it as render.hip / render_yuv.hip do, or replace
+// it by the mean of its cell x cell square of the picture (a redaction mosaic).  ONE definition, integers only (include/mdqe_hip.h has the
+// rule); tests/_mosaic_ref.py restates it in numpy with loops over cells and every comparison is exact.
+//
+// A cell's mean needs every sample of the cell, so a thread block owns WHOLE cells: a tile of ny x nx cells of one frame (tile_of: about
+// 16 x 64 pixels for cells up to 16, one or two cells above that, never more than 256 cells), 256 threads, four phases between barriers:
+//   1 flags   every label of the tile is read once (4 at a time where the map and W are multiples of 4 bytes); a pixel whose action is 2
+//             sets its cell's LDS flag (a plain store of 1);
+//   2 sums    only flagged cells are reduced -- a tile that flags nothing skips the phase wave by wave and its source is read once, by
+//             phase 4.  Consecutive lanes are consecutive pixels of a row (cell a multiple of 4: runs of 4 pixels, summed in the lane
+//             first; uint8 frames at the output's size and aligned NV12 rows with one v_sad_u8 per dword); with G the largest power
+//             of two in `cell`, the G (G / 4) lanes of a group lie in one row of one cell (the tile width, 256 and 64 are multiples of
+//             G), so a butterfly of wave shuffles adds them up and the group's first lane adds the result to the cell's LDS counters
+//             (ds_add_u32: integer sums are the same in any order; nothing touches global memory).  Channels 0 and 2 (U and V) ride
+//             in one register: 64 values of at most 1023 stay below 2^16;
+//   3 means   one thread per flagged cell: (sum + n / 2) / n over the n in-picture samples, the one integer division of a cell, packed
+//             into one LDS dword per cell;
+//   4 paint   the painters of render.hip and render_yuv.hip with the action selecting the value.  RGB: groups of 4 pixels laid out from
+//             the OUTPUT address as there (three aligned dword stores per group; a group cut by the tile's side stores its pixels as
+//             bytes), labels and uint8 frames of a whole group read 4 bytes at a time.  Surfaces: a thread owns 2 rows x PX pixels,
+//             PX = 4 with 4-byte (P010: 8-byte) accesses where every pointer, pitch, stride and W are multiples of 4 bytes, else PX = 2
+//             and single samples.  Contour neighbours are looked at for tinted pixels only, straight from the label map (L1).
+// With the mosaic on the background nearly every cell is reduced: the frame is read twice, the second time from L2 (a tile's 3 to 12 KB
+// were touched microseconds before).  No atomics on global memory, no data-dependent order anywhere: identical from run to run.
+// Row and cell indices inside a tile come from multiplications by ceil(2^32 / d) (exact while n * d < 2^32; a tile has fewer than 2^13
+// pixels and d <= 124).
+#include "common.h"
+#include "render_planes.h"
+
+namespace {
+
+constexpr int MAX_CELLS = 256;
+
+struct Tile { int ny, nx; };
+// ny x nx cells: about 16 rows by 64 columns, at least one cell, the width a multiple of 4 (cell is even; an odd count of cells of
+// 4k + 2 pixels gets one more).  cell = 2: 8 x 32 = 256 cells.
+Tile tile_of(int cell) {
+  int ny = 16 / cell, nx = 64 / cell;
+  if (ny < 1) ny = 1;
+  if (nx < 1) nx = 1;
+  if ((nx * cell) & 3) ++nx;
+  return {ny, nx};
+}
+
+uint32_t magic(int d) { return (uint32_t)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }   // d >= 2
+__device__ __forceinline__ int mdiv(int n, uint32_t m) { return (int)__umulhi((uint32_t)n, m); }
+
+struct TileArgs {
+  const unsigned char* labels;   // [F, H, W]
+  const unsigned char* action;   // [256]
+  int H, W;
+  int cell, ny, nx, G;           // G: lanes of a reduction group
+  int TH, TW;                    // ny * cell, nx * cell
+  unsigned tiles_x, tiles_y;
+  uint32_t m_tw, m_cell, m_items, m_htw, m_q;   // magic of TW, cell, items per row (pair), TW / 2, TW / 4
+  int lab4;                      // labels and W are multiples of 4 bytes: a row of a tile is read 4 labels at a time
+  int items;                     // paint items per tile row (RGB) or row pair (surfaces)
+  uint32_t a256;
+};
+
+__device__ __forceinline__ uint32_t ld4(const unsigned char* p) {     // (any alignment)
+  uint32_t v;
+  __builtin_memcpy(&v, p, 4);
+  return v;
+}
+
+// float32 frame value -> 0..255: round half to even, clamp, NaN -> 0 (both comparisons are false for a NaN)
+__device__ __forceinline__ uint32_t to_u8(float v) {
+  const float r = __builtin_rintf(v);
+  return r >= 0.f ? (r > 255.f ? 255u : (uint32_t)r) : 0u;
+}
+
+// edge of the rule: pixel (Y, X) with label l at q has, within R pixels along an axis and inside the picture, a neighbour of another label
+template <int R>
+__device__ __forceinline__ bool edge_at(const unsigned char* q, uint32_t l, int Y, int X, int H, int W) {
+  bool edge = false;
+#pragma unroll
+  for (int d = 1; d <= R; ++d) {
+    if (X - d >= 0) edge |= q[-d] != l;
+    if (X + d < W) edge |= q[d] != l;
+    if (Y - d >= 0) edge |= q[-(long)d * W] != l;
+    if (Y + d < H) edge |= q[(long)d * W] != l;
+  }
+  return edge;
+}
+
+struct TilePos { int f, Y0, X0, th, tw; };                            // frame, origin, in-picture rows and columns of the tile
+
+__device__ __forceinline__ TilePos tile_pos(const TileArgs& a) {
+  unsigned b = blockIdx.x;
+  const unsigned tx = b % a.tiles_x;
+  b /= a.tiles_x;
+  const unsigned ty = b % a.tiles_y;
+  TilePos p;
+  p.f = (int)(b / a.tiles_y);
+  p.Y0 = (int)ty * a.TH;
+  p.X0 = (int)tx * a.TW;
+  p.th = a.H - p.Y0 < a.TH ? a.H - p.Y0 : a.TH;
+  p.tw = a.W - p.X0 < a.TW ? a.W - p.X0 : a.TW;
+  return p;
+}
+
+// phase 1: flag[cell] = 1 where a pixel of the cell has action 2 (between the caller's barriers)
+__device__ __forceinline__ void flag_cells(const TileArgs& a, const TilePos& p, const unsigned char* act, uint32_t* flag) {
+  const unsigned char* lab0 = a.labels + ((long)p.f * a.H + p.Y0) * a.W + p.X0;
+  if (a.lab4) {                                                       // (W and the tile's width are multiples of 4: so is tw)
+    const int Q = a.TW >> 2;
+    for (int i = threadIdx.x; i < p.th * Q; i += 256) {
+      const int r = mdiv(i, a.m_q), c = 4 * (i - r * Q);
+      if (c >= p.tw) continue;
+      const uint32_t l4 = *(const uint32_t*)(lab0 + (long)r * a.W + c);
+      const int cyn = mdiv(r, a.m_cell) * a.nx;
+      // (cell is even: pixels c, c + 1 share a cell and so do c + 2, c + 3)
+      if (act[l4 & 0xFFu] == 2 || act[(l4 >> 8) & 0xFFu] == 2) flag[cyn + mdiv(c, a.m_cell)] = 1u;
+      if (act[(l4 >> 16) & 0xFFu] == 2 || act[l4 >> 24] == 2) flag[cyn + mdiv(c + 2, a.m_cell)] = 1u;
+    }
+    return;
+  }
+  for (int i = threadIdx.x; i < p.th * a.TW; i += 256) {
+    const int r = mdiv(i, a.m_tw), c = i - r * a.TW;
+    if (c < p.tw && act[lab0[(long)r * a.W + c]] == 2) flag[mdiv(r, a.m_cell) * a.nx + mdiv(c, a.m_cell)] = 1u;
+  }
+}
+
+// in-picture rows / columns of cell (cy, cx) of the tile
+__device__ __forceinline__ int cell_extent(int cell, int k, int have) { return have - k * cell < cell ? have - k * cell : cell; }
+
+// ---- RGB ----------------------------------------------------------------------------------------------------------------------------
+struct MosaicArgs {
+  TileArgs t;
+  const void* frames;            // [F, 3, h0, w0] planes, frame stride `frame_stride` elements; unused for KIND 0
+  long frame_stride;
+  long plane;                    // h0 * w0
+  int h0, w0;
+  const unsigned char* palette;  // [256, 3]
+  unsigned char* out;            // at frame f_off already: [F, Ho, Wo, 3]
+  unsigned head;                 // out address mod 4: groups of 4 pixels start at flat pixels = head (mod 4)
+  int ident;
+};
+
+// The source pixel of output pixel (f, Y, X) as c0 | c1 << 8 | c2 << 16.  KIND 0: no frames (black), 1: uint8, 2: float32.
+template <int KIND>
+__device__ __forceinline__ uint32_t source_px(const MosaicArgs& a, int f, int Y, int X) {
+  if (KIND == 0) return 0u;
+  const int sy = a.ident ? Y : (int)((unsigned)Y * (unsigned)a.h0 / (unsigned)a.t.H);
+  const int sx = a.ident ? X : (int)((unsigned)X * (unsigned)a.w0 / (unsigned)a.t.W);
+  const long at = (long)f * a.frame_stride + (long)sy * a.w0 + sx;
+  if (KIND == 1) {
+    const unsigned char* s = (const unsigned char*)a.frames + at;
+    return (uint32_t)s[0] | (uint32_t)s[a.plane] << 8 | (uint32_t)s[2 * a.plane] << 16;
+  }
+  const float* s = (const float*)a.frames + at;
+  return to_u8(s[0]) | to_u8(s[a.plane]) << 8 | to_u8(s[2 * a.plane]) << 16;
+}
+
+// out_c = (s_c * (256 - a) + pal_c * a + 128) >> 8 on a packed pixel, as render.hip's paint: channels 0 and 2 share one multiply
+__device__ __forceinline__ uint32_t tint(uint32_t s, uint32_t pal, bool edge, uint32_t a) {
+  const uint32_t rb = ((s & 0x00FF00FFu) * (256u - a) + (pal & 0x00FF00FFu) * a + 0x00800080u) >> 8 & 0x00FF00FFu;
+  const uint32_t g = (((s >> 8) & 0xFFu) * (256u - a) + ((pal >> 8) & 0xFFu) * a + 128u) & 0xFF00u;
+  return edge ? pal : (rb | g);
+}
+
+template <int KIND, int R>
+__global__ __launch_bounds__(256) void render_mosaic_kernel(const MosaicArgs a) {
+  __shared__ uint32_t pal[256];
+  __shared__ unsigned char act[256];
+  __shared__ uint32_t flag[MAX_CELLS];
+  __shared__ uint32_t sum[3][MAX_CELLS];
+  __shared__ uint32_t mean[MAX_CELLS];
+  const TileArgs& t = a.t;
+  const int tid = (int)threadIdx.x;
+  {
+    const unsigned char* q = a.palette + 3 * tid;
+    pal[tid] = (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16;
+    act[tid] = t.action[tid];
+    flag[tid] = 0u;
+    sum[0][tid] = 0u; sum[1][tid] = 0u; sum[2][tid] = 0u;
+  }
+  __syncthreads();
+  const TilePos p = tile_pos(t);
+  flag_cells(t, p, act, flag);
+  __syncthreads();
+  // sums of the flagged cells.  G >= 4 (cell a multiple of 4): a lane sums 4 consecutive pixels of a row, which share a cell, and a
+  // group is G / 4 lanes; else one pixel per lane, groups of G = 2
+  if (t.G >= 4) {
+    const int Q = t.TW >> 2, GQ = t.G >> 2;
+    for (int i0 = 0; i0 < p.th * Q; i0 += 256) {                     // (the same trip count for every lane: the shuffles need all of them)
+      const int i = i0 + tid;
+      const int r = mdiv(i, t.m_q), c = 4 * (i - r * Q);
+      const int ci = mdiv(r, t.m_cell) * t.nx + mdiv(c, t.m_cell);
+      const bool on = i < p.th * Q && c < p.tw && flag[ci] != 0u;
+      if (!__any(on)) continue;                                       // (uniform over the wave)
+      uint32_t v02 = 0u, v1 = 0u;
+      if (on) {
+        if (KIND == 1 && a.ident && c + 4 <= p.tw) {
+          const unsigned char* q = (const unsigned char*)a.frames + (long)p.f * a.frame_stride + (long)(p.Y0 + r) * a.w0 + p.X0 + c;
+          v02 = __builtin_amdgcn_sad_u8(ld4(q), 0u, 0u) | __builtin_amdgcn_sad_u8(ld4(q + 2 * a.plane), 0u, 0u) << 16;   // byte sums
+          v1 = __builtin_amdgcn_sad_u8(ld4(q + a.plane), 0u, 0u);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (c + k < p.tw) {
+              const uint32_t s = source_px<KIND>(a, p.f, p.Y0 + r, p.X0 + c + k);
+              v02 += s & 0x00FF00FFu; v1 += (s >> 8) & 0xFFu;
+            }
+        }
+      }
+      for (int d = 1; d < GQ; d <<= 1) {
+        v02 += (uint32_t)__shfl_xor((int)v02, d);
+        v1 += (uint32_t)__shfl_xor((int)v1, d);
+      }
+      if (on && (tid & (GQ - 1)) == 0) {
+        atomicAdd(&sum[0][ci], v02 & 0xFFFFu);
+        atomicAdd(&sum[1][ci], v1);
+        atomicAdd(&sum[2][ci], v02 >> 16);
+      }
+    }
+  } else
+  for (int i0 = 0; i0 < p.th * t.TW; i0 += 256) {
+    const int i = i0 + tid;
+    const int r = mdiv(i, t.m_tw), c = i - r * t.TW;
+    const int ci = mdiv(r, t.m_cell) * t.nx + mdiv(c, t.m_cell);
+    const bool in = i < p.th * t.TW;
+    const bool on = in && c < p.tw && flag[ci] != 0u;
+    if (!__any(on)) continue;                                         // (uniform over the wave)
+    const uint32_t s = on ? source_px<KIND>(a, p.f, p.Y0 + r, p.X0 + c) : 0u;
+    uint32_t v02 = s & 0x00FF00FFu, v1 = (s >> 8) & 0xFFu;
+    for (int d = 1; d < t.G; d <<= 1) {
+      v02 += (uint32_t)__shfl_xor((int)v02, d);
+      v1 += (uint32_t)__shfl_xor((int)v1, d);
+    }
+    if (on && (tid & (t.G - 1)) == 0) {                               // the group's first lane: the smallest column, in the picture if any is
+      atomicAdd(&sum[0][ci], v02 & 0xFFFFu);
+      atomicAdd(&sum[1][ci], v1);
+      atomicAdd(&sum[2][ci], v02 >> 16);
+    }
+  }
+  __syncthreads();
+  if (tid < t.ny * t.nx && flag[tid] != 0u) {
+    const int cy = tid / t.nx, cx = tid - cy * t.nx;
+    const uint32_t n = (uint32_t)(cell_extent(t.cell, cy, p.th) * cell_extent(t.cell, cx, p.tw));   // (> 0: the cell has a flagged pixel)
+    mean[tid] = (sum[0][tid] + n / 2) / n | (sum[1][tid] + n / 2) / n << 8 | (sum[2][tid] + n / 2) / n << 16;
+  }
+  __syncthreads();
+  // paint: item j of tile row r is the j-th group of 4 flat pixels that meets the row's segment
+  for (int it = tid; it < p.th * t.items; it += 256) {
+    const int r = mdiv(it, t.m_items), j = it - r * t.items;
+    const int Y = p.Y0 + r;
+    const long row = ((long)p.f * t.H + Y) * t.W;                    // flat pixel of (f, Y, 0), < 2^31
+    const long seg = row + p.X0;                                      // the segment: flat pixels [seg, seg + tw)
+    const long ps = 4 * ((seg + 4 - a.head) / 4 + j) + a.head - 4;    // the group's first flat pixel (may lie before seg)
+    const long lo = ps > seg ? ps : seg, hi = ps + 4 < seg + p.tw ? ps + 4 : seg + p.tw;
+    if (lo >= hi) continue;
+    const int cyn = mdiv(r, t.m_cell) * t.nx;
+    const bool whole = hi - lo == 4;
+    uint32_t l4 = 0u, c0 = 0u, c1 = 0u, c2 = 0u;
+    const bool wide_src = KIND == 1 && whole && a.ident;
+    if (whole) l4 = ld4(t.labels + ps);
+    if (wide_src) {
+      const unsigned char* q = (const unsigned char*)a.frames + (long)p.f * a.frame_stride + (long)Y * a.w0 + (int)(ps - row);
+      c0 = ld4(q); c1 = ld4(q + a.plane); c2 = ld4(q + 2 * a.plane);
+    }
+    uint32_t px[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const long q = ps + k;
+      if (q < lo || q >= hi) continue;
+      const int X = (int)(q - row);
+      const uint32_t l = whole ? (l4 >> 8 * k) & 0xFFu : (uint32_t)t.labels[q];
+      const uint32_t ac = act[l];
+      if (ac == 2u) {
+        px[k] = mean[cyn + mdiv(X - p.X0, t.m_cell)];
+        continue;
+      }
+      const uint32_t s = wide_src ? ((c0 >> 8 * k) & 0xFFu) | ((c1 >> 8 * k) & 0xFFu) << 8 | ((c2 >> 8 * k) & 0xFFu) << 16
+                                  : source_px<KIND>(a, p.f, Y, X);
+      px[k] = ac == 0u ? s : tint(s, pal[l], edge_at<R>(t.labels + q, l, Y, X, t.H, t.W), t.a256);
+    }
+    unsigned char* o = a.out + 3L * ps;
+    if (whole) {
+      uint32_t* o4 = (uint32_t*)o;                                    // 4-byte aligned by the groups' layout
+      o4[0] = px[0] | px[1] << 24;
+      o4[1] = px[1] >> 8 | px[2] << 16;
+      o4[2] = px[2] >> 16 | px[3] << 8;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (ps + k >= lo && ps + k < hi) {
+          o[3 * k] = (unsigned char)px[k]; o[3 * k + 1] = (unsigned char)(px[k] >> 8); o[3 * k + 2] = (unsigned char)(px[k] >> 16);
+        }
+    }
+  }
+}
+
+template <int KIND>
+void launch_mosaic(int contour, dim3 grid, hipStream_t stream, const MosaicArgs& a) {
+  switch (contour) {
+    case 0: hipLaunchKernelGGL((render_mosaic_kernel<KIND, 0>), grid, dim3(256), 0, stream, a); break;
+    case 1: hipLaunchKernelGGL((render_mosaic_kernel<KIND, 1>), grid, dim3(256), 0, stream, a); break;
+    case 2: hipLaunchKernelGGL((render_mosaic_kernel<KIND, 2>), grid, dim3(256), 0, stream, a); break;
+    default: hipLaunchKernelGGL((render_mosaic_kernel<KIND, 3>), grid, dim3(256), 0, stream, a); break;
+  }
+}
+
+// the tile part of a launch's arguments; -> the number of tiles
+long tile_args(TileArgs& t, const unsigned char* labels, const unsigned char* action, int F, int H, int W, int cell, int a256) {
+  const Tile tl = tile_of(cell);
+  t.labels = labels;
+  t.action = action;
+  t.H = H; t.W = W;
+  t.cell = cell; t.ny = tl.ny; t.nx = tl.nx;
+  t.G = cell & -cell;
+  t.TH = tl.ny * cell; t.TW = tl.nx * cell;
+  t.tiles_x = (unsigned)((W + t.TW - 1) / t.TW);
+  t.tiles_y = (unsigned)((H + t.TH - 1) / t.TH);
+  t.m_tw = magic(t.TW);
+  t.m_cell = magic(cell);
+  t.m_htw = magic(t.TW / 2);
+  t.m_q = magic(t.TW / 4);
+  t.lab4 = (((uintptr_t)labels | (uintptr_t)W) & 3u) == 0;
+  t.a256 = (uint32_t)a256;
+  return (long)F * t.tiles_y * t.tiles_x;                             // <= F * H * W < 2^31
+}
+
+// ---- surfaces -----------------------------------------------------------------------------------------------------------------------
+struct MosaicYuvArgs {
+  TileArgs t;
+  const unsigned char* y;
+  const unsigned char* uv;
+  const unsigned short* palette;                 // [256, 3]: Y, U, V in sample units
+  unsigned char* oy;                             // at frame f_off already
+  unsigned char* ouv;
+  long y_pitch, y_stride, uv_pitch, uv_stride;   // bytes
+  long oy_pitch, oy_stride, ouv_pitch, ouv_stride;
+};
+
+template <int FMT>
+__device__ __forceinline__ uint32_t row_raw(const unsigned char* row, int i) {
+  return FMT == 0 ? (uint32_t)row[i] : (uint32_t)((const unsigned short*)row)[i];
+}
+template <int FMT>
+__device__ __forceinline__ void row_put(unsigned char* row, int i, uint32_t raw) {
+  if (FMT == 0) row[i] = (unsigned char)raw; else ((unsigned short*)row)[i] = (unsigned short)raw;
+}
+template <int FMT> __device__ __forceinline__ uint32_t value_of(uint32_t raw) { return FMT == 0 ? raw : raw >> 6; }
+template <int FMT> __device__ __forceinline__ uint32_t stored(uint32_t v) { return FMT == 0 ? v : v << 6; }
+template <int FMT> __device__ __forceinline__ uint32_t comp(uint32_t c, int k) { return (c >> 10 * k) & (FMT ? 0x3FFu : 0xFFu); }
+
+// tinted value of the rule: the palette component on an edge, else the blend.  s, p <= 1023: s * (256 - a) + p * a + 128 < 2^19.
+__device__ __forceinline__ uint32_t tint1(uint32_t s, uint32_t p, bool edge, uint32_t a) {
+  return edge ? p : (s * (256u - a) + p * a + 128u) >> 8;
+}
+
+// One 2 x 2 block (columns c, c + 1 of rows r0, r0 + 1; nr x nc of them in the picture): the rule as written, on stored samples ry, ru,
+// rv handed in and the block's labels read at `lab` (the label of (r0, c)).  m: the packed means of the block's cell.
+template <int FMT, int R>
+__device__ __forceinline__ void block2x2(const TileArgs& t, const uint32_t* pal, const unsigned char* act, uint32_t m,
+                                         const unsigned char* lab, int r0, int c, int nr, int nc,
+                                         const uint32_t (&ry)[2][2], uint32_t ru, uint32_t rv, uint32_t (&oy)[2][2], uint32_t& ou, uint32_t& ov) {
+  const uint32_t U = value_of<FMT>(ru), V = value_of<FMT>(rv);
+  uint32_t su = 0u, sv = 0u, any = 0u;
+#pragma unroll
+  for (int row = 0; row < 2; ++row) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      oy[row][k] = 0u;
+      if (row >= nr || k >= nc) continue;
+      const unsigned char* q = lab + (long)row * t.W + k;
+      const uint32_t l = q[0], ac = act[l];
+      any |= ac;
+      if (ac == 0u) {
+        oy[row][k] = ry[row][k];
+        su += U; sv += V;
+      } else if (ac == 2u) {
+        oy[row][k] = stored<FMT>(comp<FMT>(m, 0));
+        su += comp<FMT>(m, 1); sv += comp<FMT>(m, 2);
+      } else {
+        const bool edge = edge_at<R>(q, l, r0 + row, c + k, t.H, t.W);
+        const uint32_t col = pal[l];
+        oy[row][k] = stored<FMT>(tint1(value_of<FMT>(ry[row][k]), comp<FMT>(col, 0), edge, t.a256));
+        su += tint1(U, comp<FMT>(col, 1), edge, t.a256);
+        sv += tint1(V, comp<FMT>(col, 2), edge, t.a256);
+      }
+    }
+  }
+  const uint32_t sh = (uint32_t)(nr * nc) >> 1;                       // n = 1, 2, 4: n / 2 = log2(n) = 0, 1, 2
+  ou = any != 0u ? stored<FMT>((su + sh) >> sh) : ru;
+  ov = any != 0u ? stored<FMT>((sv + sh) >> sh) : rv;
+}
+
+template <int FMT, int PX, int R>
+__global__ __launch_bounds__(256) void render_mosaic_yuv_kernel(const MosaicYuvArgs a) {
+  __shared__ uint32_t pal[256];
+  __shared__ unsigned char act[256];
+  __shared__ uint32_t flag[MAX_CELLS];
+  __shared__ uint32_t sum[3][MAX_CELLS];
+  __shared__ uint32_t mean[MAX_CELLS];
+  const TileArgs& t = a.t;
+  const int tid = (int)threadIdx.x;
+  {
+    const unsigned short* q = a.palette + 3 * tid;
+    pal[tid] = ((uint32_t)q[0] & 0x3FFu) | ((uint32_t)q[1] & 0x3FFu) << 10 | ((uint32_t)q[2] & 0x3FFu) << 20;
+    act[tid] = t.action[tid];
+    flag[tid] = 0u;
+    sum[0][tid] = 0u; sum[1][tid] = 0u; sum[2][tid] = 0u;
+  }
+  __syncthreads();
+  const TilePos p = tile_pos(t);
+  constexpr int BPS = FMT ? 2 : 1;                                   // bytes per sample
+  const unsigned char* y0 = a.y + p.f * a.y_stride + (long)p.Y0 * a.y_pitch + (long)p.X0 * BPS;          // sample (Y0, X0)
+  const unsigned char* c0p = a.uv + p.f * a.uv_stride + (long)(p.Y0 / 2) * a.uv_pitch + (long)p.X0 * BPS;  // pair (Y0 / 2, X0 / 2)
+  unsigned char* oy0 = a.oy + p.f * a.oy_stride + (long)p.Y0 * a.oy_pitch + (long)p.X0 * BPS;
+  unsigned char* oc0 = a.ouv + p.f * a.ouv_stride + (long)(p.Y0 / 2) * a.ouv_pitch + (long)p.X0 * BPS;
+  const unsigned char* lab0 = t.labels + ((long)p.f * t.H + p.Y0) * t.W + p.X0;
+  flag_cells(t, p, act, flag);
+  __syncthreads();
+  // luma sums of the flagged cells, 4 samples per lane where cell is a multiple of 4 (as the RGB kernel's)
+  if (t.G >= 4) {
+    const int Q = t.TW >> 2, GQ = t.G >> 2;
+    for (int i0 = 0; i0 < p.th * Q; i0 += 256) {
+      const int i = i0 + tid;
+      const int r = mdiv(i, t.m_q), c = 4 * (i - r * Q);
+      const int ci = mdiv(r, t.m_cell) * t.nx + mdiv(c, t.m_cell);
+      const bool on = i < p.th * Q && c < p.tw && flag[ci] != 0u;
+      if (!__any(on)) continue;
+      uint32_t v = 0u;
+      if (on) {
+        const unsigned char* q = y0 + (long)r * a.y_pitch;
+        if (PX == 4) {                                                // (aligned, and tw is a multiple of 4)
+          uint32_t w[BPS];
+          __builtin_memcpy(w, __builtin_assume_aligned(q + (long)c * BPS, 4), 4 * BPS);
+          if (FMT == 0) v = __builtin_amdgcn_sad_u8(w[0], 0u, 0u);
+          else v = ((w[0] & 0xFFFFu) >> 6) + (w[0] >> 22) + ((w[BPS - 1] & 0xFFFFu) >> 6) + (w[BPS - 1] >> 22);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (c + k < p.tw) v += value_of<FMT>(row_raw<FMT>(q, c + k));
+        }
+      }
+      for (int d = 1; d < GQ; d <<= 1) v += (uint32_t)__shfl_xor((int)v, d);
+      if (on && (tid & (GQ - 1)) == 0) atomicAdd(&sum[0][ci], v);
+    }
+  } else
+  for (int i0 = 0; i0 < p.th * t.TW; i0 += 256) {
+    const int i = i0 + tid;
+    const int r = mdiv(i, t.m_tw), c = i - r * t.TW;
+    const int ci = mdiv(r, t.m_cell) * t.nx + mdiv(c, t.m_cell);
+    const bool on = i < p.th * t.TW && c < p.tw && flag[ci] != 0u;
+    if (!__any(on)) continue;
+    uint32_t v = on ? value_of<FMT>(row_raw<FMT>(y0 + (long)r * a.y_pitch, c)) : 0u;
+    for (int d = 1; d < t.G; d <<= 1) v += (uint32_t)__shfl_xor((int)v, d);
+    if (on && (tid & (t.G - 1)) == 0) atomicAdd(&sum[0][ci], v);
+  }
+  // chroma sums: the pairs under the same cells, groups of G / 2 lanes
+  const int chr = (p.th + 1) / 2, chc = (p.tw + 1) / 2, HTW = t.TW / 2, GC = t.G / 2;
+  for (int i0 = 0; i0 < chr * HTW; i0 += 256) {
+    const int i = i0 + tid;
+    const int r = mdiv(i, t.m_htw), c = i - r * HTW;
+    const int ci = mdiv(2 * r, t.m_cell) * t.nx + mdiv(2 * c, t.m_cell);
+    const bool on = i < chr * HTW && c < chc && flag[ci] != 0u;
+    if (!__any(on)) continue;
+    uint32_t v = 0u;
+    if (on) {
+      const unsigned char* q = c0p + (long)r * a.uv_pitch;
+      v = value_of<FMT>(row_raw<FMT>(q, 2 * c)) | value_of<FMT>(row_raw<FMT>(q, 2 * c + 1)) << 16;
+    }
+    for (int d = 1; d < GC; d <<= 1) v += (uint32_t)__shfl_xor((int)v, d);
+    if (on && (tid & (GC - 1)) == 0) {                                // (G >= 2: GC >= 1)
+      atomicAdd(&sum[1][ci], v & 0xFFFFu);
+      atomicAdd(&sum[2][ci], v >> 16);
+    }
+  }
+  __syncthreads();
+  if (tid < t.ny * t.nx && flag[tid] != 0u) {
+    const int cy = tid / t.nx, cx = tid - cy * t.nx;
+    const int hh = cell_extent(t.cell, cy, p.th), ww = cell_extent(t.cell, cx, p.tw);
+    const uint32_t n = (uint32_t)(hh * ww), nc = (uint32_t)(((hh + 1) / 2) * ((ww + 1) / 2));
+    mean[tid] = (sum[0][tid] + n / 2) / n | (sum[1][tid] + nc / 2) / nc << 10 | (sum[2][tid] + nc / 2) / nc << 20;
+  }
+  __syncthreads();
+  // paint: item j of row pair rp is the block of 2 rows x PX pixels at column PX * j of the tile
+  for (int it = tid; it < chr * t.items; it += 256) {
+    const int rp = mdiv(it, t.m_items), j = it - rp * t.items;
+    const int cb = PX * j;                                            // column inside the tile
+    if (cb >= p.tw) continue;
+    const int r0 = p.Y0 + 2 * rp, c0 = p.X0 + cb;
+    const int nr = r0 + 1 < t.H ? 2 : 1;
+    const int cyn = mdiv(2 * rp, t.m_cell) * t.nx;
+    const unsigned char* yrow = y0 + (long)(2 * rp) * a.y_pitch;
+    const unsigned char* crow = c0p + (long)rp * a.uv_pitch;
+    unsigned char* oyrow = oy0 + (long)(2 * rp) * a.oy_pitch;
+    unsigned char* ocrow = oc0 + (long)rp * a.ouv_pitch;
+    const unsigned char* lab = lab0 + (long)(2 * rp) * t.W + cb;
+    if constexpr (PX == 4) {
+      // every pointer, pitch, stride and W are multiples of 4 and so is the tile's width: the block lies inside the row, 4-byte aligned
+      constexpr int NW = BPS;                                         // dwords of 4 samples
+      uint32_t yw[2][NW], cw[NW], oyw[2][NW], ocw[NW];
+      __builtin_memcpy(yw[0], __builtin_assume_aligned(yrow + (long)cb * BPS, 4), 4 * NW);
+      if (nr == 2) __builtin_memcpy(yw[1], __builtin_assume_aligned(yrow + a.y_pitch + (long)cb * BPS, 4), 4 * NW);
+      else { yw[1][0] = 0u; yw[1][NW - 1] = 0u; }
+      __builtin_memcpy(cw, __builtin_assume_aligned(crow + (long)cb * BPS, 4), 4 * NW);
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {                                   // the block's two chroma pairs
+        uint32_t ry[2][2], o[2][2], ou, ov;
+#pragma unroll
+        for (int row = 0; row < 2; ++row) {
+          if (FMT == 0) { ry[row][0] = (yw[row][0] >> 16 * q) & 0xFFu; ry[row][1] = (yw[row][0] >> (16 * q + 8)) & 0xFFu; }
+          else { ry[row][0] = yw[row][q] & 0xFFFFu; ry[row][1] = yw[row][q] >> 16; }
+        }
+        const uint32_t ru = FMT == 0 ? (cw[0] >> 16 * q) & 0xFFu : cw[q] & 0xFFFFu;
+        const uint32_t rv = FMT == 0 ? (cw[0] >> (16 * q + 8)) & 0xFFu : cw[q] >> 16;
+        block2x2<FMT, R>(t, pal, act, mean[cyn + mdiv(cb + 2 * q, t.m_cell)], lab + 2 * q, r0, c0 + 2 * q, nr, 2, ry, ru, rv, o, ou, ov);
+        if (FMT == 0) {
+#pragma unroll
+          for (int row = 0; row < 2; ++row) {
+            const uint32_t two = o[row][0] | o[row][1] << 8;
+            oyw[row][0] = q == 0 ? two : oyw[row][0] | two << 16;
+          }
+          ocw[0] = q == 0 ? (ou | ov << 8) : ocw[0] | (ou | ov << 8) << 16;
+        } else {
+          oyw[0][q] = o[0][0] | o[0][1] << 16;
+          oyw[1][q] = o[1][0] | o[1][1] << 16;
+          ocw[q] = ou | ov << 16;
+        }
+      }
+      __builtin_memcpy(__builtin_assume_aligned(oyrow + (long)cb * BPS, 4), oyw[0], 4 * NW);
+      if (nr == 2) __builtin_memcpy(__builtin_assume_aligned(oyrow + a.oy_pitch + (long)cb * BPS, 4), oyw[1], 4 * NW);
+      __builtin_memcpy(__builtin_assume_aligned(ocrow + (long)cb * BPS, 4), ocw, 4 * NW);
+    } else {
+      const int nc = c0 + 1 < t.W ? 2 : 1;
+      uint32_t ry[2][2] = {{0u, 0u}, {0u, 0u}}, o[2][2], ou, ov;
+#pragma unroll
+      for (int row = 0; row < 2; ++row)
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+          if (row < nr && k < nc) ry[row][k] = row_raw<FMT>(yrow + (long)row * a.y_pitch, cb + k);
+      const uint32_t ru = row_raw<FMT>(crow, cb), rv = row_raw<FMT>(crow, cb + 1);
+      block2x2<FMT, R>(t, pal, act, mean[cyn + mdiv(cb, t.m_cell)], lab, r0, c0, nr, nc, ry, ru, rv, o, ou, ov);
+#pragma unroll
+      for (int row = 0; row < 2; ++row)
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+          if (row < nr && k < nc) row_put<FMT>(oyrow + (long)row * a.oy_pitch, cb + k, o[row][k]);
+      row_put<FMT>(ocrow, cb, ou);
+      row_put<FMT>(ocrow, cb + 1, ov);
+    }
+  }
+}
+
+template <int FMT, int PX>
+void launch_my(int contour, dim3 grid, hipStream_t stream, const MosaicYuvArgs& a) {
+  switch (contour) {
+    case 0: hipLaunchKernelGGL((render_mosaic_yuv_kernel<FMT, PX, 0>), grid, dim3(256), 0, stream, a); break;
+    case 1: hipLaunchKernelGGL((render_mosaic_yuv_kernel<FMT, PX, 1>), grid, dim3(256), 0, stream, a); break;
+    case 2: hipLaunchKernelGGL((render_mosaic_yuv_kernel<FMT, PX, 2>), grid, dim3(256), 0, stream, a); break;
+    default: hipLaunchKernelGGL((render_mosaic_yuv_kernel<FMT, PX, 3>), grid, dim3(256), 0, stream, a); break;
+  }
+}
+
+bool cell_ok(int cell) { return cell >= 2 && cell <= 64 && (cell & 1) == 0; }
+
+}  // namespace
+
+extern "C" int mdqe_render_mosaic_u8(const void* frames, int is_u8, long frame_stride, int h0, int w0,
+                                     const unsigned char* labels, int F, int Ho, int Wo,
+                                     const unsigned char* palette, const unsigned char* action, int a256, int contour, int cell,
+                                     unsigned char* out, int f_off, void* stream) {
+  MDQE_REQUIRE(a256 >= 0 && a256 <= 256 && contour >= 0 && contour <= 3 && cell_ok(cell));
+  MDQE_REQUIRE(F >= 0 && Ho > 0 && Wo > 0 && f_off >= 0 && (long)Ho * Wo * 3 < 0x7FFFFFFFL);
+  MDQE_REQUIRE((long)F * Ho * Wo < 0x7FFFFFFFL);                     // the flat pixel index of one call is 32-bit
+  if (frames != nullptr) {
+    MDQE_REQUIRE(h0 > 0 && w0 > 0 && (long)h0 * Ho < 0x7FFFFFFFL && (long)w0 * Wo < 0x7FFFFFFFL);   // (Y * h0, X * w0 in 32 bits)
+    MDQE_REQUIRE(frame_stride >= 3L * h0 * w0 || F <= 1);
+  }
+  if (F == 0) return MDQE_OK;
+  MDQE_CHECK_PTR(labels);
+  MDQE_CHECK_PTR(palette);
+  MDQE_CHECK_PTR(action);
+  MDQE_CHECK_PTR(out);
+  MosaicArgs a;
+  const long tiles = tile_args(a.t, labels, action, F, Ho, Wo, cell, a256);
+  a.frames = frames;
+  a.frame_stride = frame_stride;
+  a.h0 = frames ? h0 : 1;
+  a.w0 = frames ? w0 : 1;
+  a.plane = (long)a.h0 * a.w0;
+  a.palette = palette;
+  a.out = out + (long)f_off * Ho * Wo * 3;
+  a.head = (unsigned)((uintptr_t)a.out & 3u);
+  // a segment of TW pixels meets at most TW / 4 + 1 groups; exactly TW / 4 where every segment starts a group (Wo and the tiles'
+  // width are multiples of 4 and so is the output address)
+  a.t.items = a.t.TW / 4 + ((Wo & 3) == 0 && a.head == 0 ? 0 : 1);
+  a.t.m_items = magic(a.t.items);
+  a.ident = frames != nullptr && h0 == Ho && w0 == Wo;
+  mdqe_clear_error();
+  const dim3 grid((unsigned)tiles);
+  if (frames == nullptr) launch_mosaic<0>(contour, grid, (hipStream_t)stream, a);
+  else if (is_u8) launch_mosaic<1>(contour, grid, (hipStream_t)stream, a);
+  else launch_mosaic<2>(contour, grid, (hipStream_t)stream, a);
+  return mdqe_launch_status();
+}
+
+extern "C" int mdqe_render_mosaic_yuv420sp(const void* y, long y_pitch, long y_stride, const void* uv, long uv_pitch, long uv_stride,
+                                           int F, int H, int W, int fmt, const unsigned char* labels,
+                                           const unsigned short* palette_yuv, const unsigned char* action, int a256, int contour, int cell,
+                                           void* out_y, long out_y_pitch, long out_y_stride,
+                                           void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream) {
+  MDQE_REQUIRE(a256 >= 0 && a256 <= 256 && contour >= 0 && contour <= 3 && cell_ok(cell));
+  MDQE_REQUIRE(F >= 0 && H > 0 && W > 0 && f_off >= 0 && (fmt == 0 || fmt == 1));
+  const long bps = fmt ? 2 : 1, yb = bps * W, cb = bps * 2 * ((W + 1L) / 2), CH = (H + 1L) / 2;
+  MDQE_REQUIRE(y_pitch >= yb && uv_pitch >= cb && y_stride >= 0 && uv_stride >= 0);
+  MDQE_REQUIRE(out_y_pitch >= yb && out_uv_pitch >= cb && out_y_stride >= 0 && out_uv_stride >= 0);
+  if (fmt == 1)
+    MDQE_REQUIRE(((y_pitch | y_stride | uv_pitch | uv_stride | out_y_pitch | out_y_stride | out_uv_pitch | out_uv_stride) & 1L) == 0);
+  // (two output surfaces that shared bytes would have two writers)
+  if (F > 1) MDQE_REQUIRE(out_y_stride >= (H - 1) * out_y_pitch + yb && out_uv_stride >= (CH - 1) * out_uv_pitch + cb);
+  MDQE_REQUIRE((long)F * H * W < 0x7FFFFFFFL);
+  if (F == 0) return MDQE_OK;
+  MDQE_CHECK_PTR(y);
+  MDQE_CHECK_PTR(uv);
+  MDQE_CHECK_PTR(labels);
+  MDQE_CHECK_PTR(palette_yuv);
+  MDQE_CHECK_PTR(action);
+  MDQE_CHECK_PTR(out_y);
+  MDQE_CHECK_PTR(out_uv);
+  MDQE_REQUIRE(((uintptr_t)palette_yuv & 1u) == 0);
+  if (fmt == 1) MDQE_REQUIRE((((uintptr_t)y | (uintptr_t)uv | (uintptr_t)out_y | (uintptr_t)out_uv) & 1u) == 0);
+  unsigned char* oy = (unsigned char*)out_y + (long)f_off * out_y_stride;
+  unsigned char* ouv = (unsigned char*)out_uv + (long)f_off * out_uv_stride;
+  {
+    // a cell's mean reads samples that other threads write: no output plane may meet an input plane (not in place either), the other
+    // output plane, the labels, the palette or the action table
+    const Plane sy = plane_of(y, y_pitch, y_stride, F, H, yb), sc = plane_of(uv, uv_pitch, uv_stride, F, CH, cb);
+    const Plane ty = plane_of(oy, out_y_pitch, out_y_stride, F, H, yb), tc = plane_of(ouv, out_uv_pitch, out_uv_stride, F, CH, cb);
+    const Plane sl = plane_of(labels, W, (long)H * W, F, H, W), sp = plane_of(palette_yuv, 6, 0, 1, 256, 6);
+    const Plane sa = plane_of(action, 256, 0, 1, 1, 256);
+    MDQE_REQUIRE(apart(sy, ty) && apart(sc, tc) && apart(sy, tc) && apart(sc, ty) && apart(ty, tc));
+    MDQE_REQUIRE(apart(sl, ty) && apart(sl, tc) && apart(sp, ty) && apart(sp, tc) && apart(sa, ty) && apart(sa, tc));
+  }
+  // 4-byte accesses where every address of the launch is aligned for them (strides matter only between surfaces)
+  uintptr_t m = (uintptr_t)y | (uintptr_t)uv | (uintptr_t)oy | (uintptr_t)ouv | (uintptr_t)labels | (uintptr_t)W
+              | (uintptr_t)y_pitch | (uintptr_t)uv_pitch | (uintptr_t)out_y_pitch | (uintptr_t)out_uv_pitch;
+  if (F > 1) m |= (uintptr_t)y_stride | (uintptr_t)uv_stride | (uintptr_t)out_y_stride | (uintptr_t)out_uv_stride | (uintptr_t)((long)H * W);
+  const int px = (m & 3u) == 0 ? 4 : 2;
+  MosaicYuvArgs a;
+  const long tiles = tile_args(a.t, labels, action, F, H, W, cell, a256);
+  a.t.items = a.t.TW / px;                                            // (TW is a multiple of 4)
+  a.t.m_items = magic(a.t.items);
+  a.y = (const unsigned char*)y;
+  a.uv = (const unsigned char*)uv;
+  a.palette = palette_yuv;
+  a.oy = oy;
+  a.ouv = ouv;
+  a.y_pitch = y_pitch; a.y_stride = y_stride; a.uv_pitch = uv_pitch; a.uv_stride = uv_stride;
+  a.oy_pitch = out_y_pitch; a.oy_stride = out_y_stride; a.ouv_pitch = out_uv_pitch; a.ouv_stride = out_uv_stride;
+  mdqe_clear_error();
+  const dim3 grid((unsigned)tiles);
+  hipStream_t s = (hipStream_t)stream;
+  if (fmt == 0) { if (px == 4) launch_my<0, 4>(contour, grid, s, a); else launch_my<0, 2>(contour, grid, s, a); }
+  else { if (px == 4) launch_my<1, 4>(contour, grid, s, a); else launch_my<1, 2>(contour, grid, s, a); }
+  return mdqe_launch_status();
+}

@@ -211,24 +211,32 @@ class FrameStore:
         return out
 
 
-def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, source, f0, style, out, o_off):
+def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, source, f0, style, cls, out, o_off):
     """A window's overlay: the label map of window logits m [n, F, Hm, Wm] into labels[l_off:l_off + F] (`label_maps`: all n rows
     compete, as in every label path), then that map painted over video frames [f0, f0 + F) of `source` (a FrameStore) into
     out[o_off:o_off + F] (uint8 [>= o_off + F, Ho, Wo, 3], device) in `style` (render.Style) -- one ops.render_overlay launch per
     contiguous piece of source frames, on the stream the label map runs on (the current one).  A surface picture (`out` a device
     YuvFrames; the pieces are then the surfaces handed in, of the output size): painted in the YUV domain, one
-    ops.render_overlay_yuv launch per piece, with the palette in the surfaces' samples.  -> `label_maps`' geometry table or None."""
+    ops.render_overlay_yuv launch per piece, with the palette in the surfaces' samples.  A style with a mosaic (style.mosaic): the
+    same launches of ops.render_mosaic / ops.render_mosaic_yuv with the style's action table; `cls`, the window's class rows [n, K]
+    on the host, is what a style with `classes` builds that table from.  -> `label_maps`' geometry table or None."""
     from . import ops
     geom = label_maps(m, stride, frame_hw, out_size, geometry, labels, l_off)
     nf = int(m.shape[1])
     surface = not torch.is_tensor(out)
     pal = style.palette_yuv_on(m.device, *out.meta()[2:]) if surface else style.palette_on(m.device)
+    act = style.actions_on(m.device, cls) if style.mosaic is not None else None
     for t, first in source.pieces(int(f0), int(f0) + nf, stream=torch.cuda.current_stream(m.device)):
         k, d = len(t), first - int(f0)
-        if surface:
-            ops.render_overlay_yuv(labels[l_off + d:l_off + d + k], t, pal, out, o_off + d, style.a256, style.contour)
+        lab = labels[l_off + d:l_off + d + k]
+        if act is not None and surface:
+            ops.render_mosaic_yuv(lab, t, pal, act, out, o_off + d, style.a256, style.contour, style.cell)
+        elif act is not None:
+            ops.render_mosaic(lab, t, pal, act, out, o_off + d, style.a256, style.contour, style.cell)
+        elif surface:
+            ops.render_overlay_yuv(lab, t, pal, out, o_off + d, style.a256, style.contour)
         else:
-            ops.render_overlay(labels[l_off + d:l_off + d + k], t, pal, out, o_off + d, style.a256, style.contour)
+            ops.render_overlay(lab, t, pal, out, o_off + d, style.a256, style.contour)
     return geom
 
 
@@ -277,8 +285,8 @@ def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels
     """What `forms` asks for of ONE flushed window (logits m [n, F, Hm, Wm]), on the current stream, for every path; the only caller
     of `overlay_frames`, `label_maps`, `dense_masks` and `rle_positions`.  First the label map of ALL n rows into labels = (device
     buffer, frame offset) and, with picture = (buffer, offset), its overlay, painted from paint = (FrameStore, first video frame,
-    render.Style).  Then the planes of `rows` (int32 device; None or empty: none): dense into planes = (buffer, offset) when given,
-    else, with forms.planes == "rle", their run boundaries on the host.  `hop(stage, geom) -> geom` runs behind each stage ("labels" |
+    render.Style, the window's class rows [n, K] on the host -- what a mosaic of classes is chosen by).  Then the planes of `rows`
+    (int32 device; None or empty: none): dense into planes = (buffer, offset) when given, else, with forms.planes == "rle", their run boundaries on the host.  `hop(stage, geom) -> geom` runs behind each stage ("labels" |
     "planes") that filled device buffers: the early and the online path send them to the host there, the map under the planes' kernel.
     -> (labels' geometry table [n, F, 5] or None, planes' table [len(rows), F, 5] or None, (pos, n_pos) of `rle_positions` or None)."""
     lgeom = pgeom = runs = None
@@ -433,12 +441,12 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
             d_pic = surface_picture(frame_source, n_frames, out_size, model.device)
         d_planes = torch.zeros(len(sel), n_frames, Ho, Wo, **u8) if forms.planes else None
         sel_dev = torch.tensor(sel, dtype=torch.int32, device=model.device) if forms.planes else None
-        for f_off, m in windows:
+        for i, (f_off, m) in enumerate(windows):
             n, nf = int(m.shape[0]), int(m.shape[1])
             cnt = sum(1 for i in sel if i < n)                     # sel is ascending: these are its first `cnt` entries
             at = [None if t is None else (t, f_off) for t in (d_planes, d_lab, d_pic)]
             lg, pg, _ = build_window(m, forms, sel_dev[:cnt] if forms.planes else None, model.cfg.match_stride, frame_hw, out_size, *at,
-                                     paint=(frame_source, f_off, model.overlay_style) if forms.overlay else None)
+                                     paint=(frame_source, f_off, model.overlay_style, cls_clips[i]) if forms.overlay else None)
             label_geoms.append((f_off, nf, n, lg))
             if cnt:
                 plane_geoms.append((f_off, nf, cnt, pg))
@@ -599,17 +607,18 @@ class ClipMerger:
                 if self.online:
                     self.emitted.append(self._online_window(c, m))
                 elif self.emit_masks and self.use_side and self.n_frames is not None and (self.early_on or self.forms.early_always):
-                    self._early_masks(m)
+                    self._early_masks(m, c)
                 elif self.emit_masks:
                     self.windows.append((self.f_off, m))
                 self.f_off += m.shape[1]
                 self.saved += 1
         self.done = self.done or bool(last)
 
-    def _window_to_host(self, m, pairs, event):
+    def _window_to_host(self, m, pairs, event, c=None):
         """The early and the online path: the forms of ALL n rows of the window just flushed (m: [n, F, Hm, Wm] mean logits) into
         per-window device scratch (`build_window`), each stage sent to the host behind it (`to_host`): pairs(kind, buffer) -> its (pinned
-        destination, source) pairs, kind = "labels" | "overlay" | "planes"; `event()` is recorded behind each hop.  -> build_window's."""
+        destination, source) pairs, kind = "labels" | "overlay" | "planes"; `event()` is recorded behind each hop; c: the window's class rows on the host (an
+        overlay's mosaic of classes).  -> build_window's."""
         forms, u8 = self.forms, dict(dtype=torch.uint8, device=self.dev)
         n, nf, Ho, Wo = int(m.shape[0]), int(m.shape[1]), int(self.out_size[0]), int(self.out_size[1])
         lab = torch.empty(nf, Ho, Wo, **u8) if forms.labels or forms.overlay else None    # (an overlay alone: a scratch, not copied)
@@ -625,10 +634,10 @@ class ClipMerger:
         cs = copy_stream(self.model) if copies["labels"] or copies["planes"] else None
         at = [None if t is None else (t, 0) for t in (planes, lab, pic)]
         return build_window(m, forms, rows, self.model.cfg.match_stride, self.frame_hw, self.out_size, *at,
-                            paint=(self.frame_source, self.f_off, self.style),
+                            paint=(self.frame_source, self.f_off, self.style, c),
                             hop=lambda stage, geom: to_host(cs, self.side, copies[stage], geom, event()))
 
-    def _early_masks(self, m):
+    def _early_masks(self, m, c=None):
         """Every form of EVERY instance tracked so far goes to pinned host memory while later windows compute; finish() then only
         selects rows.  A few rows may be produced in vain (instances that miss the final top-k).  Planes: one pinned [L, Ho, Wo] buffer
         per track (no re-allocation as tracks appear; the caching host allocator recycles the blocks of the previous call), or the run
@@ -655,7 +664,7 @@ class ClipMerger:
             if getattr(early, kind) is None:
                 setattr(early, kind, model.pinned_mask_buffer(shape + (3,) * (kind == "overlay")))
             return [(getattr(early, kind)[f0:f0 + nf], buf)]
-        lgeom, pgeom, runs = self._window_to_host(m, pairs, lambda: early.done)
+        lgeom, pgeom, runs = self._window_to_host(m, pairs, lambda: early.done, c)
         if forms.label_geometry:
             early.label_geom.append((f0, nf, n, lgeom))
         if runs is not None:
@@ -684,7 +693,7 @@ class ClipMerger:
         def event():                                # (None stays where nothing is copied: RLE, or a window without tracks)
             rec["ready"] = rec["ready"] or torch.cuda.Event()
             return rec["ready"]
-        lgeom, pgeom, runs = self._window_to_host(m, pairs, event)
+        lgeom, pgeom, runs = self._window_to_host(m, pairs, event, c)
         if forms.planes == "rle":
             rec["rles"] = R.positions_to_rles(*runs, out_size, nf) if n else []
         if forms.label_geometry:

@@ -1,5 +1,6 @@
 """How an overlay is painted (model.overlay_output, online_video(emit="overlay")): the palette and the style.  The painting itself is
-ops.render_overlay (csrc/render.hip) behind the label map; merge.overlay_frames puts the two together for a tracker window.
+ops.render_overlay (csrc/render.hip) behind the label map; merge.overlay_frames puts the two together for a tracker window.  A style
+with a mosaic (redaction) is painted by ops.render_mosaic (csrc/render_mosaic.hip) from the style's per-label action table.
 
 A track's colour depends only on its tracker row (label = row + 1), so it keeps its colour across windows and pushes."""
 import dataclasses
@@ -72,10 +73,18 @@ def palette_yuv(palette_rgb, fmt="nv12", matrix="bt709", full_range=False, order
 class Style:
     """alpha: weight of the track colour inside a region, 0..1 (the kernel blends with a256 = round(alpha * 256) in 1/256 steps);
     contour: reach in pixels, 0..3, of the full-colour line where a region meets another label (0: none); palette: uint8 [256, 3] in
-    the frames' channel order, row = label (None: default_palette())."""
+    the frames' channel order, row = label (None: default_palette()).
+    mosaic: None, or what is pixelated instead of tinted (ops.render_mosaic, csrc/render_mosaic.hip): "tracks" -- every track, or with
+    `classes` the tracks of those classes, the others tinted as ever; the background stays as decoded -- or "background" -- everything
+    but the tracks, which are tinted as alpha / contour say (alpha=0, contour=0: left exactly as decoded).  cell: the side of a mosaic
+    cell in output pixels, an even int in 2..64.  classes: None or a collection of class ids >= 0 (kept as a sorted tuple), only with
+    mosaic="tracks"."""
     alpha: float = 0.5
     contour: int = 1
     palette: torch.Tensor = None
+    mosaic: str = None
+    cell: int = 16
+    classes: tuple = None
 
     def __post_init__(self):
         if isinstance(self.alpha, bool) or not isinstance(self.alpha, (int, float)) or not 0.0 <= self.alpha <= 1.0:
@@ -85,10 +94,58 @@ class Style:
         if self.palette is not None and (not torch.is_tensor(self.palette) or self.palette.dtype != torch.uint8
                                          or tuple(self.palette.shape) != (256, 3)):
             raise ValueError("overlay style: palette must be a uint8 [256, 3] tensor or None")
+        if self.mosaic not in (None, "tracks", "background"):
+            raise ValueError("overlay style: mosaic must be None, 'tracks' or 'background', got %r" % (self.mosaic,))
+        if isinstance(self.cell, bool) or not isinstance(self.cell, int) or not 2 <= self.cell <= 64 or self.cell % 2:
+            raise ValueError("overlay style: cell must be an even int in 2..64, got %r" % (self.cell,))
+        if self.classes is not None:
+            try:
+                cls = tuple(self.classes) if not isinstance(self.classes, (str, bytes)) else None
+            except TypeError:
+                cls = None
+            if cls is None or any(isinstance(c, bool) or not isinstance(c, int) or c < 0 for c in cls):
+                raise ValueError("overlay style: classes must be None or a collection of ints >= 0, got %r" % (self.classes,))
+            if self.mosaic != "tracks":
+                raise ValueError("overlay style: classes selects the tracks that mosaic='tracks' pixelates; got classes with mosaic=%r"
+                                 % (self.mosaic,))
+            self.classes = tuple(sorted(set(cls)))
 
     @property
     def a256(self):
         return int(round(self.alpha * 256))
+
+    def actions(self, cls_probs=None):
+        """The per-label action table of ops.render_mosaic, uint8 [256] on the host (0 keep, 1 tint, 2 mosaic; entry 0 is the
+        background's), a pure function.  mosaic=None: [0, 1, 1, ...] (the plain overlay); "background": [2, 1, 1, ...]; "tracks":
+        [0, 2, 2, ...], or with `classes`, from the window's class rows cls_probs [n, K] (win.cls_probs): label t + 1 gets 2 when the
+        first maximum of row t is a class in `classes` and 1 otherwise, and so do the labels above n."""
+        act = torch.ones(256, dtype=torch.uint8)
+        act[0] = 2 if self.mosaic == "background" else 0
+        if self.mosaic == "tracks" and self.classes is None:
+            act[1:] = 2
+        elif self.mosaic == "tracks":
+            if not torch.is_tensor(cls_probs) or cls_probs.dim() != 2:
+                raise ValueError("overlay style: a mosaic of classes needs the window's class rows [n, K], got %r" % (type(cls_probs).__name__,))
+            n = min(int(cls_probs.shape[0]), 255)
+            if n and cls_probs.shape[1]:
+                rows = cls_probs[:n].detach().cpu()
+                first = rows.argmax(1)                  # (of several maxima the first: torch.argmax's rule)
+                hit = torch.isin(first, torch.tensor(self.classes, dtype=first.dtype))
+                act[1:n + 1] = torch.where(hit, 2, 1).to(torch.uint8)
+        return act
+
+    def actions_on(self, device, cls_probs=None):
+        """`actions` on `device`: cached per device as the palette is where the table does not depend on the window (no `classes`);
+        with `classes` built from the window's class rows and uploaded, 256 bytes per window."""
+        if self.classes is not None:
+            return self.actions(cls_probs).to(device)
+        cache = self.__dict__.setdefault("_act_on", {})
+        key = str(device)
+        if key not in cache:
+            cache[key] = self.actions().to(device)
+            if cache[key].is_cuda:
+                torch.cuda.current_stream(cache[key].device).synchronize()
+        return cache[key]
 
     def palette_on(self, device):
         """The palette on `device`, contiguous (cached per device: one tiny upload per session, not per window)."""
