@@ -120,7 +120,8 @@ def test_stem_maxpool_upsample_dw():
         wk = ops.stem_weight_kmajor(w.permute(0, 2, 3, 1).contiguous())
         out = ops.stem_conv(fr.cuda(), 64, 96, mean, std, wk.cuda(), b.cuda()).cpu().permute(0, 3, 1, 2)
         assert rel(out, F.relu(ref + b.view(1, 64, 1, 1))) < 2e-5
-    # fused stem: ragged tiles (output 36 x 44 is not a multiple of the 8 x 16 tile), more tiles than one block walks
+    # fused stem: ragged tiles (output 36 x 44 is not a multiple of the 8 x 16 tile).  45 tiles on 45 blocks: every block walks ONE tile;
+    # the persistent loop and its register prefetch run in tests/test_conv_spatial_gpu.py (1560 tiles on 768 blocks)
     fr = torch.randint(0, 256, (3, 3, 70, 85), generator=g).to(torch.uint8)
     xn = (fr.float() - torch.tensor(mean).view(1, 3, 1, 1)) / torch.tensor(std).view(1, 3, 1, 1)
     xp = torch.zeros(3, 3, 72, 88); xp[:, :, :70, :85] = xn

@@ -5,36 +5,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-
-def wino_weight(w):
-    """w [Cout, 3, 3, Cin] -> U [16, Cout, Cin] = G g G^T in double, rounded once (wino_weight_kernel)."""
-    g = w.double()
-    t = torch.stack([g[:, 0], 0.5 * (g[:, 0] + g[:, 1] + g[:, 2]), 0.5 * (g[:, 0] - g[:, 1] + g[:, 2]), g[:, 2]], 1)   # [Co, 4, 3, Ci]
-    u = torch.stack([t[:, :, 0], 0.5 * (t[:, :, 0] + t[:, :, 1] + t[:, :, 2]), 0.5 * (t[:, :, 0] - t[:, :, 1] + t[:, :, 2]), t[:, :, 2]], 2)
-    return u.float().permute(1, 2, 0, 3).reshape(16, w.shape[0], w.shape[3]).contiguous()
-
-
-def wino_conv(x, w, b):
-    """x [NI, H, W, Cin] fp32 NHWC, w [Cout, 3, 3, Cin] -> [NI, H, W, Cout] (stride 1, pad 1), the kernels' order of operations."""
-    NI, H, W, C = x.shape
-    th, tw = (H + 1) // 2, (W + 1) // 2
-    xp = torch.zeros(NI, 2 * th + 2, 2 * tw + 2, C)
-    xp[:, 1:H + 1, 1:W + 1] = x
-    d = xp.unfold(1, 4, 2).unfold(2, 4, 2)                     # [NI, th, tw, C, 4 (row), 4 (col)]
-    e = [d[..., 0, :] - d[..., 2, :], d[..., 1, :] + d[..., 2, :], d[..., 2, :] - d[..., 1, :], d[..., 1, :] - d[..., 3, :]]
-    V = []
-    for a in range(4):
-        r = e[a]
-        V += [r[..., 0] - r[..., 2], r[..., 1] + r[..., 2], r[..., 2] - r[..., 1], r[..., 1] - r[..., 3]]
-    V = torch.stack(V, 0).reshape(16, -1, C)                   # [16, T, Cin]
-    M = torch.bmm(V, wino_weight(w).transpose(1, 2))           # [16, T, Cout], fp32
-    m = M.reshape(4, 4, NI, th, tw, -1)
-    q = [(m[0] + m[1]) + m[2], (m[1] - m[2]) - m[3]]
-    y = torch.empty(NI, th, 2, tw, 2, M.shape[-1])
-    for a in range(2):
-        y[:, :, a, :, 0] = ((q[a][0] + q[a][1]) + q[a][2]) + b
-        y[:, :, a, :, 1] = ((q[a][1] - q[a][2]) - q[a][3]) + b
-    return y.reshape(NI, 2 * th, 2 * tw, -1)[:, :H, :W]
+# the emulation lives beside the float64 references and bounds that tests/test_conv_spatial_*.py hold the kernels to
+from _conv_spatial_ref import wino_eval as wino_conv, wino_weight
 
 
 @pytest.mark.parametrize("NI,H,W,Cin,Cout", [(3, 12, 20, 256, 256), (2, 24, 40, 256, 256), (1, 48, 80, 128, 128), (1, 15, 27, 256, 256),
