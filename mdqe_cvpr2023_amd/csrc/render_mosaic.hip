@@ -24,8 +24,10 @@
 // were touched microseconds before).  No atomics on global memory, no data-dependent order anywhere: identical from run to run.
 // Row and cell indices inside a tile come from multiplications by ceil(2^32 / d) (exact while n * d < 2^32; a tile has fewer than 2^13
 // pixels and d <= 124).
-#include "common.h"
-#include "render_planes.h"
+// Both kernels say a phase once: the LDS block (TileLds, init_lds), tile_pos, flag_cells, the sum loop (sum_flagged over what a lane adds
+// up: RgbSum, LumaSum, ChromaSum; the fast loads are the loader each kernel passes in) and cell_means.  The rule's pieces (source pixel,
+// tints, sample helpers, contour test and dispatch) and the entries' checks are render_rule.h's, shared with the plain painters.
+#include "render_rule.h"
 
 namespace {
 
@@ -57,32 +59,6 @@ struct TileArgs {
   int items;                     // paint items per tile row (RGB) or row pair (surfaces)
   uint32_t a256;
 };
-
-__device__ __forceinline__ uint32_t ld4(const unsigned char* p) {     // (any alignment)
-  uint32_t v;
-  __builtin_memcpy(&v, p, 4);
-  return v;
-}
-
-// float32 frame value -> 0..255: round half to even, clamp, NaN -> 0 (both comparisons are false for a NaN)
-__device__ __forceinline__ uint32_t to_u8(float v) {
-  const float r = __builtin_rintf(v);
-  return r >= 0.f ? (r > 255.f ? 255u : (uint32_t)r) : 0u;
-}
-
-// edge of the rule: pixel (Y, X) with label l at q has, within R pixels along an axis and inside the picture, a neighbour of another label
-template <int R>
-__device__ __forceinline__ bool edge_at(const unsigned char* q, uint32_t l, int Y, int X, int H, int W) {
-  bool edge = false;
-#pragma unroll
-  for (int d = 1; d <= R; ++d) {
-    if (X - d >= 0) edge |= q[-d] != l;
-    if (X + d < W) edge |= q[d] != l;
-    if (Y - d >= 0) edge |= q[-(long)d * W] != l;
-    if (Y + d < H) edge |= q[(long)d * W] != l;
-  }
-  return edge;
-}
 
 struct TilePos { int f, Y0, X0, th, tw; };                            // frame, origin, in-picture rows and columns of the tile
 
@@ -125,122 +101,140 @@ __device__ __forceinline__ void flag_cells(const TileArgs& a, const TilePos& p, 
 // in-picture rows / columns of cell (cy, cx) of the tile
 __device__ __forceinline__ int cell_extent(int cell, int k, int have) { return have - k * cell < cell ? have - k * cell : cell; }
 
+// A block's LDS: the palette rows (packed by the kernel's format), the action table, and per cell of the tile its flag, sums and mean.
+// A view of five arrays that each kernel declares itself (TILE_LDS): as members of ONE struct in LDS the compiler addressed them
+// differently and the kernels' code was no longer the measured one.
+struct TileLds {
+  uint32_t (&pal)[256];
+  unsigned char (&act)[256];
+  uint32_t (&flag)[MAX_CELLS];
+  uint32_t (&sum)[3][MAX_CELLS];
+  uint32_t (&mean)[MAX_CELLS];
+};
+#define TILE_LDS(name)                                                                                              \
+  __shared__ uint32_t pal[256];                                                                                     \
+  __shared__ unsigned char act[256];                                                                                \
+  __shared__ uint32_t flag[MAX_CELLS];                                                                              \
+  __shared__ uint32_t sum[3][MAX_CELLS];                                                                            \
+  __shared__ uint32_t mean[MAX_CELLS];                                                                              \
+  const TileLds name{pal, act, flag, sum, mean}
+
+// thread tid's share of the prologue (before the first barrier): its palette row, its action, and zeroes
+__device__ __forceinline__ void init_lds(const TileLds& lds, const TileArgs& t, int tid, uint32_t pal_row) {
+  lds.pal[tid] = pal_row;
+  lds.act[tid] = t.action[tid];
+  lds.flag[tid] = 0u;
+  lds.sum[0][tid] = 0u; lds.sum[1][tid] = 0u; lds.sum[2][tid] = 0u;
+}
+
+// What a lane adds up in phase 2, with the wave-shuffle step of the butterfly and the add to the cell's LDS counters.  RGB: channels 0
+// and 2 in one register, channel 1 in another; a surface's luma: one register; its chroma: U | V << 16 in one.
+struct RgbSum {
+  uint32_t v02 = 0u, v1 = 0u;
+  __device__ __forceinline__ void px(uint32_t s) { v02 += s & 0x00FF00FFu; v1 += (s >> 8) & 0xFFu; }
+  __device__ __forceinline__ void shuffle_add(int d) { v02 += (uint32_t)__shfl_xor((int)v02, d); v1 += (uint32_t)__shfl_xor((int)v1, d); }
+  __device__ __forceinline__ void add_to(const TileLds& lds, int ci) const {
+    atomicAdd(&lds.sum[0][ci], v02 & 0xFFFFu);
+    atomicAdd(&lds.sum[1][ci], v1);
+    atomicAdd(&lds.sum[2][ci], v02 >> 16);
+  }
+};
+struct LumaSum {
+  uint32_t v = 0u;
+  __device__ __forceinline__ void shuffle_add(int d) { v += (uint32_t)__shfl_xor((int)v, d); }
+  __device__ __forceinline__ void add_to(const TileLds& lds, int ci) const { atomicAdd(&lds.sum[0][ci], v); }
+};
+struct ChromaSum {
+  uint32_t v = 0u;
+  __device__ __forceinline__ void shuffle_add(int d) { v += (uint32_t)__shfl_xor((int)v, d); }
+  __device__ __forceinline__ void add_to(const TileLds& lds, int ci) const {
+    atomicAdd(&lds.sum[1][ci], v & 0xFFFFu);
+    atomicAdd(&lds.sum[2][ci], v >> 16);
+  }
+};
+
+// phase 2: the sums of the flagged cells over `rows` rows of Q lanes, lane j of a row taking the N consecutive samples from column
+// c = N * j (in the picture while c < cols) as load(r, c) -> V.  SUB = 2: a chroma plane, whose pair (r, c) lies under pixel (2r, 2c).
+// Consecutive lanes are consecutive samples of a row and the `lanes` (a power of two) lanes of a group lie in one row of one cell, so a
+// butterfly of wave shuffles adds them up and the group's first lane -- the smallest column, in the picture if any is -- adds the
+// result to the cell's counters.  m_q: the magic of Q.
+template <int N, int SUB, class V, class Load>
+__device__ __forceinline__ void sum_flagged(const TileArgs& t, const TileLds& lds, int tid, int rows, int cols, int Q, uint32_t m_q, int lanes, Load load) {
+  for (int i0 = 0; i0 < rows * Q; i0 += 256) {                         // (the same trip count for every lane: the shuffles need all of them)
+    const int i = i0 + tid;
+    const int r = mdiv(i, m_q), c = N * (i - r * Q);
+    const int ci = mdiv(SUB * r, t.m_cell) * t.nx + mdiv(SUB * c, t.m_cell);
+    const bool on = i < rows * Q && c < cols && lds.flag[ci] != 0u;
+    if (!__any(on)) continue;                                         // (uniform over the wave)
+    V v;
+    if (on) v = load(r, c);
+    for (int d = 1; d < lanes; d <<= 1) v.shuffle_add(d);
+    if (on && (tid & (lanes - 1)) == 0) v.add_to(lds, ci);
+  }
+}
+
+// phase 3: one thread per flagged cell: (sum + n / 2) / n over the n in-picture samples (> 0: the cell has a flagged pixel), the three
+// means packed BITS apart into the cell's LDS dword.  CHROMA: sums 1 and 2 are over the pairs under the cell, not over its pixels.
+template <int BITS, bool CHROMA>
+__device__ __forceinline__ void cell_means(const TileArgs& t, const TilePos& p, const TileLds& lds, int tid) {
+  if (tid < t.ny * t.nx && lds.flag[tid] != 0u) {
+    const int cy = tid / t.nx, cx = tid - cy * t.nx;
+    const int hh = cell_extent(t.cell, cy, p.th), ww = cell_extent(t.cell, cx, p.tw);
+    const uint32_t n = (uint32_t)(hh * ww), nc = CHROMA ? (uint32_t)(((hh + 1) / 2) * ((ww + 1) / 2)) : n;
+    lds.mean[tid] = (lds.sum[0][tid] + n / 2) / n | (lds.sum[1][tid] + nc / 2) / nc << BITS | (lds.sum[2][tid] + nc / 2) / nc << 2 * BITS;
+  }
+}
+
 // ---- RGB ----------------------------------------------------------------------------------------------------------------------------
 struct MosaicArgs {
   TileArgs t;
-  const void* frames;            // [F, 3, h0, w0] planes, frame stride `frame_stride` elements; unused for KIND 0
-  long frame_stride;
-  long plane;                    // h0 * w0
-  int h0, w0;
+  RgbSource src;
   const unsigned char* palette;  // [256, 3]
   unsigned char* out;            // at frame f_off already: [F, Ho, Wo, 3]
   unsigned head;                 // out address mod 4: groups of 4 pixels start at flat pixels = head (mod 4)
   int ident;
 };
 
-// The source pixel of output pixel (f, Y, X) as c0 | c1 << 8 | c2 << 16.  KIND 0: no frames (black), 1: uint8, 2: float32.
+// the source pixel of output pixel (f, Y, X)
 template <int KIND>
-__device__ __forceinline__ uint32_t source_px(const MosaicArgs& a, int f, int Y, int X) {
-  if (KIND == 0) return 0u;
-  const int sy = a.ident ? Y : (int)((unsigned)Y * (unsigned)a.h0 / (unsigned)a.t.H);
-  const int sx = a.ident ? X : (int)((unsigned)X * (unsigned)a.w0 / (unsigned)a.t.W);
-  const long at = (long)f * a.frame_stride + (long)sy * a.w0 + sx;
-  if (KIND == 1) {
-    const unsigned char* s = (const unsigned char*)a.frames + at;
-    return (uint32_t)s[0] | (uint32_t)s[a.plane] << 8 | (uint32_t)s[2 * a.plane] << 16;
-  }
-  const float* s = (const float*)a.frames + at;
-  return to_u8(s[0]) | to_u8(s[a.plane]) << 8 | to_u8(s[2 * a.plane]) << 16;
-}
-
-// out_c = (s_c * (256 - a) + pal_c * a + 128) >> 8 on a packed pixel, as render.hip's paint: channels 0 and 2 share one multiply
-__device__ __forceinline__ uint32_t tint(uint32_t s, uint32_t pal, bool edge, uint32_t a) {
-  const uint32_t rb = ((s & 0x00FF00FFu) * (256u - a) + (pal & 0x00FF00FFu) * a + 0x00800080u) >> 8 & 0x00FF00FFu;
-  const uint32_t g = (((s >> 8) & 0xFFu) * (256u - a) + ((pal >> 8) & 0xFFu) * a + 128u) & 0xFF00u;
-  return edge ? pal : (rb | g);
+__device__ __forceinline__ uint32_t source_of(const MosaicArgs& a, int f, int Y, int X) {
+  return source_px<KIND>(a.src, a.ident, (long)f * a.src.frame_stride, Y, X, a.t.H, a.t.W);
 }
 
 template <int KIND, int R>
 __global__ __launch_bounds__(256) void render_mosaic_kernel(const MosaicArgs a) {
-  __shared__ uint32_t pal[256];
-  __shared__ unsigned char act[256];
-  __shared__ uint32_t flag[MAX_CELLS];
-  __shared__ uint32_t sum[3][MAX_CELLS];
-  __shared__ uint32_t mean[MAX_CELLS];
+  TILE_LDS(lds);
   const TileArgs& t = a.t;
   const int tid = (int)threadIdx.x;
-  {
-    const unsigned char* q = a.palette + 3 * tid;
-    pal[tid] = (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16;
-    act[tid] = t.action[tid];
-    flag[tid] = 0u;
-    sum[0][tid] = 0u; sum[1][tid] = 0u; sum[2][tid] = 0u;
-  }
+  init_lds(lds, t, tid, pack_rgb(a.palette + 3 * tid));
   __syncthreads();
   const TilePos p = tile_pos(t);
-  flag_cells(t, p, act, flag);
+  flag_cells(t, p, lds.act, lds.flag);
   __syncthreads();
-  // sums of the flagged cells.  G >= 4 (cell a multiple of 4): a lane sums 4 consecutive pixels of a row, which share a cell, and a
-  // group is G / 4 lanes; else one pixel per lane, groups of G = 2
-  if (t.G >= 4) {
-    const int Q = t.TW >> 2, GQ = t.G >> 2;
-    for (int i0 = 0; i0 < p.th * Q; i0 += 256) {                     // (the same trip count for every lane: the shuffles need all of them)
-      const int i = i0 + tid;
-      const int r = mdiv(i, t.m_q), c = 4 * (i - r * Q);
-      const int ci = mdiv(r, t.m_cell) * t.nx + mdiv(c, t.m_cell);
-      const bool on = i < p.th * Q && c < p.tw && flag[ci] != 0u;
-      if (!__any(on)) continue;                                       // (uniform over the wave)
-      uint32_t v02 = 0u, v1 = 0u;
-      if (on) {
-        if (KIND == 1 && a.ident && c + 4 <= p.tw) {
-          const unsigned char* q = (const unsigned char*)a.frames + (long)p.f * a.frame_stride + (long)(p.Y0 + r) * a.w0 + p.X0 + c;
-          v02 = __builtin_amdgcn_sad_u8(ld4(q), 0u, 0u) | __builtin_amdgcn_sad_u8(ld4(q + 2 * a.plane), 0u, 0u) << 16;   // byte sums
-          v1 = __builtin_amdgcn_sad_u8(ld4(q + a.plane), 0u, 0u);
-        } else {
+  // G >= 4 (cell a multiple of 4): a lane sums 4 consecutive pixels of a row, which share a cell, and a group is G / 4 lanes (uint8
+  // frames at the output's size: one v_sad_u8 per plane); else one pixel per lane, groups of G = 2
+  if (t.G >= 4)
+    sum_flagged<4, 1, RgbSum>(t, lds, tid, p.th, p.tw, t.TW >> 2, t.m_q, t.G >> 2, [&](int r, int c) {
+      RgbSum v;
+      if (KIND == 1 && a.ident && c + 4 <= p.tw) {
+        const unsigned char* q = (const unsigned char*)a.src.frames + (long)p.f * a.src.frame_stride + (long)(p.Y0 + r) * a.src.w0 + p.X0 + c;
+        v.v02 = __builtin_amdgcn_sad_u8(ld4(q), 0u, 0u) | __builtin_amdgcn_sad_u8(ld4(q + 2 * a.src.plane), 0u, 0u) << 16;   // byte sums
+        v.v1 = __builtin_amdgcn_sad_u8(ld4(q + a.src.plane), 0u, 0u);
+      } else {
 #pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (c + k < p.tw) {
-              const uint32_t s = source_px<KIND>(a, p.f, p.Y0 + r, p.X0 + c + k);
-              v02 += s & 0x00FF00FFu; v1 += (s >> 8) & 0xFFu;
-            }
-        }
+        for (int k = 0; k < 4; ++k)
+          if (c + k < p.tw) v.px(source_of<KIND>(a, p.f, p.Y0 + r, p.X0 + c + k));
       }
-      for (int d = 1; d < GQ; d <<= 1) {
-        v02 += (uint32_t)__shfl_xor((int)v02, d);
-        v1 += (uint32_t)__shfl_xor((int)v1, d);
-      }
-      if (on && (tid & (GQ - 1)) == 0) {
-        atomicAdd(&sum[0][ci], v02 & 0xFFFFu);
-        atomicAdd(&sum[1][ci], v1);
-        atomicAdd(&sum[2][ci], v02 >> 16);
-      }
-    }
-  } else
-  for (int i0 = 0; i0 < p.th * t.TW; i0 += 256) {
-    const int i = i0 + tid;
-    const int r = mdiv(i, t.m_tw), c = i - r * t.TW;
-    const int ci = mdiv(r, t.m_cell) * t.nx + mdiv(c, t.m_cell);
-    const bool in = i < p.th * t.TW;
-    const bool on = in && c < p.tw && flag[ci] != 0u;
-    if (!__any(on)) continue;                                         // (uniform over the wave)
-    const uint32_t s = on ? source_px<KIND>(a, p.f, p.Y0 + r, p.X0 + c) : 0u;
-    uint32_t v02 = s & 0x00FF00FFu, v1 = (s >> 8) & 0xFFu;
-    for (int d = 1; d < t.G; d <<= 1) {
-      v02 += (uint32_t)__shfl_xor((int)v02, d);
-      v1 += (uint32_t)__shfl_xor((int)v1, d);
-    }
-    if (on && (tid & (t.G - 1)) == 0) {                               // the group's first lane: the smallest column, in the picture if any is
-      atomicAdd(&sum[0][ci], v02 & 0xFFFFu);
-      atomicAdd(&sum[1][ci], v1);
-      atomicAdd(&sum[2][ci], v02 >> 16);
-    }
-  }
+      return v;
+    });
+  else
+    sum_flagged<1, 1, RgbSum>(t, lds, tid, p.th, p.tw, t.TW, t.m_tw, t.G, [&](int r, int c) {
+      RgbSum v;
+      v.px(source_of<KIND>(a, p.f, p.Y0 + r, p.X0 + c));
+      return v;
+    });
   __syncthreads();
-  if (tid < t.ny * t.nx && flag[tid] != 0u) {
-    const int cy = tid / t.nx, cx = tid - cy * t.nx;
-    const uint32_t n = (uint32_t)(cell_extent(t.cell, cy, p.th) * cell_extent(t.cell, cx, p.tw));   // (> 0: the cell has a flagged pixel)
-    mean[tid] = (sum[0][tid] + n / 2) / n | (sum[1][tid] + n / 2) / n << 8 | (sum[2][tid] + n / 2) / n << 16;
-  }
+  cell_means<8, false>(t, p, lds, tid);
   __syncthreads();
   // paint: item j of tile row r is the j-th group of 4 flat pixels that meets the row's segment
   for (int it = tid; it < p.th * t.items; it += 256) {
@@ -257,8 +251,8 @@ __global__ __launch_bounds__(256) void render_mosaic_kernel(const MosaicArgs a) 
     const bool wide_src = KIND == 1 && whole && a.ident;
     if (whole) l4 = ld4(t.labels + ps);
     if (wide_src) {
-      const unsigned char* q = (const unsigned char*)a.frames + (long)p.f * a.frame_stride + (long)Y * a.w0 + (int)(ps - row);
-      c0 = ld4(q); c1 = ld4(q + a.plane); c2 = ld4(q + 2 * a.plane);
+      const unsigned char* q = (const unsigned char*)a.src.frames + (long)p.f * a.src.frame_stride + (long)Y * a.src.w0 + (int)(ps - row);
+      c0 = ld4(q); c1 = ld4(q + a.src.plane); c2 = ld4(q + 2 * a.src.plane);
     }
     uint32_t px[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -267,14 +261,14 @@ __global__ __launch_bounds__(256) void render_mosaic_kernel(const MosaicArgs a) 
       if (q < lo || q >= hi) continue;
       const int X = (int)(q - row);
       const uint32_t l = whole ? (l4 >> 8 * k) & 0xFFu : (uint32_t)t.labels[q];
-      const uint32_t ac = act[l];
+      const uint32_t ac = lds.act[l];
       if (ac == 2u) {
-        px[k] = mean[cyn + mdiv(X - p.X0, t.m_cell)];
+        px[k] = lds.mean[cyn + mdiv(X - p.X0, t.m_cell)];
         continue;
       }
       const uint32_t s = wide_src ? ((c0 >> 8 * k) & 0xFFu) | ((c1 >> 8 * k) & 0xFFu) << 8 | ((c2 >> 8 * k) & 0xFFu) << 16
-                                  : source_px<KIND>(a, p.f, Y, X);
-      px[k] = ac == 0u ? s : tint(s, pal[l], edge_at<R>(t.labels + q, l, Y, X, t.H, t.W), t.a256);
+                                  : source_of<KIND>(a, p.f, Y, X);
+      px[k] = ac == 0u ? s : tint(s, lds.pal[l], edge_at<R>(t.labels + q, l, Y, X, t.H, t.W), t.a256);
     }
     unsigned char* o = a.out + 3L * ps;
     if (whole) {
@@ -294,12 +288,9 @@ __global__ __launch_bounds__(256) void render_mosaic_kernel(const MosaicArgs a) 
 
 template <int KIND>
 void launch_mosaic(int contour, dim3 grid, hipStream_t stream, const MosaicArgs& a) {
-  switch (contour) {
-    case 0: hipLaunchKernelGGL((render_mosaic_kernel<KIND, 0>), grid, dim3(256), 0, stream, a); break;
-    case 1: hipLaunchKernelGGL((render_mosaic_kernel<KIND, 1>), grid, dim3(256), 0, stream, a); break;
-    case 2: hipLaunchKernelGGL((render_mosaic_kernel<KIND, 2>), grid, dim3(256), 0, stream, a); break;
-    default: hipLaunchKernelGGL((render_mosaic_kernel<KIND, 3>), grid, dim3(256), 0, stream, a); break;
-  }
+  with_contour(contour, [&](auto R) {
+    hipLaunchKernelGGL((render_mosaic_kernel<KIND, decltype(R)::value>), grid, dim3(256), 0, stream, a);
+  });
 }
 
 // the tile part of a launch's arguments; -> the number of tiles
@@ -333,23 +324,6 @@ struct MosaicYuvArgs {
   long y_pitch, y_stride, uv_pitch, uv_stride;   // bytes
   long oy_pitch, oy_stride, ouv_pitch, ouv_stride;
 };
-
-template <int FMT>
-__device__ __forceinline__ uint32_t row_raw(const unsigned char* row, int i) {
-  return FMT == 0 ? (uint32_t)row[i] : (uint32_t)((const unsigned short*)row)[i];
-}
-template <int FMT>
-__device__ __forceinline__ void row_put(unsigned char* row, int i, uint32_t raw) {
-  if (FMT == 0) row[i] = (unsigned char)raw; else ((unsigned short*)row)[i] = (unsigned short)raw;
-}
-template <int FMT> __device__ __forceinline__ uint32_t value_of(uint32_t raw) { return FMT == 0 ? raw : raw >> 6; }
-template <int FMT> __device__ __forceinline__ uint32_t stored(uint32_t v) { return FMT == 0 ? v : v << 6; }
-template <int FMT> __device__ __forceinline__ uint32_t comp(uint32_t c, int k) { return (c >> 10 * k) & (FMT ? 0x3FFu : 0xFFu); }
-
-// tinted value of the rule: the palette component on an edge, else the blend.  s, p <= 1023: s * (256 - a) + p * a + 128 < 2^19.
-__device__ __forceinline__ uint32_t tint1(uint32_t s, uint32_t p, bool edge, uint32_t a) {
-  return edge ? p : (s * (256u - a) + p * a + 128u) >> 8;
-}
 
 // One 2 x 2 block (columns c, c + 1 of rows r0, r0 + 1; nr x nc of them in the picture): the rule as written, on stored samples ry, ru,
 // rv handed in and the block's labels read at `lab` (the label of (r0, c)).  m: the packed means of the block's cell.
@@ -390,20 +364,10 @@ __device__ __forceinline__ void block2x2(const TileArgs& t, const uint32_t* pal,
 
 template <int FMT, int PX, int R>
 __global__ __launch_bounds__(256) void render_mosaic_yuv_kernel(const MosaicYuvArgs a) {
-  __shared__ uint32_t pal[256];
-  __shared__ unsigned char act[256];
-  __shared__ uint32_t flag[MAX_CELLS];
-  __shared__ uint32_t sum[3][MAX_CELLS];
-  __shared__ uint32_t mean[MAX_CELLS];
+  TILE_LDS(lds);
   const TileArgs& t = a.t;
   const int tid = (int)threadIdx.x;
-  {
-    const unsigned short* q = a.palette + 3 * tid;
-    pal[tid] = ((uint32_t)q[0] & 0x3FFu) | ((uint32_t)q[1] & 0x3FFu) << 10 | ((uint32_t)q[2] & 0x3FFu) << 20;
-    act[tid] = t.action[tid];
-    flag[tid] = 0u;
-    sum[0][tid] = 0u; sum[1][tid] = 0u; sum[2][tid] = 0u;
-  }
+  init_lds(lds, t, tid, pack_yuv(a.palette + 3 * tid));
   __syncthreads();
   const TilePos p = tile_pos(t);
   constexpr int BPS = FMT ? 2 : 1;                                   // bytes per sample
@@ -412,71 +376,38 @@ __global__ __launch_bounds__(256) void render_mosaic_yuv_kernel(const MosaicYuvA
   unsigned char* oy0 = a.oy + p.f * a.oy_stride + (long)p.Y0 * a.oy_pitch + (long)p.X0 * BPS;
   unsigned char* oc0 = a.ouv + p.f * a.ouv_stride + (long)(p.Y0 / 2) * a.ouv_pitch + (long)p.X0 * BPS;
   const unsigned char* lab0 = t.labels + ((long)p.f * t.H + p.Y0) * t.W + p.X0;
-  flag_cells(t, p, act, flag);
+  flag_cells(t, p, lds.act, lds.flag);
   __syncthreads();
-  // luma sums of the flagged cells, 4 samples per lane where cell is a multiple of 4 (as the RGB kernel's)
-  if (t.G >= 4) {
-    const int Q = t.TW >> 2, GQ = t.G >> 2;
-    for (int i0 = 0; i0 < p.th * Q; i0 += 256) {
-      const int i = i0 + tid;
-      const int r = mdiv(i, t.m_q), c = 4 * (i - r * Q);
-      const int ci = mdiv(r, t.m_cell) * t.nx + mdiv(c, t.m_cell);
-      const bool on = i < p.th * Q && c < p.tw && flag[ci] != 0u;
-      if (!__any(on)) continue;
-      uint32_t v = 0u;
-      if (on) {
-        const unsigned char* q = y0 + (long)r * a.y_pitch;
-        if (PX == 4) {                                                // (aligned, and tw is a multiple of 4)
-          uint32_t w[BPS];
-          __builtin_memcpy(w, __builtin_assume_aligned(q + (long)c * BPS, 4), 4 * BPS);
-          if (FMT == 0) v = __builtin_amdgcn_sad_u8(w[0], 0u, 0u);
-          else v = ((w[0] & 0xFFFFu) >> 6) + (w[0] >> 22) + ((w[BPS - 1] & 0xFFFFu) >> 6) + (w[BPS - 1] >> 22);
-        } else {
+  // luma: 4 samples per lane where cell is a multiple of 4, as the RGB kernel's (an aligned launch, whose tw is a multiple of 4, reads
+  // them as one dword -- one v_sad_u8 -- or as P010's dword pair)
+  if (t.G >= 4)
+    sum_flagged<4, 1, LumaSum>(t, lds, tid, p.th, p.tw, t.TW >> 2, t.m_q, t.G >> 2, [&](int r, int c) {
+      LumaSum v;
+      const unsigned char* q = y0 + (long)r * a.y_pitch;
+      if (PX == 4) {
+        uint32_t w[BPS];
+        __builtin_memcpy(w, __builtin_assume_aligned(q + (long)c * BPS, 4), 4 * BPS);
+        if (FMT == 0) v.v = __builtin_amdgcn_sad_u8(w[0], 0u, 0u);
+        else v.v = ((w[0] & 0xFFFFu) >> 6) + (w[0] >> 22) + ((w[BPS - 1] & 0xFFFFu) >> 6) + (w[BPS - 1] >> 22);
+      } else {
 #pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (c + k < p.tw) v += value_of<FMT>(row_raw<FMT>(q, c + k));
-        }
+        for (int k = 0; k < 4; ++k)
+          if (c + k < p.tw) v.v += value_of<FMT>(row_raw<FMT>(q, c + k));
       }
-      for (int d = 1; d < GQ; d <<= 1) v += (uint32_t)__shfl_xor((int)v, d);
-      if (on && (tid & (GQ - 1)) == 0) atomicAdd(&sum[0][ci], v);
-    }
-  } else
-  for (int i0 = 0; i0 < p.th * t.TW; i0 += 256) {
-    const int i = i0 + tid;
-    const int r = mdiv(i, t.m_tw), c = i - r * t.TW;
-    const int ci = mdiv(r, t.m_cell) * t.nx + mdiv(c, t.m_cell);
-    const bool on = i < p.th * t.TW && c < p.tw && flag[ci] != 0u;
-    if (!__any(on)) continue;
-    uint32_t v = on ? value_of<FMT>(row_raw<FMT>(y0 + (long)r * a.y_pitch, c)) : 0u;
-    for (int d = 1; d < t.G; d <<= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    if (on && (tid & (t.G - 1)) == 0) atomicAdd(&sum[0][ci], v);
-  }
-  // chroma sums: the pairs under the same cells, groups of G / 2 lanes
-  const int chr = (p.th + 1) / 2, chc = (p.tw + 1) / 2, HTW = t.TW / 2, GC = t.G / 2;
-  for (int i0 = 0; i0 < chr * HTW; i0 += 256) {
-    const int i = i0 + tid;
-    const int r = mdiv(i, t.m_htw), c = i - r * HTW;
-    const int ci = mdiv(2 * r, t.m_cell) * t.nx + mdiv(2 * c, t.m_cell);
-    const bool on = i < chr * HTW && c < chc && flag[ci] != 0u;
-    if (!__any(on)) continue;
-    uint32_t v = 0u;
-    if (on) {
-      const unsigned char* q = c0p + (long)r * a.uv_pitch;
-      v = value_of<FMT>(row_raw<FMT>(q, 2 * c)) | value_of<FMT>(row_raw<FMT>(q, 2 * c + 1)) << 16;
-    }
-    for (int d = 1; d < GC; d <<= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    if (on && (tid & (GC - 1)) == 0) {                                // (G >= 2: GC >= 1)
-      atomicAdd(&sum[1][ci], v & 0xFFFFu);
-      atomicAdd(&sum[2][ci], v >> 16);
-    }
-  }
+      return v;
+    });
+  else
+    sum_flagged<1, 1, LumaSum>(t, lds, tid, p.th, p.tw, t.TW, t.m_tw, t.G, [&](int r, int c) {
+      return LumaSum{value_of<FMT>(row_raw<FMT>(y0 + (long)r * a.y_pitch, c))};
+    });
+  // chroma: the pairs under the same cells, groups of G / 2 lanes (G >= 2)
+  const int chr = (p.th + 1) / 2, chc = (p.tw + 1) / 2;
+  sum_flagged<1, 2, ChromaSum>(t, lds, tid, chr, chc, t.TW / 2, t.m_htw, t.G / 2, [&](int r, int c) {
+    const unsigned char* q = c0p + (long)r * a.uv_pitch;
+    return ChromaSum{value_of<FMT>(row_raw<FMT>(q, 2 * c)) | value_of<FMT>(row_raw<FMT>(q, 2 * c + 1)) << 16};
+  });
   __syncthreads();
-  if (tid < t.ny * t.nx && flag[tid] != 0u) {
-    const int cy = tid / t.nx, cx = tid - cy * t.nx;
-    const int hh = cell_extent(t.cell, cy, p.th), ww = cell_extent(t.cell, cx, p.tw);
-    const uint32_t n = (uint32_t)(hh * ww), nc = (uint32_t)(((hh + 1) / 2) * ((ww + 1) / 2));
-    mean[tid] = (sum[0][tid] + n / 2) / n | (sum[1][tid] + nc / 2) / nc << 10 | (sum[2][tid] + nc / 2) / nc << 20;
-  }
+  cell_means<10, true>(t, p, lds, tid);
   __syncthreads();
   // paint: item j of row pair rp is the block of 2 rows x PX pixels at column PX * j of the tile
   for (int it = tid; it < chr * t.items; it += 256) {
@@ -509,7 +440,7 @@ __global__ __launch_bounds__(256) void render_mosaic_yuv_kernel(const MosaicYuvA
         }
         const uint32_t ru = FMT == 0 ? (cw[0] >> 16 * q) & 0xFFu : cw[q] & 0xFFFFu;
         const uint32_t rv = FMT == 0 ? (cw[0] >> (16 * q + 8)) & 0xFFu : cw[q] >> 16;
-        block2x2<FMT, R>(t, pal, act, mean[cyn + mdiv(cb + 2 * q, t.m_cell)], lab + 2 * q, r0, c0 + 2 * q, nr, 2, ry, ru, rv, o, ou, ov);
+        block2x2<FMT, R>(t, lds.pal, lds.act, lds.mean[cyn + mdiv(cb + 2 * q, t.m_cell)], lab + 2 * q, r0, c0 + 2 * q, nr, 2, ry, ru, rv, o, ou, ov);
         if (FMT == 0) {
 #pragma unroll
           for (int row = 0; row < 2; ++row) {
@@ -535,7 +466,7 @@ __global__ __launch_bounds__(256) void render_mosaic_yuv_kernel(const MosaicYuvA
         for (int k = 0; k < 2; ++k)
           if (row < nr && k < nc) ry[row][k] = row_raw<FMT>(yrow + (long)row * a.y_pitch, cb + k);
       const uint32_t ru = row_raw<FMT>(crow, cb), rv = row_raw<FMT>(crow, cb + 1);
-      block2x2<FMT, R>(t, pal, act, mean[cyn + mdiv(cb, t.m_cell)], lab, r0, c0, nr, nc, ry, ru, rv, o, ou, ov);
+      block2x2<FMT, R>(t, lds.pal, lds.act, lds.mean[cyn + mdiv(cb, t.m_cell)], lab, r0, c0, nr, nc, ry, ru, rv, o, ou, ov);
 #pragma unroll
       for (int row = 0; row < 2; ++row)
 #pragma unroll
@@ -549,12 +480,9 @@ __global__ __launch_bounds__(256) void render_mosaic_yuv_kernel(const MosaicYuvA
 
 template <int FMT, int PX>
 void launch_my(int contour, dim3 grid, hipStream_t stream, const MosaicYuvArgs& a) {
-  switch (contour) {
-    case 0: hipLaunchKernelGGL((render_mosaic_yuv_kernel<FMT, PX, 0>), grid, dim3(256), 0, stream, a); break;
-    case 1: hipLaunchKernelGGL((render_mosaic_yuv_kernel<FMT, PX, 1>), grid, dim3(256), 0, stream, a); break;
-    case 2: hipLaunchKernelGGL((render_mosaic_yuv_kernel<FMT, PX, 2>), grid, dim3(256), 0, stream, a); break;
-    default: hipLaunchKernelGGL((render_mosaic_yuv_kernel<FMT, PX, 3>), grid, dim3(256), 0, stream, a); break;
-  }
+  with_contour(contour, [&](auto R) {
+    hipLaunchKernelGGL((render_mosaic_yuv_kernel<FMT, PX, decltype(R)::value>), grid, dim3(256), 0, stream, a);
+  });
 }
 
 bool cell_ok(int cell) { return cell >= 2 && cell <= 64 && (cell & 1) == 0; }
@@ -565,33 +493,17 @@ extern "C" int mdqe_render_mosaic_u8(const void* frames, int is_u8, long frame_s
                                      const unsigned char* labels, int F, int Ho, int Wo,
                                      const unsigned char* palette, const unsigned char* action, int a256, int contour, int cell,
                                      unsigned char* out, int f_off, void* stream) {
-  MDQE_REQUIRE(a256 >= 0 && a256 <= 256 && contour >= 0 && contour <= 3 && cell_ok(cell));
-  MDQE_REQUIRE(F >= 0 && Ho > 0 && Wo > 0 && f_off >= 0 && (long)Ho * Wo * 3 < 0x7FFFFFFFL);
-  MDQE_REQUIRE((long)F * Ho * Wo < 0x7FFFFFFFL);                     // the flat pixel index of one call is 32-bit
-  if (frames != nullptr) {
-    MDQE_REQUIRE(h0 > 0 && w0 > 0 && (long)h0 * Ho < 0x7FFFFFFFL && (long)w0 * Wo < 0x7FFFFFFFL);   // (Y * h0, X * w0 in 32 bits)
-    MDQE_REQUIRE(frame_stride >= 3L * h0 * w0 || F <= 1);
-  }
-  if (F == 0) return MDQE_OK;
-  MDQE_CHECK_PTR(labels);
-  MDQE_CHECK_PTR(palette);
-  MDQE_CHECK_PTR(action);
-  MDQE_CHECK_PTR(out);
+  MDQE_REQUIRE(cell_ok(cell));
   MosaicArgs a;
+  const int st = rgb_call(frames, frame_stride, h0, w0, labels, F, Ho, Wo, palette, action, true, a256, contour, out, f_off, a.src, a.ident, a.out);
+  if (st != MDQE_OK || F == 0) return st;
   const long tiles = tile_args(a.t, labels, action, F, Ho, Wo, cell, a256);
-  a.frames = frames;
-  a.frame_stride = frame_stride;
-  a.h0 = frames ? h0 : 1;
-  a.w0 = frames ? w0 : 1;
-  a.plane = (long)a.h0 * a.w0;
   a.palette = palette;
-  a.out = out + (long)f_off * Ho * Wo * 3;
   a.head = (unsigned)((uintptr_t)a.out & 3u);
   // a segment of TW pixels meets at most TW / 4 + 1 groups; exactly TW / 4 where every segment starts a group (Wo and the tiles'
   // width are multiples of 4 and so is the output address)
   a.t.items = a.t.TW / 4 + ((Wo & 3) == 0 && a.head == 0 ? 0 : 1);
   a.t.m_items = magic(a.t.items);
-  a.ident = frames != nullptr && h0 == Ho && w0 == Wo;
   mdqe_clear_error();
   const dim3 grid((unsigned)tiles);
   if (frames == nullptr) launch_mosaic<0>(contour, grid, (hipStream_t)stream, a);
@@ -605,43 +517,14 @@ extern "C" int mdqe_render_mosaic_yuv420sp(const void* y, long y_pitch, long y_s
                                            const unsigned short* palette_yuv, const unsigned char* action, int a256, int contour, int cell,
                                            void* out_y, long out_y_pitch, long out_y_stride,
                                            void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream) {
-  MDQE_REQUIRE(a256 >= 0 && a256 <= 256 && contour >= 0 && contour <= 3 && cell_ok(cell));
-  MDQE_REQUIRE(F >= 0 && H > 0 && W > 0 && f_off >= 0 && (fmt == 0 || fmt == 1));
-  const long bps = fmt ? 2 : 1, yb = bps * W, cb = bps * 2 * ((W + 1L) / 2), CH = (H + 1L) / 2;
-  MDQE_REQUIRE(y_pitch >= yb && uv_pitch >= cb && y_stride >= 0 && uv_stride >= 0);
-  MDQE_REQUIRE(out_y_pitch >= yb && out_uv_pitch >= cb && out_y_stride >= 0 && out_uv_stride >= 0);
-  if (fmt == 1)
-    MDQE_REQUIRE(((y_pitch | y_stride | uv_pitch | uv_stride | out_y_pitch | out_y_stride | out_uv_pitch | out_uv_stride) & 1L) == 0);
-  // (two output surfaces that shared bytes would have two writers)
-  if (F > 1) MDQE_REQUIRE(out_y_stride >= (H - 1) * out_y_pitch + yb && out_uv_stride >= (CH - 1) * out_uv_pitch + cb);
-  MDQE_REQUIRE((long)F * H * W < 0x7FFFFFFFL);
-  if (F == 0) return MDQE_OK;
-  MDQE_CHECK_PTR(y);
-  MDQE_CHECK_PTR(uv);
-  MDQE_CHECK_PTR(labels);
-  MDQE_CHECK_PTR(palette_yuv);
-  MDQE_CHECK_PTR(action);
-  MDQE_CHECK_PTR(out_y);
-  MDQE_CHECK_PTR(out_uv);
-  MDQE_REQUIRE(((uintptr_t)palette_yuv & 1u) == 0);
-  if (fmt == 1) MDQE_REQUIRE((((uintptr_t)y | (uintptr_t)uv | (uintptr_t)out_y | (uintptr_t)out_uv) & 1u) == 0);
-  unsigned char* oy = (unsigned char*)out_y + (long)f_off * out_y_stride;
-  unsigned char* ouv = (unsigned char*)out_uv + (long)f_off * out_uv_stride;
-  {
-    // a cell's mean reads samples that other threads write: no output plane may meet an input plane (not in place either), the other
-    // output plane, the labels, the palette or the action table
-    const Plane sy = plane_of(y, y_pitch, y_stride, F, H, yb), sc = plane_of(uv, uv_pitch, uv_stride, F, CH, cb);
-    const Plane ty = plane_of(oy, out_y_pitch, out_y_stride, F, H, yb), tc = plane_of(ouv, out_uv_pitch, out_uv_stride, F, CH, cb);
-    const Plane sl = plane_of(labels, W, (long)H * W, F, H, W), sp = plane_of(palette_yuv, 6, 0, 1, 256, 6);
-    const Plane sa = plane_of(action, 256, 0, 1, 1, 256);
-    MDQE_REQUIRE(apart(sy, ty) && apart(sc, tc) && apart(sy, tc) && apart(sc, ty) && apart(ty, tc));
-    MDQE_REQUIRE(apart(sl, ty) && apart(sl, tc) && apart(sp, ty) && apart(sp, tc) && apart(sa, ty) && apart(sa, tc));
-  }
-  // 4-byte accesses where every address of the launch is aligned for them (strides matter only between surfaces)
-  uintptr_t m = (uintptr_t)y | (uintptr_t)uv | (uintptr_t)oy | (uintptr_t)ouv | (uintptr_t)labels | (uintptr_t)W
-              | (uintptr_t)y_pitch | (uintptr_t)uv_pitch | (uintptr_t)out_y_pitch | (uintptr_t)out_uv_pitch;
-  if (F > 1) m |= (uintptr_t)y_stride | (uintptr_t)uv_stride | (uintptr_t)out_y_stride | (uintptr_t)out_uv_stride | (uintptr_t)((long)H * W);
-  const int px = (m & 3u) == 0 ? 4 : 2;
+  MDQE_REQUIRE(cell_ok(cell));
+  // not in place: a cell's mean reads samples that other threads write
+  SurfaceOut o;
+  const int st = surface_call(y, y_pitch, y_stride, uv, uv_pitch, uv_stride, F, H, W, fmt, labels, palette_yuv, action, true, false, a256,
+                              contour, out_y, out_y_pitch, out_y_stride, out_uv, out_uv_pitch, out_uv_stride, f_off, o);
+  if (st != MDQE_OK || F == 0) return st;
+  // 4-byte accesses where every address of the launch is aligned for them
+  const int px = (o.m & 3u) == 0 ? 4 : 2;
   MosaicYuvArgs a;
   const long tiles = tile_args(a.t, labels, action, F, H, W, cell, a256);
   a.t.items = a.t.TW / px;                                            // (TW is a multiple of 4)
@@ -649,8 +532,8 @@ extern "C" int mdqe_render_mosaic_yuv420sp(const void* y, long y_pitch, long y_s
   a.y = (const unsigned char*)y;
   a.uv = (const unsigned char*)uv;
   a.palette = palette_yuv;
-  a.oy = oy;
-  a.ouv = ouv;
+  a.oy = o.oy;
+  a.ouv = o.ouv;
   a.y_pitch = y_pitch; a.y_stride = y_stride; a.uv_pitch = uv_pitch; a.uv_stride = uv_stride;
   a.oy_pitch = out_y_pitch; a.oy_stride = out_y_stride; a.ouv_pitch = out_uv_pitch; a.ouv_stride = out_uv_stride;
   mdqe_clear_error();

@@ -24,8 +24,9 @@
 // No clamp is needed anywhere: a blend lies between its two operands and a rounded mean between its smallest and largest term.  The
 // shifts are plain shifts of non-negative 32-bit values, each followed by a mask or a select, never a shift-then-clamp pair (see the
 // note above clamp8 in yuv.hip); the exact comparisons of tests/test_overlay_yuv_gpu.py are the guard.
-#include "common.h"
-#include "render_planes.h"
+// The rule's pieces (sample helpers, tint, contour test and dispatch) and the entry's checks, the overlap test among them, are
+// render_rule.h's, shared with the other painters; the chunk helpers of the wide path are this file's own.
+#include "render_rule.h"
 
 namespace {
 
@@ -68,32 +69,13 @@ __device__ __forceinline__ void chunk_put(uint32_t* w, int i, uint32_t raw) {
   }
 }
 
-// stored sample i of a plane row in memory, and its store
-template <int FMT>
-__device__ __forceinline__ uint32_t row_raw(const unsigned char* row, int i) {
-  return FMT == 0 ? (uint32_t)row[i] : (uint32_t)((const unsigned short*)row)[i];
-}
-
-template <int FMT>
-__device__ __forceinline__ void row_put(unsigned char* row, int i, uint32_t raw) {
-  if (FMT == 0) row[i] = (unsigned char)raw; else ((unsigned short*)row)[i] = (unsigned short)raw;
-}
-
-// the value of a stored sample, and the stored form of a value the rule produced
-template <int FMT> __device__ __forceinline__ uint32_t value_of(uint32_t raw) { return FMT == 0 ? raw : raw >> 6; }
-template <int FMT> __device__ __forceinline__ uint32_t stored(uint32_t v) { return FMT == 0 ? v : v << 6; }
-
-// px(s, p) of the rule: background keeps the sample, a contour pixel takes the palette component, the rest blends.  s, p <= 1023:
-// s * (256 - a) + p * a + 128 <= 1023 * 256 + 128 < 2^19.
+// px(s, p) of the rule: background keeps the sample, a contour pixel takes the palette component, the rest blends.  (tint1 with the
+// blend taken first and both selects after it: written this way the compiler emits the kernels profiles/overlay_surface_ab.txt measured.)
 __device__ __forceinline__ uint32_t px(uint32_t s, uint32_t p, uint32_t l, bool edge, uint32_t a) {
-  const uint32_t b = (s * (256u - a) + p * a + 128u) >> 8;
+  const uint32_t b = blend1(s, p, a);
   const uint32_t o = edge ? p : b;
   return l != 0u ? o : s;
 }
-
-template <int FMT> __device__ __forceinline__ uint32_t pal_y(uint32_t c) { return c & (FMT ? 0x3FFu : 0xFFu); }
-template <int FMT> __device__ __forceinline__ uint32_t pal_u(uint32_t c) { return (c >> 10) & (FMT ? 0x3FFu : 0xFFu); }
-template <int FMT> __device__ __forceinline__ uint32_t pal_v(uint32_t c) { return (c >> 20) & (FMT ? 0x3FFu : 0xFFu); }
 
 // One 2 x 2 block (columns c, c + 1 of rows r0, r0 + 1; c even, c < W, r0 < H) with every bound checked: the rule as written.  `lab` is
 // the label of (r0, c), yrow / oyrow row r0 of the luma planes, crow / ocrow the chroma row of the pair.
@@ -108,20 +90,13 @@ __device__ __forceinline__ void paint_block(const RenderYuvArgs& a, const uint32
       const int Y = r0 + row, X = c + k;
       const unsigned char* q = lab + (long)row * a.W + k;
       const uint32_t l = q[0];
-      bool edge = false;
-#pragma unroll
-      for (int d = 1; d <= R; ++d) {
-        if (X - d >= 0) edge |= q[-d] != l;
-        if (X + d < a.W) edge |= q[d] != l;
-        if (Y - d >= 0) edge |= q[-(long)d * a.W] != l;
-        if (Y + d < a.H) edge |= q[(long)d * a.W] != l;
-      }
+      const bool edge = edge_at<R>(q, l, Y, X, a.H, a.W);
       const uint32_t col = pal[l];
       const uint32_t ry = row_raw<FMT>(yrow + (long)row * a.y_pitch, X);
-      const uint32_t yo = px(value_of<FMT>(ry), pal_y<FMT>(col), l, edge, a.a256);
+      const uint32_t yo = px(value_of<FMT>(ry), comp<FMT>(col, 0), l, edge, a.a256);
       row_put<FMT>(oyrow + (long)row * a.oy_pitch, X, l != 0u ? stored<FMT>(yo) : ry);
-      su += px(U, pal_u<FMT>(col), l, edge, a.a256);
-      sv += px(V, pal_v<FMT>(col), l, edge, a.a256);
+      su += px(U, comp<FMT>(col, 1), l, edge, a.a256);
+      sv += px(V, comp<FMT>(col, 2), l, edge, a.a256);
       any |= l;
       ++n;
     }
@@ -136,10 +111,7 @@ __device__ __forceinline__ void paint_block(const RenderYuvArgs& a, const uint32
 template <int FMT, int PX, int R>
 __global__ __launch_bounds__(256) void render_overlay_yuv_kernel(const RenderYuvArgs a) {
   __shared__ uint32_t pal[256];
-  {
-    const unsigned short* q = a.palette + 3 * threadIdx.x;
-    pal[threadIdx.x] = ((uint32_t)q[0] & 0x3FFu) | ((uint32_t)q[1] & 0x3FFu) << 10 | ((uint32_t)q[2] & 0x3FFu) << 20;
-  }
+  pal[threadIdx.x] = pack_yuv(a.palette + 3 * threadIdx.x);
   __syncthreads();
   const unsigned u = blockIdx.x * 256u + threadIdx.x;
   if (u >= a.n_units) return;
@@ -216,10 +188,10 @@ __global__ __launch_bounds__(256) void render_overlay_yuv_kernel(const RenderYuv
           const bool edge = ((diff[row][i >> 2] >> (8 * (i & 3))) & 0xFFu) != 0u;
           const uint32_t col = pal[l];
           const uint32_t ry = chunk_raw<FMT>(yw[row], i);
-          const uint32_t yo = px(value_of<FMT>(ry), pal_y<FMT>(col), l, edge, a.a256);
+          const uint32_t yo = px(value_of<FMT>(ry), comp<FMT>(col, 0), l, edge, a.a256);
           chunk_put<FMT>(oyw[row], i, l != 0u ? stored<FMT>(yo) : ry);
-          su += px(U, pal_u<FMT>(col), l, edge, a.a256);
-          sv += px(V, pal_v<FMT>(col), l, edge, a.a256);
+          su += px(U, comp<FMT>(col, 1), l, edge, a.a256);
+          sv += px(V, comp<FMT>(col, 2), l, edge, a.a256);
           any |= l;
         }
       }
@@ -242,12 +214,9 @@ __global__ __launch_bounds__(256) void render_overlay_yuv_kernel(const RenderYuv
 
 template <int FMT, int PX>
 void launch_r(int contour, dim3 grid, hipStream_t stream, const RenderYuvArgs& a) {
-  switch (contour) {
-    case 0: hipLaunchKernelGGL((render_overlay_yuv_kernel<FMT, PX, 0>), grid, dim3(256), 0, stream, a); break;
-    case 1: hipLaunchKernelGGL((render_overlay_yuv_kernel<FMT, PX, 1>), grid, dim3(256), 0, stream, a); break;
-    case 2: hipLaunchKernelGGL((render_overlay_yuv_kernel<FMT, PX, 2>), grid, dim3(256), 0, stream, a); break;
-    default: hipLaunchKernelGGL((render_overlay_yuv_kernel<FMT, PX, 3>), grid, dim3(256), 0, stream, a); break;
-  }
+  with_contour(contour, [&](auto R) {
+    hipLaunchKernelGGL((render_overlay_yuv_kernel<FMT, PX, decltype(R)::value>), grid, dim3(256), 0, stream, a);
+  });
 }
 
 template <int FMT>
@@ -266,56 +235,24 @@ extern "C" int mdqe_render_overlay_yuv420sp(const void* y, long y_pitch, long y_
                                             const unsigned short* palette_yuv, int a256, int contour,
                                             void* out_y, long out_y_pitch, long out_y_stride,
                                             void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream) {
-  MDQE_REQUIRE(a256 >= 0 && a256 <= 256 && contour >= 0 && contour <= 3);
-  MDQE_REQUIRE(F >= 0 && H > 0 && W > 0 && f_off >= 0 && (fmt == 0 || fmt == 1));
-  const long bps = fmt ? 2 : 1, yb = bps * W, cb = bps * 2 * ((W + 1L) / 2), CH = (H + 1L) / 2;
-  MDQE_REQUIRE(y_pitch >= yb && uv_pitch >= cb && y_stride >= 0 && uv_stride >= 0);
-  MDQE_REQUIRE(out_y_pitch >= yb && out_uv_pitch >= cb && out_y_stride >= 0 && out_uv_stride >= 0);
-  if (fmt == 1)
-    MDQE_REQUIRE(((y_pitch | y_stride | uv_pitch | uv_stride | out_y_pitch | out_y_stride | out_uv_pitch | out_uv_stride) & 1L) == 0);
-  // (two output surfaces that shared bytes would have two writers)
-  if (F > 1) MDQE_REQUIRE(out_y_stride >= (H - 1) * out_y_pitch + yb && out_uv_stride >= (CH - 1) * out_uv_pitch + cb);
-  MDQE_REQUIRE((long)F * H * W < 0x7FFFFFFFL);                       // the block index of one call is 32-bit
-  if (F == 0) return MDQE_OK;
-  MDQE_CHECK_PTR(y);
-  MDQE_CHECK_PTR(uv);
-  MDQE_CHECK_PTR(labels);
-  MDQE_CHECK_PTR(palette_yuv);
-  MDQE_CHECK_PTR(out_y);
-  MDQE_CHECK_PTR(out_uv);
-  MDQE_REQUIRE(((uintptr_t)palette_yuv & 1u) == 0);
-  if (fmt == 1) MDQE_REQUIRE((((uintptr_t)y | (uintptr_t)uv | (uintptr_t)out_y | (uintptr_t)out_uv) & 1u) == 0);
-  unsigned char* oy = (unsigned char*)out_y + (long)f_off * out_y_stride;
-  unsigned char* ouv = (unsigned char*)out_uv + (long)f_off * out_uv_stride;
-  {
-    // in place (an output plane IS its input plane: same address, pitch and stride) or apart; nothing else is a function of the inputs
-    const Plane sy = plane_of(y, y_pitch, y_stride, F, H, yb), sc = plane_of(uv, uv_pitch, uv_stride, F, CH, cb);
-    const Plane ty = plane_of(oy, out_y_pitch, out_y_stride, F, H, yb), tc = plane_of(ouv, out_uv_pitch, out_uv_stride, F, CH, cb);
-    const Plane sl = plane_of(labels, W, (long)H * W, F, H, W), sp = plane_of(palette_yuv, 6, 0, 1, 256, 6);
-    const bool same_y = oy == (const unsigned char*)y && out_y_pitch == y_pitch && (F == 1 || out_y_stride == y_stride);
-    const bool same_c = ouv == (const unsigned char*)uv && out_uv_pitch == uv_pitch && (F == 1 || out_uv_stride == uv_stride);
-    MDQE_REQUIRE(same_y || apart(sy, ty));
-    MDQE_REQUIRE(same_c || apart(sc, tc));
-    MDQE_REQUIRE(apart(sy, tc) && apart(sc, ty) && apart(ty, tc));
-    MDQE_REQUIRE(apart(sl, ty) && apart(sl, tc) && apart(sp, ty) && apart(sp, tc));
-  }
-  // the widest form every address of the launch is aligned for (strides matter only between surfaces)
-  uintptr_t m = (uintptr_t)y | (uintptr_t)uv | (uintptr_t)oy | (uintptr_t)ouv | (uintptr_t)labels | (uintptr_t)W
-              | (uintptr_t)y_pitch | (uintptr_t)uv_pitch | (uintptr_t)out_y_pitch | (uintptr_t)out_uv_pitch;
-  if (F > 1) m |= (uintptr_t)y_stride | (uintptr_t)uv_stride | (uintptr_t)out_y_stride | (uintptr_t)out_uv_stride | (uintptr_t)((long)H * W);
-  const int px = (m & 15u) == 0 && contour == 0 ? 16 : ((m & 3u) == 0 ? 4 : 2);
+  SurfaceOut o;                                                      // in place is accepted: a thread reads only the samples it writes
+  const int st = surface_call(y, y_pitch, y_stride, uv, uv_pitch, uv_stride, F, H, W, fmt, labels, palette_yuv, nullptr, false, true, a256,
+                              contour, out_y, out_y_pitch, out_y_stride, out_uv, out_uv_pitch, out_uv_stride, f_off, o);
+  if (st != MDQE_OK || F == 0) return st;
+  // the widest form every address of the launch is aligned for
+  const int px = (o.m & 15u) == 0 && contour == 0 ? 16 : ((o.m & 3u) == 0 ? 4 : 2);
   RenderYuvArgs a;
   a.y = (const unsigned char*)y;
   a.uv = (const unsigned char*)uv;
   a.labels = labels;
   a.palette = palette_yuv;
-  a.oy = oy;
-  a.ouv = ouv;
+  a.oy = o.oy;
+  a.ouv = o.ouv;
   a.y_pitch = y_pitch; a.y_stride = y_stride; a.uv_pitch = uv_pitch; a.uv_stride = uv_stride;
   a.oy_pitch = out_y_pitch; a.oy_stride = out_y_stride; a.ouv_pitch = out_uv_pitch; a.ouv_stride = out_uv_stride;
   a.H = H; a.W = W;
   a.XU = (unsigned)((W + px - 1) / px);
-  a.RP = (unsigned)CH;
+  a.RP = (unsigned)((H + 1) / 2);
   a.n_units = (unsigned)F * a.RP * a.XU;                             // <= F * H * W < 2^31
   a.a256 = (uint32_t)a256;
   mdqe_clear_error();

@@ -635,6 +635,47 @@ def final_masks_overlap(logits, inst_idx, factor, h, w, Ho, Wo, gt_bits, G, f_of
     return inter, area
 
 
+def _mosaic_args(name, action, cell):
+    if not torch.is_tensor(action) or action.dtype != torch.uint8 or tuple(action.shape) != (256,) or not action.is_contiguous():
+        raise RuntimeError("%s: action must be contiguous uint8 [256] (render.Style.actions)" % name)
+    if isinstance(cell, bool) or not isinstance(cell, int) or not 2 <= cell <= 64 or cell % 2:
+        raise RuntimeError("%s: cell must be an even int in 2..64, got %r" % (name, cell))
+
+
+def _rgb_paint_args(name, labels, frames, palette, out, f_off, a256, contour, mosaic=None):
+    """The checks of render_overlay and of render_mosaic (mosaic = (action, cell)).  -> (F, Ho, Wo, h0, w0, frame stride)."""
+    # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
+    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        raise RuntimeError("%s: labels must be contiguous uint8 [F, Ho, Wo]" % name)
+    F, Ho, Wo = (int(v) for v in labels.shape)
+    if not isinstance(a256, int) or not isinstance(contour, int) or not 0 <= a256 <= 256 or not 0 <= contour <= 3:
+        raise RuntimeError("%s: a256 must be an int in 0..256 and contour an int in 0..3, got %r, %r" % (name, a256, contour))
+    if mosaic is not None:
+        _mosaic_args(name, *mosaic)
+    if Ho < 1 or Wo < 1 or Ho * Wo * 3 >= 2 ** 31 or F * Ho * Wo >= 2 ** 31:
+        raise RuntimeError("%s: Ho, Wo must be positive with Ho*Wo*3 < 2^31 and F*Ho*Wo < 2^31, got %s" % (name, tuple(labels.shape)))
+    if not torch.is_tensor(palette) or palette.dtype != torch.uint8 or tuple(palette.shape) != (256, 3) or not palette.is_contiguous():
+        raise RuntimeError("%s: palette must be contiguous uint8 [256, 3]" % name)
+    if (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 4 or tuple(out.shape[1:]) != (Ho, Wo, 3) or f_off < 0
+            or f_off + F > out.shape[0] or not out.is_contiguous()):
+        raise RuntimeError("%s: out must be contiguous CUDA uint8 [>= f_off + F = %d, Ho, Wo, 3]" % (name, f_off + F))
+    h0 = w0 = stride = 0
+    if frames is not None:
+        if (not torch.is_tensor(frames) or frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4
+                or int(frames.shape[0]) != F or int(frames.shape[1]) != 3 or frames.shape[2] < 1 or frames.shape[3] < 1):
+            raise RuntimeError("%s: frames must be uint8 or float32 [F = %d, 3, h0, w0] or None" % (name, F))
+        h0, w0 = int(frames.shape[2]), int(frames.shape[3])
+        stride = int(frames.stride(0)) if F > 1 else 3 * h0 * w0
+        if tuple(frames.stride()[1:]) != (h0 * w0, w0, 1) or stride < 3 * h0 * w0 or h0 * Ho >= 2 ** 31 or w0 * Wo >= 2 ** 31:
+            raise RuntimeError("%s: every frame must be contiguous and the frames a stride >= 3*h0*w0 apart, got strides %s"
+                               % (name, tuple(frames.stride())))
+    tensors = [(labels, "labels"), (palette, "palette")] + ([(mosaic[0], "action")] if mosaic is not None else []) + [(out, "out"), (frames, "frames")]
+    for t, what in tensors:
+        if t is not None and (not t.is_cuda or t.device != out.device):
+            raise RuntimeError("%s: %s must be a CUDA tensor on out's device, got %s" % (name, what, t.device))
+    return F, Ho, Wo, h0, w0, stride
+
+
 def render_overlay(labels, frames, palette, out, f_off=0, a256=128, contour=1):
     """The picture of a label map: out[f_off + f] (uint8 [>= f_off + F, Ho, Wo, 3], CUDA, contiguous, pixel-interleaved) painted from
     labels (uint8 [F, Ho, Wo], ops.final_label_map's output), frames ([F, 3, h0, w0] uint8 or float32, each frame contiguous, the frames
@@ -642,36 +683,63 @@ def render_overlay(labels, frames, palette, out, f_off=0, a256=128, contour=1):
     order).  Background keeps the frame (nearest-sampled at another size), a labelled pixel becomes (s*(256 - a256) + colour*a256 + 128)
     >> 8, and one with a neighbour of another label within `contour` pixels along an axis, inside the image, the plain colour: the
     integer rule of include/mdqe_hip.h, mdqe_render_overlay_u8.  a256 in 0..256, contour in 0..3.  -> out."""
-    # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
-    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
-        raise RuntimeError("render_overlay: labels must be contiguous uint8 [F, Ho, Wo]")
-    F, Ho, Wo = (int(v) for v in labels.shape)
-    if not isinstance(a256, int) or not isinstance(contour, int) or not 0 <= a256 <= 256 or not 0 <= contour <= 3:
-        raise RuntimeError("render_overlay: a256 must be an int in 0..256 and contour an int in 0..3, got %r, %r" % (a256, contour))
-    if Ho < 1 or Wo < 1 or Ho * Wo * 3 >= 2 ** 31 or F * Ho * Wo >= 2 ** 31:
-        raise RuntimeError("render_overlay: Ho, Wo must be positive with Ho*Wo*3 < 2^31 and F*Ho*Wo < 2^31, got %s" % (tuple(labels.shape),))
-    if not torch.is_tensor(palette) or palette.dtype != torch.uint8 or tuple(palette.shape) != (256, 3) or not palette.is_contiguous():
-        raise RuntimeError("render_overlay: palette must be contiguous uint8 [256, 3]")
-    if (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 4 or tuple(out.shape[1:]) != (Ho, Wo, 3) or f_off < 0
-            or f_off + F > out.shape[0] or not out.is_contiguous()):
-        raise RuntimeError("render_overlay: out must be contiguous CUDA uint8 [>= f_off + F = %d, Ho, Wo, 3]" % (f_off + F))
-    h0 = w0 = stride = 0
-    if frames is not None:
-        if (not torch.is_tensor(frames) or frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4
-                or int(frames.shape[0]) != F or int(frames.shape[1]) != 3 or frames.shape[2] < 1 or frames.shape[3] < 1):
-            raise RuntimeError("render_overlay: frames must be uint8 or float32 [F = %d, 3, h0, w0] or None" % F)
-        h0, w0 = int(frames.shape[2]), int(frames.shape[3])
-        stride = int(frames.stride(0)) if F > 1 else 3 * h0 * w0
-        if tuple(frames.stride()[1:]) != (h0 * w0, w0, 1) or stride < 3 * h0 * w0 or h0 * Ho >= 2 ** 31 or w0 * Wo >= 2 ** 31:
-            raise RuntimeError("render_overlay: every frame must be contiguous and the frames a stride >= 3*h0*w0 apart, got strides %s"
-                               % (tuple(frames.stride()),))
-    for t, name in ((labels, "labels"), (palette, "palette"), (out, "out"), (frames, "frames")):
-        if t is not None and (not t.is_cuda or t.device != out.device):
-            raise RuntimeError("render_overlay: %s must be a CUDA tensor on out's device, got %s" % (name, t.device))
+    F, Ho, Wo, h0, w0, stride = _rgb_paint_args("render_overlay", labels, frames, palette, out, f_off, a256, contour)
     check(lib.mdqe_render_overlay_u8(ptr(frames) if frames is not None else None, int(frames is not None and frames.dtype == torch.uint8),
                                      stride, h0, w0, ptr(labels), F, Ho, Wo, ptr(palette), a256, contour, ptr(out), f_off, cur_stream()),
           "render_overlay")
     return out
+
+
+def render_mosaic(labels, frames, palette, action, out, f_off=0, a256=128, contour=1, cell=16):
+    """`render_overlay` with a per-label action (uint8 [256], action[l]: 0 keep the source, 1 tint as render_overlay does, 2 mosaic;
+    action[0] is the background's): a mosaic pixel becomes the rounded mean of its cell x cell square of the output grid (anchored at
+    (0, 0), over all in-picture source values of the square whatever their labels; cell even, 2..64).  Every other argument is
+    render_overlay's; with action = [0, 1, 1, ...] the picture is render_overlay's bit for bit: the integer rule of
+    include/mdqe_hip.h, mdqe_render_mosaic_u8.  -> out."""
+    F, Ho, Wo, h0, w0, stride = _rgb_paint_args("render_mosaic", labels, frames, palette, out, f_off, a256, contour, (action, cell))
+    check(lib.mdqe_render_mosaic_u8(ptr(frames) if frames is not None else None, int(frames is not None and frames.dtype == torch.uint8),
+                                    stride, h0, w0, ptr(labels), F, Ho, Wo, ptr(palette), ptr(action), a256, contour, cell, ptr(out),
+                                    f_off, cur_stream()), "render_mosaic")
+    return out
+
+
+def _yuv_paint_args(name, labels, yuv, palette_yuv, out, f_off, a256, contour, mosaic=None):
+    """The checks of render_overlay_yuv and of render_mosaic_yuv (mosaic = (action, cell)); allocates `out` when None.
+    -> (F, H, W, out)."""
+    from .preprocess import YuvFrames
+    if not isinstance(yuv, YuvFrames):
+        raise RuntimeError("%s: yuv must be a preprocess.YuvFrames, got %s" % (name, type(yuv).__name__))
+    F, H, W = len(yuv), yuv.height, yuv.width
+    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or tuple(labels.shape) != (F, H, W) or not labels.is_contiguous():
+        raise RuntimeError("%s: labels must be contiguous uint8 [F = %d, H = %d, W = %d] (the surfaces' own size)" % (name, F, H, W))
+    if not isinstance(a256, int) or not isinstance(contour, int) or not 0 <= a256 <= 256 or not 0 <= contour <= 3:
+        raise RuntimeError("%s: a256 must be an int in 0..256 and contour an int in 0..3, got %r, %r" % (name, a256, contour))
+    if mosaic is not None:
+        _mosaic_args(name, *mosaic)
+    if F * H * W >= 2 ** 31 - 1:
+        raise RuntimeError("%s: F*H*W must stay below 2^31 - 1, got %s" % (name, (F, H, W)))
+    if (not torch.is_tensor(palette_yuv) or palette_yuv.dtype not in (torch.uint16, torch.int16) or tuple(palette_yuv.shape) != (256, 3)
+            or not palette_yuv.is_contiguous()):
+        raise RuntimeError("%s: palette_yuv must be contiguous uint16 [256, 3] (render.palette_yuv)" % name)
+    if out is None:
+        out = YuvFrames.empty(f_off + F, H, W, fmt=yuv.fmt, device=yuv.device, matrix=yuv.matrix, full_range=yuv.full_range, order=yuv.order)
+    if (not isinstance(out, YuvFrames) or (out.height, out.width, out.fmt) != (H, W, yuv.fmt) or not isinstance(f_off, int) or f_off < 0
+            or f_off + F > len(out)):
+        raise RuntimeError("%s: out must be a YuvFrames of >= f_off + F = %d surfaces of %d x %d %s" % (name, f_off + F, H, W, yuv.fmt))
+    tensors = [(labels, "labels"), (palette_yuv, "palette_yuv")] + ([(mosaic[0], "action")] if mosaic is not None else []) + [(out, "out")]
+    for t, what in tensors:
+        if t.device != yuv.device:
+            raise RuntimeError("%s: %s must be on the surfaces' device %s, got %s" % (name, what, yuv.device, t.device))
+    return F, H, W, out
+
+
+def _surface_call_args(labels, yuv, palette_yuv, out, F, H, W):
+    """The arguments the two surface entries share: (input planes .. palette), (output planes)."""
+    from .preprocess import YUV_FORMATS, _pitch_stride
+    (yp, ys), (cp, cs) = _pitch_stride(yuv.y), _pitch_stride(yuv.uv)
+    (oyp, oys), (ocp, ocs) = _pitch_stride(out.y), _pitch_stride(out.uv)
+    return ((ptr(yuv.y), yp, ys, ptr(yuv.uv), cp, cs, F, H, W, YUV_FORMATS.index(yuv.fmt), ptr(labels), ptr(palette_yuv)),
+            (ptr(out.y), oyp, oys, ptr(out.uv), ocp, ocs))
 
 
 def render_overlay_yuv(labels, yuv, palette_yuv, out=None, f_off=0, a256=128, contour=1):
@@ -682,124 +750,15 @@ def render_overlay_yuv(labels, yuv, palette_yuv, out=None, f_off=0, a256=128, co
     pixel keeps the decoder's bits (P010: all 16 of a word): the integer rule of include/mdqe_hip.h, mdqe_render_overlay_yuv420sp.
     `out` may be `yuv` itself (in place), nothing else that overlaps it.  On a HIP device one launch on the current stream; on host
     planes the same rule in torch integers.  -> out."""
-    from .preprocess import YUV_FORMATS, YuvFrames, _pitch_stride
-    if not isinstance(yuv, YuvFrames):
-        raise RuntimeError("render_overlay_yuv: yuv must be a preprocess.YuvFrames, got %s" % type(yuv).__name__)
-    F, H, W = len(yuv), yuv.height, yuv.width
-    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or tuple(labels.shape) != (F, H, W) or not labels.is_contiguous():
-        raise RuntimeError("render_overlay_yuv: labels must be contiguous uint8 [F = %d, H = %d, W = %d] (the surfaces' own size)" % (F, H, W))
-    if not isinstance(a256, int) or not isinstance(contour, int) or not 0 <= a256 <= 256 or not 0 <= contour <= 3:
-        raise RuntimeError("render_overlay_yuv: a256 must be an int in 0..256 and contour an int in 0..3, got %r, %r" % (a256, contour))
-    if F * H * W >= 2 ** 31 - 1:
-        raise RuntimeError("render_overlay_yuv: F*H*W must stay below 2^31 - 1, got %s" % ((F, H, W),))
-    if (not torch.is_tensor(palette_yuv) or palette_yuv.dtype not in (torch.uint16, torch.int16) or tuple(palette_yuv.shape) != (256, 3)
-            or not palette_yuv.is_contiguous()):
-        raise RuntimeError("render_overlay_yuv: palette_yuv must be contiguous uint16 [256, 3] (render.palette_yuv)")
-    if out is None:
-        out = YuvFrames.empty(f_off + F, H, W, fmt=yuv.fmt, device=yuv.device, matrix=yuv.matrix, full_range=yuv.full_range, order=yuv.order)
-    if (not isinstance(out, YuvFrames) or (out.height, out.width, out.fmt) != (H, W, yuv.fmt) or not isinstance(f_off, int) or f_off < 0
-            or f_off + F > len(out)):
-        raise RuntimeError("render_overlay_yuv: out must be a YuvFrames of >= f_off + F = %d surfaces of %d x %d %s" % (f_off + F, H, W, yuv.fmt))
-    for t, name in ((labels, "labels"), (palette_yuv, "palette_yuv"), (out, "out")):
-        if t.device != yuv.device:
-            raise RuntimeError("render_overlay_yuv: %s must be on the surfaces' device %s, got %s" % (name, yuv.device, t.device))
+    F, H, W, out = _yuv_paint_args("render_overlay_yuv", labels, yuv, palette_yuv, out, f_off, a256, contour)
     if yuv.is_cuda:
-        (yp, ys), (cp, cs) = _pitch_stride(yuv.y), _pitch_stride(yuv.uv)
-        (oyp, oys), (ocp, ocs) = _pitch_stride(out.y), _pitch_stride(out.uv)
+        src, dst = _surface_call_args(labels, yuv, palette_yuv, out, F, H, W)
         with torch.cuda.device(yuv.device):
-            check(lib.mdqe_render_overlay_yuv420sp(ptr(yuv.y), yp, ys, ptr(yuv.uv), cp, cs, F, H, W, YUV_FORMATS.index(yuv.fmt), ptr(labels),
-                                                   ptr(palette_yuv), a256, contour, ptr(out.y), oyp, oys, ptr(out.uv), ocp, ocs, f_off,
-                                                   cur_stream(yuv.device)), "render_overlay_yuv")
+            check(lib.mdqe_render_overlay_yuv420sp(*src, a256, contour, *dst, f_off, cur_stream(yuv.device)), "render_overlay_yuv")
         return out
     if F == 0:
         return out
-    # host planes: the rule of the header in torch integers
-    p010 = yuv.fmt == "p010"
-    ch, cw = (H + 1) // 2, (W + 1) // 2
-
-    def raw(t):
-        v = t.to(torch.int64)
-        return v & 0xFFFF if p010 else v
-
-    def store(dst, word):
-        dst.copy_(((word + 0x8000) & 0xFFFF) - 0x8000 if p010 else word)
-
-    lab = labels.to(torch.int64)
-    edge = torch.zeros(lab.shape, dtype=torch.bool)
-    for d in range(1, contour + 1):
-        if d < H:
-            edge[:, d:] |= lab[:, d:] != lab[:, :-d]
-            edge[:, :-d] |= lab[:, :-d] != lab[:, d:]
-        if d < W:
-            edge[:, :, d:] |= lab[:, :, d:] != lab[:, :, :-d]
-            edge[:, :, :-d] |= lab[:, :, :-d] != lab[:, :, d:]
-    col = (palette_yuv.view(torch.int16).to(torch.int64) & (0x3FF if p010 else 0xFF))[lab]          # [F, H, W, 3]
-    bg = lab == 0
-
-    def px(s, p):
-        return torch.where(bg, s, torch.where(edge, p, (s * (256 - a256) + p * a256 + 128) >> 8))
-    ry = raw(yuv.y[:, :H, :W])
-    yo = px(ry >> 6 if p010 else ry, col[..., 0])
-    store(out.y[f_off:f_off + F, :H, :W], torch.where(bg, ry, yo << 6 if p010 else yo))
-    rc = raw(yuv.uv[:, :ch, :2 * cw]).reshape(F, ch, cw, 2)
-    c = (rc >> 6 if p010 else rc).repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)[:, :H, :W]
-
-    def blocks(t):                                  # [F, H, W] -> the sum over each 2 x 2 block's in-picture pixels, [F, ch, cw]
-        full = torch.zeros((F, 2 * ch, 2 * cw), dtype=torch.int64)
-        full[:, :H, :W] = t
-        return full.reshape(F, ch, 2, cw, 2).sum((2, 4))
-    n = blocks(torch.ones((F, H, W), dtype=torch.int64))
-    sh = n >> 1                                     # n = 1, 2, 4: n / 2 = log2(n) = 0, 1, 2
-    keep = blocks((~bg).to(torch.int64)) == 0
-    oc = torch.stack([(blocks(px(c[..., k], col[..., k + 1])) + sh) >> sh for k in (0, 1)], -1)
-    word = torch.where(keep[..., None], rc, oc << 6 if p010 else oc)
-    store(out.uv[f_off:f_off + F, :ch, :2 * cw], word.reshape(F, ch, 2 * cw))
-    return out
-
-
-def _mosaic_args(name, action, cell):
-    if not torch.is_tensor(action) or action.dtype != torch.uint8 or tuple(action.shape) != (256,) or not action.is_contiguous():
-        raise RuntimeError("%s: action must be contiguous uint8 [256] (render.Style.actions)" % name)
-    if isinstance(cell, bool) or not isinstance(cell, int) or not 2 <= cell <= 64 or cell % 2:
-        raise RuntimeError("%s: cell must be an even int in 2..64, got %r" % (name, cell))
-
-
-def render_mosaic(labels, frames, palette, action, out, f_off=0, a256=128, contour=1, cell=16):
-    """`render_overlay` with a per-label action (uint8 [256], action[l]: 0 keep the source, 1 tint as render_overlay does, 2 mosaic;
-    action[0] is the background's): a mosaic pixel becomes the rounded mean of its cell x cell square of the output grid (anchored at
-    (0, 0), over all in-picture source values of the square whatever their labels; cell even, 2..64).  Every other argument is
-    render_overlay's; with action = [0, 1, 1, ...] the picture is render_overlay's bit for bit: the integer rule of
-    include/mdqe_hip.h, mdqe_render_mosaic_u8.  -> out."""
-    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
-        raise RuntimeError("render_mosaic: labels must be contiguous uint8 [F, Ho, Wo]")
-    F, Ho, Wo = (int(v) for v in labels.shape)
-    if not isinstance(a256, int) or not isinstance(contour, int) or not 0 <= a256 <= 256 or not 0 <= contour <= 3:
-        raise RuntimeError("render_mosaic: a256 must be an int in 0..256 and contour an int in 0..3, got %r, %r" % (a256, contour))
-    _mosaic_args("render_mosaic", action, cell)
-    if Ho < 1 or Wo < 1 or Ho * Wo * 3 >= 2 ** 31 or F * Ho * Wo >= 2 ** 31:
-        raise RuntimeError("render_mosaic: Ho, Wo must be positive with Ho*Wo*3 < 2^31 and F*Ho*Wo < 2^31, got %s" % (tuple(labels.shape),))
-    if not torch.is_tensor(palette) or palette.dtype != torch.uint8 or tuple(palette.shape) != (256, 3) or not palette.is_contiguous():
-        raise RuntimeError("render_mosaic: palette must be contiguous uint8 [256, 3]")
-    if (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 4 or tuple(out.shape[1:]) != (Ho, Wo, 3) or f_off < 0
-            or f_off + F > out.shape[0] or not out.is_contiguous()):
-        raise RuntimeError("render_mosaic: out must be contiguous CUDA uint8 [>= f_off + F = %d, Ho, Wo, 3]" % (f_off + F))
-    h0 = w0 = stride = 0
-    if frames is not None:
-        if (not torch.is_tensor(frames) or frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4
-                or int(frames.shape[0]) != F or int(frames.shape[1]) != 3 or frames.shape[2] < 1 or frames.shape[3] < 1):
-            raise RuntimeError("render_mosaic: frames must be uint8 or float32 [F = %d, 3, h0, w0] or None" % F)
-        h0, w0 = int(frames.shape[2]), int(frames.shape[3])
-        stride = int(frames.stride(0)) if F > 1 else 3 * h0 * w0
-        if tuple(frames.stride()[1:]) != (h0 * w0, w0, 1) or stride < 3 * h0 * w0 or h0 * Ho >= 2 ** 31 or w0 * Wo >= 2 ** 31:
-            raise RuntimeError("render_mosaic: every frame must be contiguous and the frames a stride >= 3*h0*w0 apart, got strides %s"
-                               % (tuple(frames.stride()),))
-    for t, name in ((labels, "labels"), (palette, "palette"), (action, "action"), (out, "out"), (frames, "frames")):
-        if t is not None and (not t.is_cuda or t.device != out.device):
-            raise RuntimeError("render_mosaic: %s must be a CUDA tensor on out's device, got %s" % (name, t.device))
-    check(lib.mdqe_render_mosaic_u8(ptr(frames) if frames is not None else None, int(frames is not None and frames.dtype == torch.uint8),
-                                    stride, h0, w0, ptr(labels), F, Ho, Wo, ptr(palette), ptr(action), a256, contour, cell, ptr(out),
-                                    f_off, cur_stream()), "render_mosaic")
-    return out
+    return _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour)
 
 
 def _cell_means(v, cell):
@@ -823,35 +782,12 @@ def render_mosaic_yuv(labels, yuv, palette_yuv, action, out=None, f_off=0, a256=
     of include/mdqe_hip.h, mdqe_render_mosaic_yuv420sp.  Not in place: `out` must not share memory with `yuv` (a cell's mean reads
     samples other threads write).  On a HIP device one launch on the current stream; on host planes the same rule in torch
     integers.  -> out."""
-    from .preprocess import YUV_FORMATS, YuvFrames, _pitch_stride
-    if not isinstance(yuv, YuvFrames):
-        raise RuntimeError("render_mosaic_yuv: yuv must be a preprocess.YuvFrames, got %s" % type(yuv).__name__)
-    F, H, W = len(yuv), yuv.height, yuv.width
-    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or tuple(labels.shape) != (F, H, W) or not labels.is_contiguous():
-        raise RuntimeError("render_mosaic_yuv: labels must be contiguous uint8 [F = %d, H = %d, W = %d] (the surfaces' own size)" % (F, H, W))
-    if not isinstance(a256, int) or not isinstance(contour, int) or not 0 <= a256 <= 256 or not 0 <= contour <= 3:
-        raise RuntimeError("render_mosaic_yuv: a256 must be an int in 0..256 and contour an int in 0..3, got %r, %r" % (a256, contour))
-    _mosaic_args("render_mosaic_yuv", action, cell)
-    if F * H * W >= 2 ** 31 - 1:
-        raise RuntimeError("render_mosaic_yuv: F*H*W must stay below 2^31 - 1, got %s" % ((F, H, W),))
-    if (not torch.is_tensor(palette_yuv) or palette_yuv.dtype not in (torch.uint16, torch.int16) or tuple(palette_yuv.shape) != (256, 3)
-            or not palette_yuv.is_contiguous()):
-        raise RuntimeError("render_mosaic_yuv: palette_yuv must be contiguous uint16 [256, 3] (render.palette_yuv)")
-    if out is None:
-        out = YuvFrames.empty(f_off + F, H, W, fmt=yuv.fmt, device=yuv.device, matrix=yuv.matrix, full_range=yuv.full_range, order=yuv.order)
-    if (not isinstance(out, YuvFrames) or (out.height, out.width, out.fmt) != (H, W, yuv.fmt) or not isinstance(f_off, int) or f_off < 0
-            or f_off + F > len(out)):
-        raise RuntimeError("render_mosaic_yuv: out must be a YuvFrames of >= f_off + F = %d surfaces of %d x %d %s" % (f_off + F, H, W, yuv.fmt))
-    for t, name in ((labels, "labels"), (palette_yuv, "palette_yuv"), (action, "action"), (out, "out")):
-        if t.device != yuv.device:
-            raise RuntimeError("render_mosaic_yuv: %s must be on the surfaces' device %s, got %s" % (name, yuv.device, t.device))
+    F, H, W, out = _yuv_paint_args("render_mosaic_yuv", labels, yuv, palette_yuv, out, f_off, a256, contour, (action, cell))
     if yuv.is_cuda:
-        (yp, ys), (cp, cs) = _pitch_stride(yuv.y), _pitch_stride(yuv.uv)
-        (oyp, oys), (ocp, ocs) = _pitch_stride(out.y), _pitch_stride(out.uv)
+        src, dst = _surface_call_args(labels, yuv, palette_yuv, out, F, H, W)
         with torch.cuda.device(yuv.device):
-            check(lib.mdqe_render_mosaic_yuv420sp(ptr(yuv.y), yp, ys, ptr(yuv.uv), cp, cs, F, H, W, YUV_FORMATS.index(yuv.fmt), ptr(labels),
-                                                  ptr(palette_yuv), ptr(action), a256, contour, cell, ptr(out.y), oyp, oys, ptr(out.uv),
-                                                  ocp, ocs, f_off, cur_stream(yuv.device)), "render_mosaic_yuv")
+            check(lib.mdqe_render_mosaic_yuv420sp(*src, ptr(action), a256, contour, cell, *dst, f_off, cur_stream(yuv.device)),
+                  "render_mosaic_yuv")
         return out
     if F == 0:
         return out
@@ -863,7 +799,13 @@ def render_mosaic_yuv(labels, yuv, palette_yuv, action, out=None, f_off=0, a256=
             (a0, a1), (b0, b1) = span(src), span(dst)
             if a0 < b1 and b0 < a1:
                 raise RuntimeError("render_mosaic_yuv: out must not share memory with yuv (the mosaic is not painted in place)")
-    # host planes: the rule of the header in torch integers
+    return _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action, cell)
+
+
+def _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action=None, cell=None):
+    """The surface painters' rule of include/mdqe_hip.h on host planes, in torch integers.  action None: the plain painter, which is the
+    table [0, 1, 1, ...] (no label has action 2, so no cell mean is taken) and may paint in place.  -> out."""
+    F, H, W = len(yuv), yuv.height, yuv.width
     p010 = yuv.fmt == "p010"
     ch, cw = (H + 1) // 2, (W + 1) // 2
 
@@ -877,8 +819,11 @@ def render_mosaic_yuv(labels, yuv, palette_yuv, action, out=None, f_off=0, a256=
     def up(t):                                      # a chroma-plane quantity at every pixel of its block
         return t.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)[:, :H, :W]
 
+    def means(v, sub):                              # cell means of a plane sub-sampled by `sub`; never looked at without an action 2
+        return v if action is None else _cell_means(v, cell // sub)
+
     lab = labels.to(torch.int64)
-    act = action.to(torch.int64)[lab]
+    act = (lab != 0).to(torch.int64) if action is None else action.to(torch.int64)[lab]
     edge = torch.zeros(lab.shape, dtype=torch.bool)
     for d in range(1, contour + 1):
         if d < H:
@@ -894,7 +839,7 @@ def render_mosaic_yuv(labels, yuv, palette_yuv, action, out=None, f_off=0, a256=
         return torch.where(keep_px, s, torch.where(act == 2, mean, torch.where(edge, p, (s * (256 - a256) + p * a256 + 128) >> 8)))
     ry = raw(yuv.y[:, :H, :W])
     Y = ry >> 6 if p010 else ry
-    yo = px(Y, col[..., 0], _cell_means(Y, cell))
+    yo = px(Y, col[..., 0], means(Y, 1))
     store(out.y[f_off:f_off + F, :H, :W], torch.where(keep_px, ry, yo << 6 if p010 else yo))
     rc = raw(yuv.uv[:, :ch, :2 * cw]).reshape(F, ch, cw, 2)
     C = rc >> 6 if p010 else rc
@@ -906,7 +851,7 @@ def render_mosaic_yuv(labels, yuv, palette_yuv, action, out=None, f_off=0, a256=
     n = blocks(torch.ones((F, H, W), dtype=torch.int64))
     sh = n >> 1                                     # n = 1, 2, 4: n / 2 = log2(n) = 0, 1, 2
     keep = blocks((~keep_px).to(torch.int64)) == 0
-    oc = torch.stack([(blocks(px(up(C[..., k]), col[..., k + 1], up(_cell_means(C[..., k], cell // 2)))) + sh) >> sh for k in (0, 1)], -1)
+    oc = torch.stack([(blocks(px(up(C[..., k]), col[..., k + 1], up(means(C[..., k], 2)))) + sh) >> sh for k in (0, 1)], -1)
     word = torch.where(keep[..., None], rc, oc << 6 if p010 else oc)
     store(out.uv[f_off:f_off + F, :ch, :2 * cw], word.reshape(F, ch, 2 * cw))
     return out

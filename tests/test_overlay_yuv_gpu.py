@@ -151,6 +151,119 @@ def test_properties(H, W, fmt):
         assert np.array_equal(oy >> 6, ys >> 6) and np.array_equal(oc >> 6, cs >> 6) and not np.array_equal(oy, ys)
 
 
+# ---- the entries' own overlap rules -----------------------------------------------------------------------------------------------------
+EF, EH, EW = 2, 6, 8                                                  # the shape of every call below
+(A_IN_Y, A_IN_UV, A_OUT_Y, A_OUT_UV, A_LAB, A_ACT, A_PAL, A_DEC_IN, A_DEC_OUT), A_END = range(0, 9 * 1024, 1024), 12 * 1024
+MDQE_OK, MDQE_EINVAL, MDQE_ENULL = 0, 1, 3
+
+
+@pytest.mark.parametrize("fmt", ["nv12", "p010"])
+def test_entries_accept_and_refuse_the_same_plane_overlaps(fmt):
+    """mdqe_render_overlay_yuv420sp and mdqe_render_mosaic_yuv420sp called directly: which planes of a call may meet, and the order of
+    the checks.  Every pointer of every call lies in ONE device allocation of A_END bytes, regions 1 KB apart (a surface pair is at most
+    640 bytes, the palette 1536) and 3 KB of slack behind the last: a call accepted by mistake stays inside it.  An accepted call's
+    whole allocation equals the input with the oracle's picture in the output planes; a refused call leaves every byte as it was."""
+    from mdqe_cvpr2023_amd import _lib
+    import _mosaic_ref as MREF
+    lib = _lib.load_library()
+    es = 1 if fmt == "nv12" else 2
+    P = 16 * es                                                       # row pitch: twice a row of the picture
+    CH, rb = (EH + 1) // 2, EW * es                                   # chroma rows; bytes of a luma row and of a chroma row
+    rng = np.random.default_rng(11 + es)
+    host = rng.integers(0, 256, size=A_END, dtype=np.uint8)
+    lab = REF.make_labels(5, EF, EH, EW)
+    pal_np, _ = _palette(9, fmt)
+    act_np = MREF.action_tables(1)["mix"]
+    host[A_LAB:A_LAB + lab.size] = lab.reshape(-1)
+    host[A_PAL:A_PAL + 1536] = pal_np.astype("<u2").view(np.uint8).reshape(-1)
+    host[A_ACT:A_ACT + 256] = act_np
+    dev = torch.from_numpy(host.copy()).cuda()
+    base = dev.data_ptr()
+    assert base % 256 == 0
+    stream = _lib.cur_stream()
+    a256, contour, cell = 128, 1, 4
+
+    def apart_call():                                                 # every plane a region of its own, surfaces back to back
+        return dict(y=A_IN_Y, y_pitch=P, y_stride=EH * P, uv=A_IN_UV, uv_pitch=P, uv_stride=CH * P, F=EF, labels=A_LAB, palette=A_PAL,
+                    action=A_ACT, contour=contour, oy=A_OUT_Y, oy_pitch=P, oy_stride=EH * P, ouv=A_OUT_UV, ouv_pitch=P, ouv_stride=CH * P)
+
+    def decoder_call():                                               # luma rows, chroma rows and a spare row of each frame under one stride
+        st = (EH + CH + 1) * P
+        return dict(apart_call(), y=A_DEC_IN, y_stride=st, uv=A_DEC_IN + EH * P, uv_stride=st,
+                    oy=A_DEC_OUT, oy_stride=st, ouv=A_DEC_OUT + EH * P, ouv_stride=st)
+
+    def in_place_call():
+        c = apart_call()
+        return dict(c, oy=c["y"], ouv=c["uv"])
+
+    def at(off):
+        return None if off is None else base + off
+
+    def run(mosaic, c):
+        head = (at(c["y"]), c["y_pitch"], c["y_stride"], at(c["uv"]), c["uv_pitch"], c["uv_stride"], c["F"], EH, EW, es - 1,
+                at(c["labels"]), at(c["palette"]))
+        tail = (at(c["oy"]), c["oy_pitch"], c["oy_stride"], at(c["ouv"]), c["ouv_pitch"], c["ouv_stride"], 0, stream)
+        if mosaic:
+            return lib.mdqe_render_mosaic_yuv420sp(*head, at(c["action"]), a256, c["contour"], cell, *tail)
+        return lib.mdqe_render_overlay_yuv420sp(*head, a256, c["contour"], *tail)
+
+    def plane(buf, off, pitch, stride, rows):                         # [EF, rows, rb] bytes of a plane of `buf`
+        return np.lib.stride_tricks.as_strided(buf[off:], (EF, rows, rb), (stride, pitch, 1))
+
+    def samples(a):
+        a = np.ascontiguousarray(a)
+        return a if fmt == "nv12" else a.view("<u2")
+
+    def accepted(mosaic, c, what):
+        ys = samples(plane(host, c["y"], c["y_pitch"], c["y_stride"], EH))
+        cs = samples(plane(host, c["uv"], c["uv_pitch"], c["uv_stride"], CH))
+        if mosaic:
+            wy, wc = MREF.paint_yuv(ys, cs, lab, pal_np, act_np, fmt, a256, contour, cell)
+        else:
+            wy, wc = REF.paint(ys, cs, lab, pal_np, fmt, a256, contour)
+        expect = host.copy()
+        plane(expect, c["oy"], c["oy_pitch"], c["oy_stride"], EH)[...] = wy.astype("<u2" if es == 2 else np.uint8).view(np.uint8).reshape(EF, EH, rb)
+        plane(expect, c["ouv"], c["ouv_pitch"], c["ouv_stride"], CH)[...] = wc.astype("<u2" if es == 2 else np.uint8).view(np.uint8).reshape(EF, CH, rb)
+        assert not np.array_equal(expect, host)
+        dev.copy_(torch.from_numpy(host))
+        assert run(mosaic, c) == MDQE_OK, (what, mosaic)
+        assert np.array_equal(dev.cpu().numpy(), expect), (what, mosaic)
+        dev.copy_(torch.from_numpy(host))
+
+    def refused(mosaic, c, what, status=MDQE_EINVAL):
+        assert run(mosaic, c) == status, (what, mosaic)
+        torch.cuda.synchronize()
+        assert np.array_equal(dev.cpu().numpy(), host), (what, mosaic)
+
+    for mosaic in (False, True):
+        accepted(mosaic, apart_call(), "apart")
+        accepted(mosaic, decoder_call(), "one decoder allocation each")
+    accepted(False, in_place_call(), "in place")
+    refused(True, in_place_call(), "in place")
+    a = apart_call()
+    both = [("out luma one row into the input luma", dict(a, oy=a["y"] + P)),
+            ("out luma at the input's address, another pitch", dict(a, oy=a["y"], oy_pitch=2 * P, oy_stride=2 * EH * P)),
+            ("out chroma meets the input luma", dict(a, ouv=a["y"] + 2 * P)),
+            ("out luma meets out chroma", dict(a, ouv=a["oy"] + 2 * P)),
+            ("labels in the out luma", dict(a, labels=a["oy"])),
+            ("palette in the out chroma", dict(a, palette=a["ouv"])),
+            ("two writers: an out stride below one surface", dict(a, oy_stride=P))]
+    if fmt == "p010":
+        both += [("odd pitch", dict(a, y_pitch=P + 1)), ("odd out pitch", dict(a, ouv_pitch=P + 1)),
+                 ("odd pointer", dict(a, uv=a["uv"] + 1)), ("odd out pointer", dict(a, oy=a["oy"] + 1))]
+    for what, c in both:
+        for mosaic in (False, True):
+            refused(mosaic, c, what)
+    refused(True, dict(a, action=a["oy"] + P), "action table in the out luma")
+    refused(True, dict(a, action=a["ouv"]), "action table in the out chroma")
+    # the order of the checks: sizes, then F == 0, then null pointers
+    null = dict(a, y=None, uv=None, labels=None, palette=None, action=None, oy=None, ouv=None)
+    for mosaic in (False, True):
+        refused(mosaic, dict(null, F=0), "no surface, null pointers", MDQE_OK)
+        refused(mosaic, dict(a, labels=None), "null labels", MDQE_ENULL)
+        refused(mosaic, dict(null, contour=4), "bad contour, null pointers")
+
+
 # ---- the model -----------------------------------------------------------------------------------------------------------------------
 def _model(**kw):
     from mdqe_cvpr2023_amd.config import PRESETS
