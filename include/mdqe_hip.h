@@ -624,6 +624,52 @@ int mdqe_render_mosaic_yuv420sp(const void* y, long y_pitch, long y_stride, cons
                                 void* out_y, long out_y_pitch, long out_y_stride,
                                 void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream);
 
+/* Track boxes and captions on a painted picture (csrc/annotate.hip): the box and the text plate per instance that the demo's
+ * visualiser draws on the host (demo/clip/visualizer.py:162,205; captions "[id] class score%", demo/visualizer.py:72-91).  An
+ * ANNOTATION PASS: it runs behind any of the four painters above, IN PLACE on the painted picture, on the same stream; the painters
+ * are not touched.  pic: uint8 [>= f_off + F, Ho, Wo, 3], frame f of the call is picture f_off + f; the surface entry's planes are
+ * mdqe_render_overlay_yuv420sp's (pitches and strides in BYTES, fmt 0 NV12 / 1 P010, surface f at y + (f_off + f) * y_stride), read and
+ * written.  geom: int32 [n*F, 5], row k*F + f = (area, xmin, ymin, xmax, ymax), the table mdqe_final_label_map_u8 writes; label l = k + 1.
+ * palette / ink: uint8 [256, 3] (surfaces: uint16 [256, 3], rows (Y, U, V) in sample units), row l the colour of label l's box and plate /
+ * of its text.  captions: uint8 [256, cap_len], row l the text of label l, ended by a 0 byte or by cap_len; NULL with cap_len == 0 (no
+ * captions).  font: uint8 [64, 7], glyph ch - 32 for ch in 0x20..0x5F, 7 rows of 5 pixels, bit 4 the leftmost.  With Wo = W, Ho = H for
+ * surfaces, integers only, ONE definition, for frame f and label l with (area, x0, y0, x1, y1) = geom[k*F + f]:
+ *   live    area >= max(1, min_area) and 0 <= x0 <= x1 < Wo and 0 <= y0 <= y1 < Ho.  Any other row -- the empty row (0, Wo, Ho, -1, -1),
+ *           garbage -- draws nothing; the entries are memory-safe for every table content;
+ *   frame   (box > 0) the pixels with x0 <= X <= x1, y0 <= Y <= y1 and min(X - x0, x1 - X, Y - y0, y1 - Y) < box;
+ *   plate   (cap_len > 0, and row l holds c >= 1 characters) w = (6c + 1) * scale by h = 9 * scale pixels at px = max(0, min(x0, Wo - w)),
+ *           py = y0 - h if that is >= 0, else y0 (inside the box at the top edge); clipped to the picture;
+ *   glyph   in a plate, u = X - px, v = Y - py, gx = u / scale - 1, gy = v / scale - 1: the pixel is INK when gx >= 0, 0 <= gy < 7,
+ *           gx % 6 < 5 and bit 4 - gx % 6 of font[ch - 32][gy] is set, ch = caption byte gx / 6, a byte outside 0x20..0x5F drawn as '?';
+ *           any other plate pixel has the plate colour;
+ *   pixel   takes its FIRST hit among: the plates of the live labels in ascending l (ink: ink[l], else palette[l]), then the frames in
+ *           ascending l (palette[l]).  A pixel that nothing hits is NOT WRITTEN;
+ *   luma    the rule per sample with the Y components;
+ *   chroma  a pair whose in-picture 2 x 2 block has no hit is not written (P010: it keeps all 16 bits of both words).  Any other pair:
+ *           Cout = (sum_i px_i + n / 2) >> log2(n) over the block's n = 1, 2 or 4 in-picture pixels, px_i the hit's U (V) component for
+ *           a hit pixel and the stored sample's VALUE otherwise -- mdqe_render_overlay_yuv420sp's chroma rule; P010 words are written as
+ *           value << 6.
+ * One thread owns each sample and each chroma pair: in place by construction.  A block owns a tile, compacts the plates and frames
+ * that meet it into LDS in label order (capacity: all 255) and each pixel walks that list; a tile with an empty list returns without
+ * reading or writing a pixel.  Stores are 4-byte wide where four neighbouring samples are all hit and their address is aligned,
+ * single samples otherwise: nothing needs to be aligned.
+ * MDQE_EINVAL, before any pointer is looked at, for box outside 0..4, scale outside 1..4, n outside 0..255, cap_len outside 0..64,
+ * min_area < 0, F < 0, f_off < 0, Ho, Wo, H or W <= 0, F*Ho*Wo >= 2^31 - 1, and for the surface entry fmt outside {0, 1}, a pitch
+ * smaller than a row, a negative stride, odd P010 pitches or strides, surfaces of a plane that share bytes (F > 1); odd P010 plane
+ * pointers, odd palette_yuv / ink_yuv pointers and a luma plane that meets the chroma plane are MDQE_EINVAL too.  F == 0, n == 0 and
+ * box == 0 with cap_len == 0 return OK and launch nothing.  ink, captions and font are looked at only when cap_len > 0.  One launch, no
+ * atomics: identical from run to run.  Never allocates, never synchronises. */
+int mdqe_annotate_u8(unsigned char* pic /* [.., Ho, Wo, 3] */, int F, int Ho, int Wo, int f_off,
+                     const int* geom /* int32 [n*F, 5], row k*F+f: final_label_map's table */, int n,
+                     const unsigned char* palette /*[256,3]*/, const unsigned char* ink /*[256,3]*/,
+                     const unsigned char* captions /*[256, cap_len] or NULL*/, int cap_len,
+                     const unsigned char* font /*[64, 7]*/, int box, int scale, int min_area, void* stream);
+int mdqe_annotate_yuv420sp(void* y, long y_pitch, long y_stride, void* uv, long uv_pitch, long uv_stride,
+                           int F, int H, int W, int fmt /*0 nv12, 1 p010*/, int f_off, const int* geom, int n,
+                           const unsigned short* palette_yuv, const unsigned short* ink_yuv,
+                           const unsigned char* captions, int cap_len, const unsigned char* font,
+                           int box, int scale, int min_area, void* stream);
+
 /* ---- COCO single-image branch, after the decoder (MDQE.inference_image, mdqe/mdqe.py:486-556), on the centre frame's
  * low-resolution logits [n,Hm,Wm]; aligned_bilinear x`factor` in closed form, crop [:h,:w].
  * stats[k] = {sum(sigmoid*[sigmoid>0.5]), count(sigmoid>0.5), xmin, ymin, xmax, ymax of (logit > 0)} (:512-516, :526;

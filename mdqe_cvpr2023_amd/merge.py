@@ -219,14 +219,19 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
     YuvFrames; the pieces are then the surfaces handed in, of the output size): painted in the YUV domain, one
     ops.render_overlay_yuv launch per piece, with the palette in the surfaces' samples.  A style with a mosaic (style.mosaic): the
     same launches of ops.render_mosaic / ops.render_mosaic_yuv with the style's action table; `cls`, the window's class rows [n, K]
-    on the host, is what a style with `classes` builds that table from.  -> `label_maps`' geometry table or None."""
+    on the host, is what a style with `classes` builds that table from.  A style that annotates (style.annotates: track boxes,
+    captions) takes the geometry table from `label_maps` whether or not `geometry` asks for it and, behind the painter launches, runs
+    one ops.annotate / ops.annotate_yuv launch per piece in place on the painted frames, on the same stream, with the captions made
+    from `cls`; nothing is read back.  -> `label_maps`' geometry table where `geometry` asks for it, else None."""
     from . import ops
-    geom = label_maps(m, stride, frame_hw, out_size, geometry, labels, l_off)
-    nf = int(m.shape[1])
+    notes = style.annotates and int(m.shape[0]) > 0
+    geom = label_maps(m, stride, frame_hw, out_size, geometry or notes, labels, l_off)
+    n, nf = int(m.shape[0]), int(m.shape[1])
     surface = not torch.is_tensor(out)
     pal = style.palette_yuv_on(m.device, *out.meta()[2:]) if surface else style.palette_on(m.device)
     act = style.actions_on(m.device, cls) if style.mosaic is not None else None
-    for t, first in source.pieces(int(f0), int(f0) + nf, stream=torch.cuda.current_stream(m.device)):
+    pieces = source.pieces(int(f0), int(f0) + nf, stream=torch.cuda.current_stream(m.device))
+    for t, first in pieces:
         k, d = len(t), first - int(f0)
         lab = labels[l_off + d:l_off + d + k]
         if act is not None and surface:
@@ -237,7 +242,15 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
             ops.render_overlay_yuv(lab, t, pal, out, o_off + d, style.a256, style.contour)
         else:
             ops.render_overlay(lab, t, pal, out, o_off + d, style.a256, style.contour)
-    return geom
+    if notes:
+        ink = style.ink_yuv_on(m.device, *out.meta()[2:]) if surface else style.ink_on(m.device)
+        text, font = style.captions_on(m.device, cls, n), style.font_on(m.device)
+        for t, first in pieces:
+            k, d = len(t), first - int(f0)
+            g = geom if k == nf else geom[:, d:d + k].contiguous()     # (the table's rows are k * F + f of the frames of ONE call)
+            (ops.annotate_yuv if surface else ops.annotate)(out, g, n, pal, ink, text, font, o_off + d, style.box, style.text_scale,
+                                                            style.min_area)
+    return geom if geometry else None
 
 
 def surface_kind(source, out_size):

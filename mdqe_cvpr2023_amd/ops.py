@@ -802,6 +802,80 @@ def render_mosaic_yuv(labels, yuv, palette_yuv, action, out=None, f_off=0, a256=
     return _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action, cell)
 
 
+def _annotate_args(name, geom, n, palette, ink, captions, font, f_off, box, scale, min_area, table_dtypes):
+    """The checks annotate and annotate_yuv share.  -> (frames of the call, cap_len)."""
+    # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= 255:
+        raise RuntimeError("%s: n must be an int in 0..255, got %r" % (name, n))
+    for what, v, lo, hi in (("box", box, 0, 4), ("scale", scale, 1, 4), ("min_area", min_area, 0, 2 ** 31 - 1), ("f_off", f_off, 0, 2 ** 31 - 1)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise RuntimeError("%s: %s must be an int in %d..%d, got %r" % (name, what, lo, hi, v))
+    if (not torch.is_tensor(geom) or geom.dtype != torch.int32 or not geom.is_contiguous() or geom.dim() not in (2, 3) or geom.shape[-1] != 5
+            or (geom.dim() == 3 and int(geom.shape[0]) != n) or (n and (geom.numel() // 5) % n)):
+        raise RuntimeError("%s: geom must be contiguous int32 [n * F, 5] or [n = %d, F, 5] (ops.final_label_map's table)" % (name, n))
+    F = geom.numel() // 5 // n if n else 0
+    for what, t in (("palette", palette), ("ink", ink)):
+        if not torch.is_tensor(t) or t.dtype not in table_dtypes or tuple(t.shape) != (256, 3) or not t.is_contiguous():
+            raise RuntimeError("%s: %s must be contiguous %s [256, 3]" % (name, what, str(table_dtypes[0]).replace("torch.", "")))
+    if captions is not None and (not torch.is_tensor(captions) or captions.dtype != torch.uint8 or captions.dim() != 2
+                                 or int(captions.shape[0]) != 256 or not 1 <= captions.shape[1] <= 64 or not captions.is_contiguous()):
+        raise RuntimeError("%s: captions must be None or contiguous uint8 [256, 1..64] (render.captions)" % name)
+    if not torch.is_tensor(font) or font.dtype != torch.uint8 or tuple(font.shape) != (64, 7) or not font.is_contiguous():
+        raise RuntimeError("%s: font must be contiguous uint8 [64, 7] (render.default_font)" % name)
+    return F, int(captions.shape[1]) if captions is not None else 0
+
+
+def annotate(pic, geom, n, palette, ink, captions, font, f_off=0, box=0, scale=1, min_area=0):
+    """Track boxes and captions drawn onto a painted picture, in place: pic (uint8 [>= f_off + F, Ho, Wo, 3], CUDA, contiguous -- what
+    ops.render_overlay / ops.render_mosaic painted) gets, in its frames f_off .. f_off + F - 1 and for each label l = 1..n whose row of
+    geom (int32 [n * F, 5] or [n, F, 5], row (l - 1) * F + f = (area, xmin, ymin, xmax, ymax): ops.final_label_map's table) is live
+    (area >= max(1, min_area), the box inside the picture), a frame of `box` pixels along its box in palette[l] (box 0: none) and, with
+    captions (uint8 [256, cap_len <= 64], render.captions; None: none), a plate in palette[l] at the box's top left corner that holds
+    row l of captions in ink[l], drawn from font (uint8 [64, 7], render.default_font) at `scale` pixels per font pixel.  Plates lie
+    over frames, lower labels over higher ones; a pixel that nothing hits is not written: the integer rule of include/mdqe_hip.h,
+    mdqe_annotate_u8.  One launch on the current stream, none when F == 0, n == 0 or there is nothing to draw.  -> pic."""
+    F, cap_len = _annotate_args("annotate", geom, n, palette, ink, captions, font, f_off, box, scale, min_area, (torch.uint8,))
+    if not torch.is_tensor(pic) or pic.dtype != torch.uint8 or pic.dim() != 4 or int(pic.shape[3]) != 3 or not pic.is_contiguous():
+        raise RuntimeError("annotate: pic must be contiguous uint8 [frames, Ho, Wo, 3]")
+    Ho, Wo = int(pic.shape[1]), int(pic.shape[2])
+    if Ho < 1 or Wo < 1 or f_off + F > pic.shape[0] or F * Ho * Wo >= 2 ** 31 - 1:
+        raise RuntimeError("annotate: pic %s must hold frames f_off .. f_off + F = %d of positive size, F*Ho*Wo < 2^31 - 1" % (tuple(pic.shape), f_off + F))
+    for t, what in ((pic, "pic"), (geom, "geom"), (palette, "palette"), (ink, "ink"), (captions, "captions"), (font, "font")):
+        if t is not None and (not t.is_cuda or t.device != pic.device):
+            raise RuntimeError("annotate: %s must be a CUDA tensor on pic's device, got %s" % (what, t.device))
+    with torch.cuda.device(pic.device):
+        check(lib.mdqe_annotate_u8(ptr(pic), F, Ho, Wo, f_off, ptr(geom), n, ptr(palette), ptr(ink), ptr(captions), cap_len, ptr(font),
+                                   box, scale, min_area, cur_stream(pic.device)), "annotate")
+    return pic
+
+
+def annotate_yuv(yuv, geom, n, palette_yuv, ink_yuv, captions, font, f_off=0, box=0, scale=1, min_area=0):
+    """`annotate` on painted decoder surfaces, in place: yuv (a preprocess.YuvFrames on a HIP device, NV12 or P010 -- what
+    ops.render_overlay_yuv / ops.render_mosaic_yuv painted) gets the same boxes and plates in its surfaces f_off .. f_off + F - 1, with
+    palette_yuv and ink_yuv (uint16 [256, 3], rows (Y, U, V) in sample units: render.palette_yuv of the palette and of render.ink).
+    Luma follows the rule per sample; a chroma pair with a hit in its 2 x 2 block becomes the rounded mean of the hits' components and
+    the stored value for the block's other pixels, a pair without a hit keeps its bits: the integer rule of include/mdqe_hip.h,
+    mdqe_annotate_yuv420sp.  -> yuv."""
+    from .preprocess import YUV_FORMATS, YuvFrames, _pitch_stride
+    F, cap_len = _annotate_args("annotate_yuv", geom, n, palette_yuv, ink_yuv, captions, font, f_off, box, scale, min_area, (torch.uint16, torch.int16))
+    if not isinstance(yuv, YuvFrames):
+        raise RuntimeError("annotate_yuv: yuv must be a preprocess.YuvFrames, got %s" % type(yuv).__name__)
+    H, W = yuv.height, yuv.width
+    if f_off + F > len(yuv) or F * H * W >= 2 ** 31 - 1:
+        raise RuntimeError("annotate_yuv: yuv holds %d surfaces, the call needs f_off + F = %d, F*H*W < 2^31 - 1" % (len(yuv), f_off + F))
+    if not yuv.is_cuda:
+        raise RuntimeError("annotate_yuv: the surfaces must be on a HIP device, got %s (the annotation pass has no host path)" % (yuv.device,))
+    for t, what in ((geom, "geom"), (palette_yuv, "palette_yuv"), (ink_yuv, "ink_yuv"), (captions, "captions"), (font, "font")):
+        if t is not None and t.device != yuv.device:
+            raise RuntimeError("annotate_yuv: %s must be on the surfaces' device %s, got %s" % (what, yuv.device, t.device))
+    (yp, ys), (cp, cs) = _pitch_stride(yuv.y), _pitch_stride(yuv.uv)
+    with torch.cuda.device(yuv.device):
+        check(lib.mdqe_annotate_yuv420sp(ptr(yuv.y), yp, ys, ptr(yuv.uv), cp, cs, F, H, W, YUV_FORMATS.index(yuv.fmt), f_off, ptr(geom), n,
+                                         ptr(palette_yuv), ptr(ink_yuv), ptr(captions), cap_len, ptr(font), box, scale, min_area,
+                                         cur_stream(yuv.device)), "annotate_yuv")
+    return yuv
+
+
 def _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action=None, cell=None):
     """The surface painters' rule of include/mdqe_hip.h on host planes, in torch integers.  action None: the plain painter, which is the
     table [0, 1, 1, ...] (no label has action 2, so no cell mean is taken) and may paint in place.  -> out."""

@@ -1,6 +1,8 @@
 """How an overlay is painted (model.overlay_output, online_video(emit="overlay")): the palette and the style.  The painting itself is
 ops.render_overlay (csrc/render.hip) behind the label map; merge.overlay_frames puts the two together for a tracker window.  A style
-with a mosaic (redaction) is painted by ops.render_mosaic (csrc/render_mosaic.hip) from the style's per-label action table.
+with a mosaic (redaction) is painted by ops.render_mosaic (csrc/render_mosaic.hip) from the style's per-label action table.  A style
+with a box or a caption has ops.annotate (csrc/annotate.hip) draw them onto the painted picture, from the label map's geometry table,
+the font, the ink colours and the window's caption table made here.
 
 A track's colour depends only on its tracker row (label = row + 1), so it keeps its colour across windows and pushes."""
 import dataclasses
@@ -69,6 +71,131 @@ def palette_yuv(palette_rgb, fmt="nv12", matrix="bt709", full_range=False, order
     return torch.stack(rows, 1).to(torch.uint16)
 
 
+# The annotation pass's font (ops.annotate, csrc/annotate.hip): 5 x 7 glyphs for 0x20..0x5F drawn for this project, one per line, 7 rows
+# top to bottom as hex, bit 4 the leftmost pixel of a row.
+_FONT = """
+  00 00 00 00 00 00 00
+! 04 04 04 04 04 00 04
+" 0A 0A 0A 00 00 00 00
+# 0A 0A 1F 0A 1F 0A 0A
+$ 04 0F 14 0E 05 1E 04
+% 18 19 02 04 08 13 03
+& 0C 12 14 08 15 12 0D
+' 0C 04 08 00 00 00 00
+( 02 04 08 08 08 04 02
+) 08 04 02 02 02 04 08
+* 00 04 15 0E 15 04 00
++ 00 04 04 1F 04 04 00
+, 00 00 00 00 0C 04 08
+- 00 00 00 1F 00 00 00
+. 00 00 00 00 00 0C 0C
+/ 00 01 02 04 08 10 00
+0 0E 11 13 15 19 11 0E
+1 04 0C 04 04 04 04 0E
+2 0E 11 01 02 04 08 1F
+3 1F 02 04 02 01 11 0E
+4 02 06 0A 12 1F 02 02
+5 1F 10 1E 01 01 11 0E
+6 06 08 10 1E 11 11 0E
+7 1F 01 02 04 08 08 08
+8 0E 11 11 0E 11 11 0E
+9 0E 11 11 0F 01 02 0C
+: 00 0C 0C 00 0C 0C 00
+; 00 0C 0C 00 0C 04 08
+< 02 04 08 10 08 04 02
+= 00 00 1F 00 1F 00 00
+> 08 04 02 01 02 04 08
+? 0E 11 01 02 04 00 04
+@ 0E 11 01 0D 15 15 0E
+A 0E 11 11 11 1F 11 11
+B 1E 11 11 1E 11 11 1E
+C 0E 11 10 10 10 11 0E
+D 1C 12 11 11 11 12 1C
+E 1F 10 10 1E 10 10 1F
+F 1F 10 10 1E 10 10 10
+G 0E 11 10 17 11 11 0F
+H 11 11 11 1F 11 11 11
+I 0E 04 04 04 04 04 0E
+J 07 02 02 02 02 12 0C
+K 11 12 14 18 14 12 11
+L 10 10 10 10 10 10 1F
+M 11 1B 15 15 11 11 11
+N 11 11 19 15 13 11 11
+O 0E 11 11 11 11 11 0E
+P 1E 11 11 1E 10 10 10
+Q 0E 11 11 11 15 12 0D
+R 1E 11 11 1E 14 12 11
+S 0F 10 10 0E 01 01 1E
+T 1F 04 04 04 04 04 04
+U 11 11 11 11 11 11 0E
+V 11 11 11 11 11 0A 04
+W 11 11 11 15 15 15 0A
+X 11 11 0A 04 0A 11 11
+Y 11 11 11 0A 04 04 04
+Z 1F 01 02 04 08 10 1F
+[ 0E 08 08 08 08 08 0E
+\\ 00 10 08 04 02 01 00
+] 0E 02 02 02 02 02 0E
+^ 04 0A 11 00 00 00 00
+_ 00 00 00 00 00 00 1F
+"""
+
+CAP_LEN = 32                      # bytes of a caption row: longer texts are cut
+CAPTIONS = (None, "id", "class", "id+class", "id+class+score", "class+score")
+
+
+def default_font():
+    """uint8 [64, 7] on the host: glyph ch - 32 for ch in 0x20..0x5F (row 0 is the space), 7 rows top to bottom, bit 4 - x of a row is
+    its pixel x = 0..4 -- the layout ops.annotate reads."""
+    lines = _FONT.strip("\n").split("\n")
+    assert len(lines) == 64 and all(ord(line[0]) == 32 + i for i, line in enumerate(lines))
+    return torch.tensor([[int(v, 16) for v in line[2:].split()] for line in lines], dtype=torch.uint8)
+
+
+def ink(palette):
+    """The colour of the text on each label's plate, uint8 [256, 3] on the host: row l is white where palette row l is dark
+    (c0 + c1 + c2 < 384), else black.  For surfaces: palette_yuv(ink(palette), ...) -- black and white do not depend on the channel order."""
+    if not torch.is_tensor(palette) or palette.dtype != torch.uint8 or tuple(palette.shape) != (256, 3):
+        raise ValueError("ink: palette must be a uint8 [256, 3] tensor")
+    dark = palette.cpu().to(torch.int64).sum(1) < 384
+    return torch.where(dark[:, None], 255, 0).to(torch.uint8).expand(256, 3).contiguous()
+
+
+def captions(style, cls_probs, n):
+    """The caption table of ops.annotate, uint8 [256, CAP_LEN] on the host, a pure function: row l is the text of label l = tracker row
+    l - 1 for l in 1..n, the fields `style.caption` lists joined by single spaces -- id: the tracker row in decimal; class:
+    style.class_names[j] upper-cased (without names: j in decimal) for j the first maximum of row l - 1 of the window's class rows
+    cls_probs [>= n, K]; score: int(100 * p + 0.5) of that maximum p (the float32 value as a Python float) and '%' -- cut to CAP_LEN
+    bytes and ended by 0 bytes.  Row 0 and the rows above n are empty."""
+    table = torch.zeros(256, CAP_LEN, dtype=torch.uint8)
+    fields = style.caption.split("+") if style.caption else []
+    n = min(int(n), 255)
+    if not fields or n <= 0:
+        return table
+    first = top = None
+    if fields != ["id"]:
+        if not torch.is_tensor(cls_probs) or cls_probs.dim() != 2 or cls_probs.shape[0] < n or cls_probs.shape[1] < 1:
+            raise ValueError("overlay style: caption %r needs the window's class rows [>= %d, K >= 1], got %s"
+                             % (style.caption, n, tuple(cls_probs.shape) if torch.is_tensor(cls_probs) else type(cls_probs).__name__))
+        rows = cls_probs[:n].detach().cpu().float()
+        first = rows.argmax(1).tolist()                 # (of several maxima the first: torch.argmax's rule)
+        top = rows.max(1)[0].tolist()
+    names = style.class_names
+    for t in range(n):
+        parts = []
+        for field in fields:
+            if field == "id":
+                parts.append(str(t))
+            elif field == "class":
+                j = first[t]
+                parts.append(str(names[j]).upper() if names is not None and j < len(names) else str(j))
+            else:
+                parts.append("%d%%" % int(100 * top[t] + 0.5))
+        text = " ".join(parts).encode("ascii", "replace")[:CAP_LEN]
+        table[t + 1, :len(text)] = torch.tensor(list(text), dtype=torch.uint8)
+    return table
+
+
 @dataclasses.dataclass
 class Style:
     """alpha: weight of the track colour inside a region, 0..1 (the kernel blends with a256 = round(alpha * 256) in 1/256 steps);
@@ -78,15 +205,41 @@ class Style:
     `classes` the tracks of those classes, the others tinted as ever; the background stays as decoded -- or "background" -- everything
     but the tracks, which are tinted as alpha / contour say (alpha=0, contour=0: left exactly as decoded).  cell: the side of a mosaic
     cell in output pixels, an even int in 2..64.  classes: None or a collection of class ids >= 0 (kept as a sorted tuple), only with
-    mosaic="tracks"."""
+    mosaic="tracks".
+    Annotations (ops.annotate, csrc/annotate.hip: a pass behind whichever painter the fields above choose): box: the thickness in
+    pixels, 0..4, of a frame around each track's visible region per frame (0: none); caption: None or which fields are written on a
+    plate at the box's top left corner -- "id", "class", "id+class", "id+class+score", "class+score" (`captions`); class_names: None or
+    a sequence of names by class id (a caption then shows the name, upper-cased, instead of the number); text_scale: pixels per font
+    pixel, 1..4; min_area: regions of fewer pixels get neither box nor caption."""
     alpha: float = 0.5
     contour: int = 1
     palette: torch.Tensor = None
     mosaic: str = None
     cell: int = 16
     classes: tuple = None
+    box: int = 0
+    caption: str = None
+    class_names: tuple = None
+    text_scale: int = 1
+    min_area: int = 0
 
     def __post_init__(self):
+        if isinstance(self.box, bool) or not isinstance(self.box, int) or not 0 <= self.box <= 4:
+            raise ValueError("overlay style: box must be an int in 0..4, got %r" % (self.box,))
+        if self.caption not in CAPTIONS:
+            raise ValueError("overlay style: caption must be one of %s, got %r" % (", ".join(repr(c) for c in CAPTIONS), self.caption))
+        if self.class_names is not None:
+            try:
+                names = tuple(self.class_names) if not isinstance(self.class_names, (str, bytes)) else None
+            except TypeError:
+                names = None
+            if names is None or any(not isinstance(s, str) for s in names):
+                raise ValueError("overlay style: class_names must be None or a sequence of strings, got %r" % (self.class_names,))
+            self.class_names = names
+        if isinstance(self.text_scale, bool) or not isinstance(self.text_scale, int) or not 1 <= self.text_scale <= 4:
+            raise ValueError("overlay style: text_scale must be an int in 1..4, got %r" % (self.text_scale,))
+        if isinstance(self.min_area, bool) or not isinstance(self.min_area, int) or not 0 <= self.min_area < 2 ** 31:
+            raise ValueError("overlay style: min_area must be an int in 0..2^31 - 1, got %r" % (self.min_area,))
         if isinstance(self.alpha, bool) or not isinstance(self.alpha, (int, float)) or not 0.0 <= self.alpha <= 1.0:
             raise ValueError("overlay style: alpha must be a number in 0..1, got %r" % (self.alpha,))
         if isinstance(self.contour, bool) or not isinstance(self.contour, int) or not 0 <= self.contour <= 3:
@@ -113,6 +266,39 @@ class Style:
     @property
     def a256(self):
         return int(round(self.alpha * 256))
+
+    @property
+    def annotates(self):
+        """Whether an annotation pass follows the painter (with the defaults: no, and exactly the painter's launches are made)."""
+        return self.box > 0 or self.caption is not None
+
+    def _cached_on(self, slot, key, make):
+        """A small host-made table on a device, made once per `key` (as `palette_on` keeps the palette)."""
+        cache = self.__dict__.setdefault(slot, {})
+        if key not in cache:
+            cache[key] = make().contiguous().to(key[0])
+            if cache[key].is_cuda:
+                torch.cuda.current_stream(cache[key].device).synchronize()
+        return cache[key]
+
+    def font_on(self, device):
+        """`default_font()` on `device` (cached per device)."""
+        return self._cached_on("_font_on", (str(device),), default_font)
+
+    def ink_on(self, device):
+        """`ink` of the palette on `device` (cached per device)."""
+        return self._cached_on("_ink_on", (str(device),), lambda: ink(default_palette() if self.palette is None else self.palette))
+
+    def ink_yuv_on(self, device, fmt, matrix, full_range, order):
+        """`palette_yuv(ink(palette), ...)` on `device` (cached per device and kind of surface, as `palette_yuv_on` is)."""
+        return self._cached_on("_ink_yuv_on", (str(device), fmt, matrix, bool(full_range), order),
+                               lambda: palette_yuv(ink(default_palette() if self.palette is None else self.palette), fmt, matrix,
+                                                   bool(full_range), order))
+
+    def captions_on(self, device, cls_probs, n):
+        """`captions` of a window on `device`, or None without a caption: built from the window's class rows and uploaded, 8 KB per
+        window (as `actions_on` does with `classes`)."""
+        return None if self.caption is None else captions(self, cls_probs, n).to(device)
 
     def actions(self, cls_probs=None):
         """The per-label action table of ops.render_mosaic, uint8 [256] on the host (0 keep, 1 tint, 2 mosaic; entry 0 is the
