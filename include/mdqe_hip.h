@@ -321,6 +321,13 @@ int mdqe_dwconv5x5_c256_f32(const float* x, const float* wt, const float* bias, 
 int mdqe_dwconv5x5_up2_c256_f32(const float* x, const float* wt, const float* bias, const float* tw, const float* tb, float* y,
                                 int NI, int Hs, int Ws, void* stream);
 
+/* mdqe_dwconv5x5_up2_c256_f32 and the 256 -> 32 projection behind it (mdqe_gemm_nt_f32 with weight pw [32,256], bias pb [32], exact
+ * fp32) as one kernel: out[pixel, 0:32] with rows ldo floats apart (ldo >= 32, ldo % 4 == 0), pixel = (img * 2Hs + Y) * 2Ws + X.  The
+ * [NI,2Hs,2Ws,256] tensor between the two is never stored; the result has the bits of the two calls in sequence (the same depthwise
+ * expressions, the K-step-16 kernel's summation order, bias last).  Every pointer 16-byte aligned.  128 KB of LDS per block. */
+int mdqe_dwconv5x5_up2_pw_c256_f32(const float* x, const float* wt, const float* bias, const float* tw, const float* tb,
+                                   const float* pw, const float* pb, float* out, long ldo, int NI, int Hs, int Ws, void* stream);
+
 /* ---- tracker, device half (mdqe/tracking/OverTracker.py) ------------------------------------------
  * siou: out3[i,j,:] = (|A_i & B_j|, |A_i|, |B_j|) with A_i = saved[i*saved_stride + k] > 0, B_j = inp[j*inp_stride + k] > 0,
  * k < n (the overlapping frames of both are contiguous); feeds OverTracker._get_siou (:92-113).
@@ -468,7 +475,9 @@ int mdqe_sample_levels_mean_f32(const float* tokens, int NI, long N, int C, cons
 
 /* ---- final masks (mdqe/mdqe.py:357-358,458-462; util/misc.py:485-507) fused: x`factor` aligned-bilinear ->
  * sigmoid -> crop [:h,:w] -> nearest resize to (Ho,Wo) -> > 0.5.  logits [*,Fw,Hm,Wm] (one tracker window);
- * row k of out (uint8 [n_sel][out_inst_stride]) takes instance inst_idx_dev[k], frames written at f_off.. */
+ * row k of out (uint8 [n_sel][out_inst_stride]) takes instance inst_idx_dev[k], frames written at f_off..  Any base address and
+ * stride (dword stores only where an address is 4-byte aligned).  MDQE_FINAL_MASK_FLAT=1 in the environment selects the flat
+ * one-byte-per-thread kernel instead of the band-mapped one: the same bytes (it also serves Ho * Wo >= 2^31). */
 int mdqe_final_masks_u8(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
                         int h, int w, int Ho, int Wo, unsigned char* out, long out_inst_stride, int f_off,
                         void* stream);

@@ -25,13 +25,68 @@ final_mask_kernel(const float* __restrict__ lg, int Fw, int Hm, int Wm, int fact
   }
 }
 
+// Band form of the same planes, shaped like final_label_map_kernel: a block owns a band of output rows of ONE frame for ALL selected
+// rows (blockIdx.x = frame * n_bands + band index) and a thread takes 4 consecutive pixels of an output row.  Where a pixel reads does
+// not depend on the track, so final_mask_taps runs once per pixel (32-bit index arithmetic, no 64-bit division) and the loop over k only
+// reads, blends (final_mask_value_at) and thresholds (final_mask_bit): the bits of final_mask_kernel by construction.  A track's four
+// bytes leave as one dword where the group is whole and its address 4-byte aligned -- decided per address, so an odd Wo, an odd base or
+// an odd stride only costs byte stores -- and byte by byte otherwise.
+__global__ void __launch_bounds__(256)
+final_mask_band_kernel(const float* __restrict__ lg, int n_sel, int Fw, int Hm, int Wm, int factor, int h, int w, int Ho, int Wo,
+                       unsigned char* __restrict__ out, long out_inst_stride, int f_off, const int* __restrict__ inst_idx, int band,
+                       int n_bands) {
+  const int f = blockIdx.x / n_bands, b = blockIdx.x - f * n_bands;
+  const float sy_scale = (float)h / (float)Ho, sx_scale = (float)w / (float)Wo;
+  const int Y0 = b * band, rows = min(band, Ho - Y0);
+  const long map_stride = (long)Hm * Wm;
+  const int Wg = (Wo + 3) >> 2;                        // groups of 4 pixels per output row
+  const int ngrp = rows * Wg;
+  unsigned char* o = out + ((long)(f_off + f) * Ho + Y0) * Wo;
+  for (int i = threadIdx.x; i < ngrp; i += 256) {
+    const int y = i / Wg, X0 = (i - y * Wg) << 2, Y = Y0 + y;
+    const int nx = min(4, Wo - X0);                    // pixels of the group inside the row
+    MaskTaps t[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) t[j] = final_mask_taps(Hm, Wm, factor, h, w, sy_scale, sx_scale, Y, min(X0 + j, Wo - 1));
+    unsigned char* og = o + (long)y * Wo + X0;
+    for (int k = 0; k < n_sel; ++k) {
+      const float* m = lg + ((long)inst_idx[k] * Fw + f) * map_stride;
+      unsigned int bits = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bits |= (unsigned int)final_mask_bit(final_mask_value_at(m, Wm, t[j])) << (8 * j);
+      unsigned char* p = og + (long)k * out_inst_stride;
+      if (nx == 4 && (reinterpret_cast<unsigned long>(p) & 3) == 0) {
+        *reinterpret_cast<unsigned int*>(p) = bits;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j < nx) p[j] = (unsigned char)((bits >> (8 * j)) & 1u);
+      }
+    }
+  }
+}
+
+// Routes to the band kernel.  The flat kernel keeps the outputs only it accepts (Ho * Wo >= 2^31: its pixel index is a long) and stays
+// selectable with MDQE_FINAL_MASK_FLAT=1 as the yardstick of tools/mask_path_ab.py and tests/test_final_mask_band_gpu.py.
 extern "C" int mdqe_final_masks_u8(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
                                    int h, int w, int Ho, int Wo, unsigned char* out, long out_inst_stride, int f_off,
                                    void* stream) {
-  MDQE_TRY(final_mask_args(n_sel, Fw, Hm, Wm, factor, h, w, Ho, Wo));      // (Ho * Wo >= 2^31 is fine here: the pixel index is a long)
+  MDQE_TRY(final_mask_args(n_sel, Fw, Hm, Wm, factor, h, w, Ho, Wo));
   if (n_sel == 0 || Fw == 0) return MDQE_OK;
   MDQE_CHECK_PTR(logits); MDQE_CHECK_PTR(inst_idx_dev); MDQE_CHECK_PTR(out);
   mdqe_clear_error();
+  const char* env = getenv("MDQE_FINAL_MASK_FLAT");
+  const bool flat = (env != nullptr && env[0] == '1') || (long)Ho * Wo >= 0x7FFFFFFFL || (long)Hm * Wm >= 0x7FFFFFFFL;
+  if (!flat) {
+    // bands per frame: about 8 blocks of 256 threads per CU over the window, at least ~1024 pixels (one group of 4 per thread) a block
+    const int band = final_mask_band(2048, Fw, Ho, Wo);
+    const int n_bands = (Ho + band - 1) / band;
+    if ((long)Fw * n_bands < 0x7FFFFFFFL && (long)band * ((Wo + 3) / 4) < 0x7FFFFFFFL) {
+      hipLaunchKernelGGL(final_mask_band_kernel, dim3((unsigned)(Fw * n_bands)), dim3(256), 0, (hipStream_t)stream, logits, n_sel, Fw, Hm,
+                         Wm, factor, h, w, Ho, Wo, out, out_inst_stride, f_off, inst_idx_dev, band, n_bands);
+      return mdqe_launch_status();
+    }
+  }
   const long total = (long)n_sel * Fw * Ho * Wo;
   long nb = (total + 255) / 256; if (nb > 256 * 64) nb = 256 * 64;
   hipLaunchKernelGGL(final_mask_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, logits, Fw, Hm, Wm, factor, h, w, Ho,

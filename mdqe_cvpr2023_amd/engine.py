@@ -586,11 +586,13 @@ class Engine:
         y = ops.dwconv5x5(x, o1.dw, o1.db)
         y = ops.linear(y.view(-1, C), o1.pw, o1.pb).view(x.shape)
         y = ops.groupnorm_nhwc(y, 32, o1.g, o1.beta, act="relu", out=y).view(x.shape)
-        z = ops.dwconv5x5(y, o2.dw, o2.db, up2=True, tw=mh.tw, tb=mh.tb)
         Md = o2.pw.shape[0]
-        if out is not None and (tuple(out.shape) != (NI, z.shape[1], z.shape[2], Md) or not out.is_contiguous()):
+        Hm, Wm = 2 * y.shape[1], 2 * y.shape[2]
+        if out is not None and (tuple(out.shape) != (NI, Hm, Wm, Md) or not out.is_contiguous()):
             raise RuntimeError("mask_features: out must be a contiguous [NI, Hm, Wm, M] tensor")
-        z2 = ops.linear(z.view(-1, C), o2.pw, o2.pb, out=None if out is None else out.view(-1, Md)).view(NI, z.shape[1], z.shape[2], Md)
+        # the up-sampling depthwise conv and its 1x1 projection: one kernel for the R50 / R101 head in exact fp32 (the [NI, Hm, Wm, C]
+        # tensor between them is never stored), the two launches otherwise -- the same bits either way
+        z2 = ops.dwconv5x5_up2_pw(y, o2.dw, o2.db, mh.tw, mh.tb, o2.pw, o2.pb, out=None if out is None else out.view(-1, Md)).view(NI, Hm, Wm, Md)
         return ops.groupnorm_nhwc(z2, 32 if Md % 32 == 0 else 24, o2.g, o2.beta, act="relu", out=z2).view(z2.shape)
 
     # ---- a11 (per-frame part): grid-guided query selection + content sampling ---------------------

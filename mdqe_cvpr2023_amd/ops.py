@@ -445,6 +445,32 @@ def dwconv5x5(x, wt, bias, up2=False, tw=None, tb=None):
 
 
 DW_FAST = os.environ.get("MDQE_DW_FAST", "1") != "0"        # 0: generic depthwise kernel (debug / A-B)
+MASK_HEAD_FUSED = os.environ.get("MDQE_MASK_HEAD_FUSED", "1") != "0"   # 0: up-sampling depthwise conv and its 1x1 as two launches
+
+
+def dwconv5x5_up2_pw(x, wt, bias, tw, tb, pw, pb, out=None):
+    """linear(dwconv5x5(x, wt, bias, up2=True, tw, tb), pw, pb): x [NI,Hs,Ws,C] -> [NI,2Hs,2Ws,N]; `out`: a [NI*2Hs*2Ws, N] view whose rows
+    may be strided (rows of a larger buffer).  C == 256, N == 32, exact-fp32 GEMM mode and 16-byte aligned operands take ONE kernel that
+    never stores the [.., C] tensor between the two (mdqe_dwconv5x5_up2_pw_c256_f32: the same bits); everything else, and
+    MDQE_MASK_HEAD_FUSED=0, takes the two launches."""
+    _chk(x, "x"); _chk(wt, "wt"); _chk(bias, "bias"); _chk(tw, "tw"); _chk(tb, "tb"); _chk(pw, "pw"); _chk(pb, "pb")
+    NI, Hs, Ws, C = x.shape
+    N = pw.shape[0]
+    rows = NI * 4 * Hs * Ws
+    if out is not None and (out.dim() != 2 or tuple(out.shape) != (rows, N) or out.stride(1) != 1 or not out.is_cuda or out.dtype != torch.float32):
+        raise RuntimeError("dwconv5x5_up2_pw: out must be a CUDA fp32 [NI*2Hs*2Ws, N] view with contiguous rows")
+    ldo = N if out is None or rows <= 1 else out.stride(0)
+    ptrs = [t.data_ptr() for t in (x, wt, bias, tw, tb, pw, pb)] + ([out.data_ptr()] if out is not None else [])
+    fused = (MASK_HEAD_FUSED and DW_FAST and C == 256 and N == 32 and pw.shape[1] == C and lib.mdqe_get_gemm_precision() == 0
+             and all(a % 16 == 0 for a in ptrs) and ldo % 4 == 0 and ldo >= N)
+    if not fused:
+        z = dwconv5x5(x, wt, bias, up2=True, tw=tw, tb=tb)
+        return linear(z.view(-1, C), pw, pb, out=out)
+    if out is None:
+        out = torch.empty((rows, N), dtype=torch.float32, device=x.device)
+    check(lib.mdqe_dwconv5x5_up2_pw_c256_f32(ptr(x), ptr(wt), ptr(bias), ptr(tw), ptr(tb), ptr(pw), ptr(pb), ptr(out), ldo, NI, Hs, Ws,
+                                             cur_stream()), "dwconv5x5_up2_pw_c256")
+    return out
 
 
 def msda(value, shapes_dev, starts_dev, loc, attn, groups=1, scale=1.0, out=None):
