@@ -679,6 +679,49 @@ int mdqe_annotate_yuv420sp(void* y, long y_pitch, long y_stride, void* uv, long 
                            const unsigned char* captions, int cap_len, const unsigned char* font,
                            int box, int scale, int min_area, void* stream);
 
+/* Per-track crops (csrc/crops.hip): one small fixed-size picture ("chip") per track and frame, cut from the frames the caller handed in and
+ * resized on the device -- what a re-identification or attribute model, a thumbnail gallery or a reviewer takes next.  A second consumer
+ * of the trio `annotate` reads: the frames, the label map, the map's geometry table.  labels: uint8 [F, Ho, Wo] as mdqe_final_label_map_u8
+ * writes it, row k's label is k + 1; geom: int32 [n*F, 5], row k*F + f = (area, xmin, ymin, xmax, ymax) of that label's visible region;
+ * frames, is_u8, frame_stride, h0, w0: exactly mdqe_render_overlay_u8's (never NULL here); the surface entry takes y .. bgr, exactly
+ * mdqe_yuv420sp_to_rgb_u8's, in their place (h0 = H, w0 = W).  Chip size Sh x Sw, each 1..512; pad256 in 0..256 (the box grows by
+ * pad256/256 of its width and height on each side); min_area >= 0; cutout in {0, 1}; fill = c0 | c1 << 8 | c2 << 16, three bytes in the
+ * frames' channel order.  Integers only, ONE definition, for row k and window frame f with (area, xmin, ymin, xmax, ymax) = geom[k*F + f]:
+ *   live       area >= max(1, min_area) and 0 <= xmin <= xmax < Wo and 0 <= ymin <= ymax < Ho: mdqe_annotate_u8's definition.  Any other
+ *              row -- the empty row, garbage -- is not live; the entries are memory-safe for every table content;
+ *   rect       px = ((xmax - xmin + 1) * pad256 + 128) >> 8, X0 = max(xmin - px, 0), X1 = min(xmax + px, Wo - 1), cw = X1 - X0 + 1; the
+ *              same with y and Ho gives py, Y0, Y1, ch;
+ *   footprint  of chip pixel (i, j), exact integer divisions: rows Ya = Y0 + (i*ch)/Sh up to but not including Yb = Y0 + ((i+1)*ch + Sh -
+ *              1)/Sh, columns Xa = X0 + (j*cw)/Sw up to but not including Xb = X0 + ((j+1)*cw + Sw - 1)/Sw.  Never empty, never leaves
+ *              the rect: a rect smaller than the chip is replicated, a larger one box-averaged;
+ *   counted    every (Y, X) of the footprint; with cutout only those with labels[f, Y, X] == k + 1;
+ *   source     mdqe_render_overlay_u8's: sy = (Y*h0)/Ho, sx = (X*w0)/Wo, s_c = frames[f, c, sy, sx], float32 as min(max(rint(v), 0), 255)
+ *              with NaN -> 0; for surfaces the (R, G, B) -- bgr: (B, G, R) -- that mdqe_yuv420sp_to_rgb_u8 defines for sample (sy, sx);
+ *   value      with m counted pixels and sum_c their channel sums: chip[i, j, c] = fill_c if m == 0, else (sum_c + m/2) / m;
+ *   not live   the whole chip is fill and the rect written is (0, 0, -1, -1); otherwise the rect written is (X0, Y0, X1, Y1).
+ * Frames taken: window frames f = f_first, f_first + f_step, ... < F, Fc of them.  The chip of (row k, t-th taken frame) is uint8 [Sh, Sw,
+ * 3], pixel-interleaved, at out + k*out_row_stride + (c_off + t)*Sh*Sw*3; its rect int32 [4] at rects + k*rect_row_stride + (c_off + t)*4
+ * (strides in elements).  Both are fully overwritten on every call and need no pre-initialisation; nothing else is written.
+ * MDQE_EINVAL, before any pointer is looked at, for Sh or Sw outside 1..512, pad256 outside 0..256, min_area < 0, cutout outside {0, 1},
+ * fill outside 0..0xFFFFFF, n outside 0..255, F < 0, Ho, Wo, h0 or w0 <= 0, Ho*Wo >= 2^24 (a uint32 sum of bytes cannot overflow), h0*Ho
+ * or w0*Wo >= 2^31, f_first < 0, f_step < 1, c_off < 0, (c_off + Fc)*Sh*Sw*3 >= 2^31, a row stride smaller than the c_off + Fc chips /
+ * rects of a row (n > 1), n * Fc * ceil(Sh*Sw / 256) >= 2^31, is_u8 outside {0, 1}, frames less than 3*h0*w0 apart (F > 1), and for
+ * the surface entry every refusal of mdqe_yuv420sp_to_rgb_u8 (fmt, matrix, pitches, strides; odd P010 plane pointers).  n == 0, F == 0
+ * or no frame taken (f_first >= F) return OK and launch nothing; NULL pointers give MDQE_ENULL.  Nothing needs to be aligned.
+ * One launch, no floating point (but the float32 frames' rint), no atomics: identical from run to run.  A block of 256 threads owns 256
+ * consecutive pixels of one chip; a chip whose footprints hold at most 256 source pixels gives each thread one chip pixel, a larger
+ * footprint is summed by a whole wave, lanes striding it, with a cross-lane reduction -- integer sums, so either split gives the same
+ * bits.  Never allocates, never synchronises. */
+int mdqe_track_crops_u8(const void* frames, int is_u8, long frame_stride, int h0, int w0,
+                        const unsigned char* labels, int F, int Ho, int Wo, const int* geom, int n,
+                        int f_first, int f_step, int Sh, int Sw, int pad256, int min_area, int cutout, int fill,
+                        unsigned char* out, long out_row_stride, int c_off, int* rects, long rect_row_stride, void* stream);
+int mdqe_track_crops_yuv420sp(const void* y, long y_pitch, long y_stride, const void* uv, long uv_pitch, long uv_stride,
+                              int H, int W, int fmt /*0 nv12, 1 p010*/, int matrix /*0 bt601, 1 bt709*/, int full_range, int bgr,
+                              const unsigned char* labels, int F, int Ho, int Wo, const int* geom, int n,
+                              int f_first, int f_step, int Sh, int Sw, int pad256, int min_area, int cutout, int fill,
+                              unsigned char* out, long out_row_stride, int c_off, int* rects, long rect_row_stride, void* stream);
+
 /* ---- COCO single-image branch, after the decoder (MDQE.inference_image, mdqe/mdqe.py:486-556), on the centre frame's
  * low-resolution logits [n,Hm,Wm]; aligned_bilinear x`factor` in closed form, crop [:h,:w].
  * stats[k] = {sum(sigmoid*[sigmoid>0.5]), count(sigmoid>0.5), xmin, ymin, xmax, ymax of (logit > 0)} (:512-516, :526;

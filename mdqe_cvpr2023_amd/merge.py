@@ -3,10 +3,11 @@
 Which forms a video produces is resolved ONCE, into a `Forms` record (from the model's flags offline, from `emit` online): per-track
 planes (dense or run boundaries), the label map (one uint8 plane per frame that names the track owning each pixel; its frames are
 disjoint between windows, so it needs no `stitch`), its overlay (that map painted over the frames the caller handed in, `FrameStore`,
-uint8 [F, Ho, Wo, 3]) and whose geometry.  A flushed window becomes those forms in ONE function, `build_window`; the three paths differ
-in the destination only: per window into per-video pinned memory (`_early_masks`), per window as a record (`_online_window`), or all
-windows into whole-video device buffers with one copy at the end (`video_result`).  Shared beside it: `to_host` (the hop on the copy
-stream), `rle.positions_to_rles`, `stitch`, `result_head` / `track_geometry` (a result's keys).
+uint8 [F, Ho, Wo, 3]), per-track crops cut from those frames along the map's visible regions (`crop_frames`, render.Crops; offline they
+gather in one device table per video, `CropTable`) and whose geometry.  A flushed window becomes those forms in ONE function,
+`build_window`; the three paths differ in the destination only: per window into per-video pinned memory (`_early_masks`), per window
+as a record (`_online_window`), or all windows into whole-video device buffers with one copy at the end (`video_result`).  Shared
+beside it: `to_host` (the hop on the copy stream), `rle.positions_to_rles`, `stitch`, `result_head` / `track_geometry` (a result's keys).
 `OverlapTables` is not an output form but a score: with a ground truth handed in (vis_score.GroundTruth), every flushed window's final
 masks are counted against it where they are decided (ops.final_masks_overlap) -- "pred_gt", beside whatever form the masks take."""
 import contextlib
@@ -29,12 +30,13 @@ class Forms:
     label_geometry: bool = False          # ... and of the labels' visible regions
     early_always: bool = False            # model.rle_output: the early path even with model.early_masks off, with or without planes
     surface: bool = False                 # the overlay is painted onto the decoder surfaces handed in: a YuvFrames, not RGB pixels
+    crops: bool = False                   # per-track chips cut from the frames (render.Crops; the map and its table: a device scratch if not returned)
 
     @classmethod
-    def _of(cls, model, geometry, planes, labels, overlay, early_always=False, surface=False):
+    def _of(cls, model, geometry, planes, labels, overlay, early_always=False, surface=False, crops=False):
         """geometry None: the model's flag.  It describes the planes where there are planes, and the labels' regions where the map is returned."""
         g = bool(getattr(model, "geometry_output", False) if geometry is None else geometry)
-        return cls(planes, labels, overlay, g and planes is not None, g and labels, early_always, bool(overlay and surface))
+        return cls(planes, labels, overlay, g and planes is not None, g and labels, early_always, bool(overlay and surface), bool(crops))
 
     @classmethod
     def of_model(cls, model, emit_masks=True, geometry=None):
@@ -43,13 +45,15 @@ class Forms:
             return cls()
         lab, rle = getattr(model, "label_output", False), bool(getattr(model, "rle_output", False))
         pic = getattr(model, "overlay_output", False)
-        return cls._of(model, geometry, None if lab == "only" else "rle" if rle else "dense", bool(lab), bool(pic), rle, pic == "surface")
+        return cls._of(model, geometry, None if lab == "only" else "rle" if rle else "dense", bool(lab), bool(pic), rle, pic == "surface",
+                       getattr(model, "crop_output", None) is not None)
 
     @classmethod
-    def of_emit(cls, emit, geometry=False, model=None, surface=False):
-        """Online ("masks" | "rle" | "labels" | "overlay"; surface: the overlay onto the surfaces pushed)."""
+    def of_emit(cls, emit, geometry=False, model=None, surface=False, crops=False):
+        """Online ("masks" | "rle" | "labels" | "overlay"; surface: the overlay onto the surfaces pushed; crops: chips beside it)."""
         lab = emit in ("labels", "overlay")
-        return cls._of(model, geometry, None if lab else {"masks": "dense", "rle": "rle"}[emit], lab, emit == "overlay", surface=surface)
+        return cls._of(model, geometry, None if lab else {"masks": "dense", "rle": "rle"}[emit], lab, emit == "overlay", surface=surface,
+                       crops=crops)
 
 
 def dense_masks(m, idx, stride, frame_hw, out_size, geometry, out, f_off):
@@ -253,6 +257,69 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
     return geom if geometry else None
 
 
+def crop_frames(n, nf, labels, l_off, geom, source, f0, spec, out, rects, c_off):
+    """A window's crops: for the window's n rows and the frames `spec` (render.Crops) takes among video frames [f0, f0 + nf), the chips
+    into out[:n, c_off:] and their rects into rects[:n, c_off:] (device), cut from the frames of `source` (a FrameStore) by the label map
+    labels[l_off:l_off + nf] and its geometry table geom [n, nf, 5] (`label_maps`) -- one ops.track_crops launch per contiguous piece
+    of source frames (ops.track_crops_yuv where the store holds decoder surfaces), the table sliced per piece as `overlay_frames` does
+    for the annotation pass and the first frame taken counted from the piece's own start, on the current stream.  -> chips written."""
+    from . import ops
+    done = 0
+    if not n:
+        return len(spec.taken(f0, int(f0) + nf))
+    for t, first in source.pieces(int(f0), int(f0) + nf, stream=torch.cuda.current_stream(labels.device)):
+        k, d = len(t), first - int(f0)
+        fst = spec.first_in(first)
+        cnt = len(range(fst, k, spec.every))
+        if cnt:
+            g = geom if k == nf else geom[:, d:d + k].contiguous()     # (the table's rows are k * F + f of the frames of ONE call)
+            fn = ops.track_crops if torch.is_tensor(t) else ops.track_crops_yuv
+            fn(labels[l_off + d:l_off + d + k], t, g, n, spec.size, out, c_off + done, rects, fst, spec.every, spec.pad256, spec.min_area,
+               spec.cutout, spec.fill)
+        done += cnt
+    return done
+
+
+class CropTable:
+    """A whole video's crops on the device (the offline paths): chips uint8 [rows, Lc, Sh, Sw, 3] and rects int32 [rows, Lc, 4] for the
+    tracker rows seen so far, Lc = ceil(L / every) -- rows * Lc * Sh * Sw * 3 bytes, which `every` scales.  Every window's launches write
+    straight into it; a row that appears grows the table, and the frames before its first window hold `fill` and the rect (0, 0, -1, -1)
+    (`stitch`'s rule for absent rows).  `result` selects the outputs' rows and reads them back once."""
+
+    def __init__(self, spec, n_frames, device):
+        self.spec, self.n_frames, self.device = spec, int(n_frames), device
+        self.out = self.rects = None
+
+    def _blank(self, rows):
+        sh, sw = self.spec.size
+        out = torch.tensor(self.spec.fill, dtype=torch.uint8, device=self.device).expand(rows, self.spec.count(self.n_frames), sh, sw, 3).contiguous()
+        rects = torch.tensor([0, 0, -1, -1], dtype=torch.int32, device=self.device).expand(rows, self.spec.count(self.n_frames), 4).contiguous()
+        return out, rects
+
+    def rows(self, n):
+        """The table with at least n rows (a few more: a video's tracks appear over its first windows), on the current stream."""
+        have = 0 if self.out is None else int(self.out.shape[0])
+        if n > have or self.out is None:
+            out, rects = self._blank(max(n, 1) + 3 - have)
+            self.out, self.rects = (out, rects) if self.out is None else (torch.cat([self.out, out]), torch.cat([self.rects, rects]))
+        return self.out, self.rects
+
+    def result(self, inst):
+        """{"pred_crops": uint8 [n_out, Lc, Sh, Sw, 3], "pred_crop_rects": int32 [n_out, Lc, 4]} in pinned host memory for the outputs whose
+        tracker rows are `inst`, and "pred_crop_frames", the video frames of the Lc columns."""
+        cur = torch.cuda.current_stream(self.device)
+        out, rects = self.rows(max(list(inst) + [0]) + 1)
+        for t in (out, rects):
+            t.record_stream(cur)
+        sel = torch.tensor(list(inst), dtype=torch.int64, device=self.device)
+        dev = (out[sel], rects[sel])
+        host = tuple(torch.empty(d.shape, dtype=d.dtype, pin_memory=True) for d in dev)
+        for h, d in zip(host, dev):
+            h.copy_(d, non_blocking=True)
+        cur.synchronize()
+        return {"pred_crops": host[0], "pred_crop_rects": host[1], "pred_crop_frames": self.spec.taken(0, self.n_frames)}
+
+
 def surface_kind(source, out_size):
     """What a surface overlay paints on: the kind (YuvFrames.meta()) of the surfaces `source` (a FrameStore) holds, which must be of the
     output size (None: not looked at) -- the painting kernel does not resample.  Raises the two refusals of the form."""
@@ -294,21 +361,28 @@ def rle_positions(m, idx, stride, frame_hw, out_size, geometry):
 
 
 def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels=None, picture=None, paint=None,
-                 hop=lambda stage, geom: geom):
+                 hop=lambda stage, geom: geom, crops=None):
     """What `forms` asks for of ONE flushed window (logits m [n, F, Hm, Wm]), on the current stream, for every path; the only caller
     of `overlay_frames`, `label_maps`, `dense_masks` and `rle_positions`.  First the label map of ALL n rows into labels = (device
     buffer, frame offset) and, with picture = (buffer, offset), its overlay, painted from paint = (FrameStore, first video frame,
     render.Style, the window's class rows [n, K] on the host -- what a mosaic of classes is chosen by).  Then the planes of `rows`
     (int32 device; None or empty: none): dense into planes = (buffer, offset) when given, else, with forms.planes == "rle", their run boundaries on the host.  `hop(stage, geom) -> geom` runs behind each stage ("labels" |
-    "planes") that filled device buffers: the early and the online path send them to the host there, the map under the planes' kernel.
+    "crops" | "planes") that filled device buffers: the early and the online path send them to the host there, the map under the planes' kernel.
+    crops = (render.Crops, FrameStore, first video frame, chips buffer, rects buffer, chip offset): behind the labels stage the window's
+    chips (`crop_frames`) from the map and its table, which are then made whether or not `forms` returns them.
     -> (labels' geometry table [n, F, 5] or None, planes' table [len(rows), F, 5] or None, (pos, n_pos) of `rle_positions` or None)."""
     lgeom = pgeom = runs = None
     if labels is not None:
+        table = forms.label_geometry or crops is not None
         if picture is not None:
-            lgeom = overlay_frames(m, stride, frame_hw, out_size, forms.label_geometry, *labels, *paint, *picture)
+            dgeom = overlay_frames(m, stride, frame_hw, out_size, table, *labels, *paint, *picture)
         else:
-            lgeom = label_maps(m, stride, frame_hw, out_size, forms.label_geometry, *labels)
-        lgeom = hop("labels", lgeom)
+            dgeom = label_maps(m, stride, frame_hw, out_size, table, *labels)
+        lgeom = hop("labels", dgeom if forms.label_geometry else None)
+        if crops is not None:
+            spec, source, f0, chips, rects, c_off = crops
+            crop_frames(int(m.shape[0]), int(m.shape[1]), *labels, dgeom, source, f0, spec, chips, rects, c_off)
+            hop("crops", None)
     if rows is not None and int(rows.numel()):
         if planes is not None:
             pgeom = hop("planes", dense_masks(m, rows, stride, frame_hw, out_size, forms.plane_geometry, *planes))
@@ -416,7 +490,7 @@ def result_head(model, cls_clips, out_size, n_frames, score=None, track_ids=True
 
 
 def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True, frame_source=None, score=None,
-                 forms=None):
+                 forms=None, crops=None):
     """mdqe/mdqe.py:430-471.  The x4 aligned-bilinear up-sampling, sigmoid, crop (:357-358), nearest resize to the original size and
     the 0.5 threshold (:458-462) run as ONE kernel per window; windows in which an instance did not exist yet stay zero (:442).
     `forms`: the merger's record (ClipMerger.finish); None: resolved from the model here.  `early` (EarlyMasks): every form is on the
@@ -425,10 +499,11 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
     planes are then encoded on the host.  `score` (OverlapTables): the counts gathered at every flush on any path -> "pred_gt".
     "pred_label_map": uint8 [L, Ho, Wo], host; label t + 1 = tracker row t, 0 = background, so pred_label_map == pred_track_ids[j] + 1
     is output j's exclusive region.  "pred_overlay": uint8 [L, Ho, Wo, 3], pinned host; with forms.surface a YuvFrames of
-    L painted surfaces (pinned host, tight pitch)."""
+    L painted surfaces (pinned host, tight pitch).  `crops` (CropTable): the early path's table, filled at every flush; without it and
+    with forms.crops the table is filled here, window by window -> "pred_crops", "pred_crop_rects", "pred_crop_frames"."""
     if forms is None:
         forms = Forms.of_model(model, emit_masks)
-        forms = dataclasses.replace(forms, overlay=forms.overlay and frame_source is not None)
+        forms = dataclasses.replace(forms, overlay=forms.overlay and frame_source is not None, crops=forms.crops and frame_source is not None)
     out_size = Ho, Wo = int(image_size[0]), int(image_size[1])
     res, inst = result_head(model, cls_clips, out_size, n_frames, score, track_ids=False)
     rows, host, planes_res = inst, {}, {"pred_masks": []}          # ([]: no per-track planes in either form)
@@ -448,7 +523,9 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
         rows = [sel.index(i) for i in inst]                        # rows of the planes' buffer = positions in sel
         plane_geoms, label_geoms, u8 = [], [], dict(dtype=torch.uint8, device=model.device)
         # (the windows tile [0, n_frames): every row of the map and the picture is written; a track's planes start at its first window)
-        d_lab = torch.empty(n_frames, Ho, Wo, **u8) if forms.labels or forms.overlay else None
+        d_lab = torch.empty(n_frames, Ho, Wo, **u8) if forms.labels or forms.overlay or forms.crops else None
+        if forms.crops:
+            crops = CropTable(model.crop_output, n_frames, model.device)
         d_pic = torch.empty(n_frames, Ho, Wo, 3, **u8) if forms.overlay and not forms.surface else None
         if forms.surface:
             d_pic = surface_picture(frame_source, n_frames, out_size, model.device)
@@ -459,7 +536,8 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
             cnt = sum(1 for i in sel if i < n)                     # sel is ascending: these are its first `cnt` entries
             at = [None if t is None else (t, f_off) for t in (d_planes, d_lab, d_pic)]
             lg, pg, _ = build_window(m, forms, sel_dev[:cnt] if forms.planes else None, model.cfg.match_stride, frame_hw, out_size, *at,
-                                     paint=(frame_source, f_off, model.overlay_style, cls_clips[i]) if forms.overlay else None)
+                                     paint=(frame_source, f_off, model.overlay_style, cls_clips[i]) if forms.overlay else None,
+                                     crops=(crops.spec, frame_source, f_off, *crops.rows(n), crops.spec.count(f_off)) if forms.crops else None)
             label_geoms.append((f_off, nf, n, lg))
             if cnt:
                 plane_geoms.append((f_off, nf, cnt, pg))
@@ -483,8 +561,10 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
                 planes_res = {"pred_rles": [enc[p] for p in rows]}
             else:
                 planes_res = {"pred_masks": [planes[p] for p in rows]}
-    if forms.labels or forms.overlay:
+    if forms.labels or forms.overlay or forms.crops:
         res.setdefault("pred_track_ids", list(inst))
+    if forms.crops:
+        res.update(crops.result(inst))
     if forms.labels:
         res["pred_label_map"] = host["labels"][:n_frames]
     if forms.overlay:
@@ -506,7 +586,7 @@ class ClipMerger:
     EARLY_TRACKS = 48                       # tracks per video the early-mask path budgets pinned memory for
 
     def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True, online=None, geometry=None, frame_source=None,
-                 style=None, ground_truth=None, surface=False, surface_pitch_align=1):
+                 style=None, ground_truth=None, surface=False, surface_pitch_align=1, crops=None):
         self.model, self.frame_hw, self.out_size, self.mask_hw = model, frame_hw, out_size, mask_hw
         self.emit_masks = emit_masks                # False: scores / labels only (ranks > 0 of a sharded video)
         # online ("masks" | "rle" | "labels" | "overlay"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their
@@ -515,7 +595,11 @@ class ClipMerger:
         self.online = online
         # the forms of this video, for every path (geometry None: model.geometry_output; online sessions pass theirs)
         # (surface, surface_pitch_align: an online session's; offline the model's overlay_output == "surface", at a tight pitch)
-        self.forms = forms = Forms.of_emit(online, geometry, model, surface) if online else Forms.of_model(model, emit_masks, geometry)
+        # crops (render.Crops): an online session's; offline the model's crop_output
+        self.crop_spec = crops if online else (getattr(model, "crop_output", None) if emit_masks else None)
+        self.forms = forms = (Forms.of_emit(online, geometry, model, surface, self.crop_spec is not None) if online
+                              else Forms.of_model(model, emit_masks, geometry))
+        self.crop_table = None                      # the early path's CropTable, from its first window
         self.surface_pitch_align = surface_pitch_align
         self.geometry = forms.plane_geometry or forms.label_geometry
         # False | True | "only" (model.label_output): the label map next to -- or, "only", instead of -- the per-track planes
@@ -523,6 +607,9 @@ class ClipMerger:
         # what an overlay paints on: the frames of `frame_source` (a FrameStore), in `style`
         self.frame_source = frame_source
         self.style = style if style is not None else getattr(model, "overlay_style", None)
+        if forms.crops and frame_source is None:
+            raise ValueError("crop output needs the frames of the whole video on this device; this path does not hold them (the sharded "
+                             "driver does not offer it: rank 0 does not hold every frame)")
         if forms.overlay and frame_source is None:
             raise ValueError("overlay output needs the frames of the whole video on this device; this path does not hold them (the sharded "
                              "driver does not offer it: rank 0 does not hold every frame)")
@@ -634,21 +721,35 @@ class ClipMerger:
         overlay's mosaic of classes).  -> build_window's."""
         forms, u8 = self.forms, dict(dtype=torch.uint8, device=self.dev)
         n, nf, Ho, Wo = int(m.shape[0]), int(m.shape[1]), int(self.out_size[0]), int(self.out_size[1])
-        lab = torch.empty(nf, Ho, Wo, **u8) if forms.labels or forms.overlay else None    # (an overlay alone: a scratch, not copied)
+        lab = torch.empty(nf, Ho, Wo, **u8) if forms.labels or forms.overlay or forms.crops else None    # (an overlay or crops alone: a scratch, not copied)
         pic = torch.empty(nf, Ho, Wo, 3, **u8) if forms.overlay and not forms.surface else None
         if forms.surface:                           # (the host's pitch: the window copy is then two plain copies, padding and all)
             pic = surface_picture(self.frame_source, nf, self.out_size, self.dev, self.surface_pitch_align)
         rows = torch.arange(n, dtype=torch.int32, device=self.dev) if n and forms.planes else None
         planes = torch.empty(n, nf, Ho, Wo, **u8) if rows is not None and forms.planes == "dense" else None
         copies = {"labels": (pairs("labels", lab) if forms.labels else []) + (pairs("overlay", pic) if forms.overlay else []),
-                  "planes": pairs("planes", planes) if planes is not None else []}
+                  "planes": pairs("planes", planes) if planes is not None else [], "crops": []}
+        crop = None
+        if forms.crops:
+            spec = self.crop_spec
+            if self.online:                         # the window's own chips: [n, frames taken, Sh, Sw, 3] and their rects, sent to the host
+                fc = len(spec.taken(self.f_off, self.f_off + nf))
+                chips = torch.empty((n, fc) + spec.size + (3,), **u8)
+                rects = torch.empty((n, fc, 4), dtype=torch.int32, device=self.dev)
+                copies["crops"] = pairs("crops", chips) + pairs("crop_rects", rects)
+                crop = (spec, self.frame_source, self.f_off, chips, rects, 0)
+            else:                                   # the video's table on the device: read back once, at the end
+                if self.crop_table is None:
+                    self.crop_table = CropTable(spec, self.n_frames, self.dev)
+                crop = (spec, self.frame_source, self.f_off, *self.crop_table.rows(n), spec.count(self.f_off))
         # (the copy stream is created BEFORE the window's kernels are launched, and only by a window that copies, as ever: the order
         # streams are first used in decides their queues)
-        cs = copy_stream(self.model) if copies["labels"] or copies["planes"] else None
+        cs = copy_stream(self.model) if copies["labels"] or copies["planes"] or copies["crops"] else None
         at = [None if t is None else (t, 0) for t in (planes, lab, pic)]
         return build_window(m, forms, rows, self.model.cfg.match_stride, self.frame_hw, self.out_size, *at,
-                            paint=(self.frame_source, self.f_off, self.style, c),
-                            hop=lambda stage, geom: to_host(cs, self.side, copies[stage], geom, event()))
+                            paint=(self.frame_source, self.f_off, self.style, c), crops=crop,
+                            hop=lambda stage, geom: (to_host(cs, self.side, copies[stage], geom, event())
+                                                     if copies[stage] or geom is not None else None))   # (a scratch stage: nothing to send)
 
     def _early_masks(self, m, c=None):
         """Every form of EVERY instance tracked so far goes to pinned host memory while later windows compute; finish() then only
@@ -699,6 +800,9 @@ class ClipMerger:
             if not torch.is_tensor(buf):            # a surface picture: pinned surfaces of the same pitch, both planes
                 host = rec["overlay"] = surface_picture(self.frame_source, nf, out_size, "cpu", self.surface_pitch_align, pin_memory=True)
                 return [(host.y, buf.y), (host.uv, buf.uv)]
+            if kind in ("crops", "crop_rects"):     # (their shape changes with the tracks: not the mask pool's kind of buffer)
+                rec[kind] = torch.empty(tuple(buf.shape), dtype=buf.dtype, pin_memory=bool(buf.numel()))
+                return [(rec[kind], buf)] if buf.numel() else []
             host = self.model.pinned_mask_buffer(tuple(buf.shape))
             rec.update({"masks": host.view(torch.bool)} if kind == "planes" else {kind: host})
             return [(host, buf)]
@@ -707,6 +811,8 @@ class ClipMerger:
             rec["ready"] = rec["ready"] or torch.cuda.Event()
             return rec["ready"]
         lgeom, pgeom, runs = self._window_to_host(m, pairs, event, c)
+        if forms.crops:
+            rec["crop_frames"] = self.crop_spec.taken(self.f_off, self.f_off + nf)
         if forms.planes == "rle":
             rec["rles"] = R.positions_to_rles(*runs, out_size, nf) if n else []
         if forms.label_geometry:
@@ -733,4 +839,5 @@ class ClipMerger:
             for _, m in self.windows:
                 m.record_stream(self.main)
         return self.model.inference_video(self.out_size, self.cls_clips, self.windows, self.frame_hw, self.f_off, early=self.early,
-                                          emit_masks=self.emit_masks, frame_source=self.frame_source, score=self.score, forms=self.forms)
+                                          emit_masks=self.emit_masks, frame_source=self.frame_source, score=self.score, forms=self.forms,
+                                          **({"crops": self.crop_table} if self.forms.crops else {}))

@@ -118,7 +118,10 @@ class MDQE(nn.Module):
         # decoder's bits, 1.5 bytes per pixel are kept and read back instead of 3, and the result goes to an encoder as it is.  The
         # output size must be the surfaces' (nothing is resampled); RGB frames are refused.
         self.overlay_output = False
-        self.merge_on_cpu = None                    # None: cfg.merge_on_cpu (MODEL.MDQE.MERGE_ON_CPU); True / False override it
+        # A render.Crops: forward() on a video adds "pred_crops" / "pred_crop_rects" / "pred_crop_frames", one fixed-size picture per
+        # output and taken frame, cut and resized on the device (ops.track_crops).  None: nothing changes.  (A property: see below.)
+        self.crop_output = None
+        self.merge_on_cpu = None                   # None: cfg.merge_on_cpu (MODEL.MDQE.MERGE_ON_CPU); True / False override it
         # Final masks of a tracker window leave the device when the window is flushed (pinned host buffers, copied under the later
         # windows' compute) instead of in one pass + one 100-MB copy after the last window.  Independent of MERGE_ON_CPU, which in the
         # reference only picks the device the window results wait on (mdqe/mdqe.py:185-186,337,354-355) and never changes an output.
@@ -288,6 +291,26 @@ class MDQE(nn.Module):
         if value:
             self.check_label_capacity()
         self.__dict__["_overlay_output"] = value
+
+    @property
+    def crop_output(self):
+        """None, or a render.Crops: forward() on a video adds "pred_crops" (uint8 [n_out, Lc, Sh, Sw, 3], pinned host: per output and
+        taken frame one fixed-size picture cut from the frames handed in -- with resize_on_device the original-size frames -- along the
+        track's visible region of the label map and resized on the device, ops.track_crops), "pred_crop_rects" (int32 [n_out, Lc, 4],
+        the source rects (X0, Y0, X1, Y1) in output pixels; (0, 0, -1, -1) beside a chip of `fill` where the track has no region),
+        "pred_crop_frames" (the Lc = ceil(L / every) video frames taken) and "pred_track_ids".  Beside every other output form.  The
+        video's chips wait on the device, n_tracks * Lc * Sh * Sw * 3 bytes, for one read-back at the end.  Videos only, one device
+        (sharding.py refuses it).  None: nothing changes."""
+        return self.__dict__.get("_crop_output", None)
+
+    @crop_output.setter
+    def crop_output(self, value):
+        from .render import Crops
+        if value is not None and not isinstance(value, Crops):
+            raise ValueError("crop_output must be None or a render.Crops, got %r" % (value,))
+        if value is not None:
+            self.check_label_capacity()
+        self.__dict__["_crop_output"] = value
 
     @property
     def overlay_style(self):
@@ -931,9 +954,9 @@ class MDQE(nn.Module):
         return gt
 
     def _frame_source(self, src, src_ready, out_size=None):
-        """The whole video as the frame source of an overlay (merge.FrameStore), or None with overlay_output off.  overlay_output =
+        """The whole video as the frame source of an overlay or of crops (merge.FrameStore), or None with both off.  overlay_output =
         "surface": refused here, before anything of the video runs, for RGB frames and for an output size that is not the surfaces'."""
-        if not self.overlay_output:
+        if not self.overlay_output and self.crop_output is None:
             return None
         store = merge.FrameStore()
         store.add(0, src, src_ready)
@@ -1031,7 +1054,7 @@ class MDQE(nn.Module):
             yield guarded(step)
 
     def online_video(self, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None,
-                     surface=False, surface_pitch_align=1):
+                     surface=False, surface_pitch_align=1, crops=None):
         """An online session over ONE video whose frames arrive in pushes (a camera, a stream, a video too long to hold): push()
         returns each tracker window as soon as it is final, close() the rest, result() the video-level scores / labels / tracks.
         height / width: output mask size (default: the frame size); emit: "masks" (bool [n, F, H, W] per window), "rle" or "labels" (one
@@ -1042,10 +1065,11 @@ class MDQE(nn.Module):
         forward()'s with geometry_output; ground_truth (vis_score.GroundTruth): result() carries "pred_gt", forward()'s with the input's
         "ground_truth" (a push past its length raises); surface (with emit="overlay", pushes of preprocess.YuvFrames): `win.overlay` is
         a YuvFrames of painted surfaces of the pushed format instead of RGB pixels (surface_pitch_align: its row pitch in bytes is
-        rounded up to a multiple of it).  See online.py."""
+        rounded up to a multiple of it); crops (render.Crops, beside any emit): every window carries `crops` / `crop_rects` /
+        `crop_frames`, one fixed-size picture per track and taken frame (`crop_output`'s).  See online.py."""
         from .online import OnlineVideo
         return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep, geometry=geometry, style=style, ground_truth=ground_truth,
-                           surface=surface, surface_pitch_align=surface_pitch_align)
+                           surface=surface, surface_pitch_align=surface_pitch_align, crops=crops)
 
     def inference_image(self, batched_inputs):
         """COCO single-image branch: MDQE.forward :213-236 -> mdqe.forward (models/mdqe.py:62-70) -> decoder
@@ -1062,6 +1086,9 @@ class MDQE(nn.Module):
         if getattr(self, "overlay_output", False) == "surface":
             raise ValueError("overlay_output = 'surface': the COCO image branch has no overlay (painted surfaces are a video output: use a "
                              "video config, or set overlay_output = False)")
+        if getattr(self, "crop_output", None) is not None:
+            raise ValueError("crop_output: the COCO image branch has no crops (per-track crops are a video output: use a video config, or "
+                             "set crop_output = None)")
         from .preprocess import YuvFrames
         if isinstance(item["image"], YuvFrames):
             raise ValueError("YuvFrames: the COCO image branch takes RGB tensors (decoder surfaces are a video input; convert one with "

@@ -47,6 +47,16 @@ session keeps the pushed surfaces themselves -- 1.5 bytes per pixel for NV12 ins
 same `frames_held` bound, and reads 1.5 bytes per pixel back.  The output size must be the surfaces' size (nothing is resampled: to run
 the model below it, push full-size surfaces and set model.resize_on_device).  win.labels is what it is without `surface`; keep=True
 makes result()["pred_overlay"] one YuvFrames of L surfaces, equal to forward()'s with model.overlay_output = "surface".
+
+crops=render.Crops(size=(128, 64), pad=0.0, cutout=False, fill=(0, 0, 0), min_area=0, every=1), beside ANY emit: every window also
+carries one fixed-size picture per track and taken frame, cut from the frames AS PUSHED (with model.resize_on_device: the original-size
+frames) along the track's visible region of the label map and resized on the device (ops.track_crops; the rule is in
+include/mdqe_hip.h): `win.crops` uint8 [n, Fc, Sh, Sw, 3] (pinned host, channel order = the frames'), `win.crop_rects` int32 [n, Fc, 4]
+(the source rect (X0, Y0, X1, Y1) in output pixels, inclusive; (0, 0, -1, -1) and a chip of `fill` where the track has no region) and
+`win.crop_frames`, the Fc video frames taken -- those with f % every == 0.  The label map and its table are then made for every emit (a
+device scratch where the emit does not return them), and the session keeps the pushed frames under the `frames_held` bound above
+whatever the emit.  keep=True adds "pred_crops" / "pred_crop_rects" / "pred_crop_frames" to result(), equal to forward()'s with
+model.crop_output.
 """
 import contextlib
 import dataclasses
@@ -134,7 +144,8 @@ class Window:
     [f1-f0, H, W] on the host (track_ids[i] + 1 where track i owns the pixel, 0 = background), masks and rles None, boxes / areas those
     of the labels' visible regions.  With emit="overlay": `labels` as above and `overlay`, uint8 [f1-f0, H, W, 3] on the host, the
     frames with that map painted on -- or, in a surface=True session, a preprocess.YuvFrames of f1-f0 painted surfaces.  (`labels` and `overlay` are init-only pseudo-fields stored as plain attributes:
-    dataclasses.fields(Window) is what it was.)"""
+    dataclasses.fields(Window) is what it was.)  In a session with crops=: `crops` uint8 [n, Fc, Sh, Sw, 3], `crop_rects` int32 [n, Fc, 4]
+    and `crop_frames`, the Fc video frames taken (pseudo-fields of the same kind)."""
     frames: tuple
     track_ids: list
     cls_probs: torch.Tensor
@@ -144,15 +155,19 @@ class Window:
     areas: torch.Tensor = None
     labels: dataclasses.InitVar[torch.Tensor] = None
     overlay: dataclasses.InitVar[torch.Tensor] = None
+    crops: dataclasses.InitVar[torch.Tensor] = None
+    crop_rects: dataclasses.InitVar[torch.Tensor] = None
+    crop_frames: dataclasses.InitVar[list] = None
 
-    def __post_init__(self, labels, overlay):
+    def __post_init__(self, labels, overlay, crops, crop_rects, crop_frames):
         self.labels = labels
         self.overlay = overlay
+        self.crops, self.crop_rects, self.crop_frames = crops, crop_rects, crop_frames
 
 
 class OnlineVideo:
     def __init__(self, model, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None,
-                 surface=False, surface_pitch_align=1):
+                 surface=False, surface_pitch_align=1, crops=None):
         if emit not in ("masks", "rle", "labels", "overlay"):
             raise ValueError("online_video: emit must be 'masks', 'rle', 'labels' or 'overlay'")
         if not isinstance(surface, bool):
@@ -165,7 +180,14 @@ class OnlineVideo:
         if surface and model.cfg.is_coco:
             raise ValueError("online_video: surface=True with a COCO image config: painted surfaces are a video output (use a video config)")
         self.surface, self.surface_pitch_align = surface, int(k)
-        if emit in ("labels", "overlay"):
+        if crops is not None:
+            from .render import Crops
+            if not isinstance(crops, Crops):
+                raise ValueError("online_video: crops must be a render.Crops, got %s" % type(crops).__name__)
+            if model.cfg.is_coco:
+                raise ValueError("online_video: crops with a COCO image config: per-track crops are a video output (use a video config)")
+        self.crops = crops
+        if emit in ("labels", "overlay") or crops is not None:
             model.check_label_capacity()
         from .render import Style
         if style is not None and (emit != "overlay" or not isinstance(style, Style)):
@@ -197,8 +219,8 @@ class OnlineVideo:
 
     @property
     def frames_held(self):
-        """Frames the session holds on the device for painting (emit="overlay"; else 0): at most those no window has emitted yet plus
-        the largest push - 1."""
+        """Frames the session holds on the device for painting or cropping (emit="overlay" or crops=; else 0): at most those no window
+        has emitted yet plus the largest push - 1."""
         return self.store.frames_held if self.store is not None else 0
 
     @contextlib.contextmanager
@@ -227,12 +249,12 @@ class OnlineVideo:
         self.hw = (h, w)
         self.geo = model.engine.geometry(h, w)
         self.mask_hw = (self.geo.Hp // cfg.match_stride, self.geo.Wp // cfg.match_stride)
-        if self.emit == "overlay":
+        if self.emit == "overlay" or self.crops is not None:
             from .merge import FrameStore
             self.store = FrameStore()
         self.merger = ClipMerger(model, self.hw, self.out_size, self.mask_hw, n_frames=None, online=self.emit,
                                  geometry=self.geometry, frame_source=self.store, style=self.style, ground_truth=self.ground_truth,
-                                 surface=self.surface, surface_pitch_align=self.surface_pitch_align)
+                                 surface=self.surface, surface_pitch_align=self.surface_pitch_align, crops=self.crops)
         shapes = model.engine.cache_shapes(self.geo)
         per_frame = 4 * sum(int(np.prod(sh)) for sh in shapes.values())
         forced = int(os.environ.get("MDQE_CACHE_FRAMES", "0"))
@@ -264,7 +286,8 @@ class OnlineVideo:
                 self.geoms.append((r["frames"][0], r["frames"][1] - r["frames"][0], n, r["geom"]))
             out.append(Window(frames=r["frames"], track_ids=list(range(n)), cls_probs=r["cls_probs"],
                               masks=r.get("masks"), rles=r.get("rles"), boxes=boxes, areas=areas, labels=r.get("labels"),
-                              overlay=r.get("overlay")))
+                              overlay=r.get("overlay"), crops=r.get("crops"), crop_rects=r.get("crop_rects"),
+                              crop_frames=r.get("crop_frames")))
         del self.merger.emitted[:]
         if self.store is not None:
             # the chunks that lie wholly before the first frame no window has emitted are done with; what stays and may be the caller's
@@ -366,5 +389,16 @@ class OnlineVideo:
                 res["pred_rles"] = merge.stitch_rles(inst, self.received, (Ho, Wo), wins)
             else:
                 res["pred_masks"] = merge.stitch(inst, self.received, wins, lambda k: torch.zeros((k, Ho, Wo), dtype=torch.bool), torch.cat)
+        if self.keep and forms.crops:             # (per output the track's chips over the taken frames; absent before its first window)
+            spec = self.crops
+            fill = torch.tensor(spec.fill, dtype=torch.uint8).expand(spec.size + (3,))
+            none = torch.tensor([0, 0, -1, -1], dtype=torch.int32)
+            at = [(spec.count(w.frames[0]), len(w.crop_frames), len(w.track_ids)) for w in self.kept]
+            lc = spec.count(self.received)
+            for key, attr, empty in (("pred_crops", "crops", fill), ("pred_crop_rects", "crop_rects", none)):
+                rows = merge.stitch(inst, lc, [a + (getattr(w, attr),) for a, w in zip(at, self.kept)],
+                                    lambda k, e=empty: e.expand((k,) + tuple(e.shape)), torch.cat)
+                res[key] = torch.stack(rows) if rows else torch.zeros((0, lc) + tuple(empty.shape), dtype=empty.dtype)
+            res["pred_crop_frames"] = spec.taken(0, self.received)
         self._result = res
         return res

@@ -902,6 +902,120 @@ def annotate_yuv(yuv, geom, n, palette_yuv, ink_yuv, captions, font, f_off=0, bo
     return yuv
 
 
+def _crop_args(name, labels, n_frames, device, geom, n, size, out, c_off, rects, first, step, pad256, min_area, cutout, fill):
+    """The checks track_crops and track_crops_yuv share; allocates `out` / `rects` when None.
+    -> (F, Ho, Wo, Sh, Sw, frames taken, packed fill, out, rects)."""
+    # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
+    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        raise RuntimeError("%s: labels must be contiguous uint8 [F, Ho, Wo]" % name)
+    F, Ho, Wo = (int(v) for v in labels.shape)
+    if n_frames != F:
+        raise RuntimeError("%s: labels hold F = %d frames, the frames handed in %d" % (name, F, n_frames))
+    if Ho < 1 or Wo < 1 or Ho * Wo >= 2 ** 24:
+        raise RuntimeError("%s: Ho, Wo must be positive with Ho*Wo < 2^24, got %s" % (name, tuple(labels.shape)))
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= 255:
+        raise RuntimeError("%s: n must be an int in 0..255, got %r" % (name, n))
+    if (not isinstance(size, (tuple, list)) or len(size) != 2
+            or any(isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 512 for v in size)):
+        raise RuntimeError("%s: size must be (Sh, Sw), ints in 1..512, got %r" % (name, size))
+    Sh, Sw = size
+    for what, v, lo, hi in (("pad256", pad256, 0, 256), ("min_area", min_area, 0, 2 ** 31 - 1), ("c_off", c_off, 0, 2 ** 31 - 1),
+                            ("first", first, 0, 2 ** 31 - 1), ("step", step, 1, 2 ** 31 - 1)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise RuntimeError("%s: %s must be an int in %d..%d, got %r" % (name, what, lo, hi, v))
+    if cutout not in (False, True, 0, 1):
+        raise RuntimeError("%s: cutout must be a bool, got %r" % (name, cutout))
+    if (not isinstance(fill, (tuple, list)) or len(fill) != 3
+            or any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255 for v in fill)):
+        raise RuntimeError("%s: fill must be three ints in 0..255 (the frames' channel order), got %r" % (name, fill))
+    if (not torch.is_tensor(geom) or geom.dtype != torch.int32 or not geom.is_contiguous() or geom.dim() not in (2, 3) or geom.shape[-1] != 5
+            or (geom.dim() == 3 and int(geom.shape[0]) != n) or geom.numel() != n * F * 5):
+        raise RuntimeError("%s: geom must be contiguous int32 [n * F = %d, 5] or [n = %d, F = %d, 5] (ops.final_label_map's table)"
+                           % (name, n * F, n, F))
+    Fc = len(range(first, F, step))
+    chips = c_off + Fc
+    if chips * Sh * Sw * 3 >= 2 ** 31 - 1:
+        raise RuntimeError("%s: (c_off + frames taken) * Sh * Sw * 3 must stay below 2^31 - 1, got %d chips of %d x %d" % (name, chips, Sh, Sw))
+    if out is None:
+        out = torch.empty((n, chips, Sh, Sw, 3), dtype=torch.uint8, device=device)
+    if (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 5 or tuple(out.shape[2:]) != (Sh, Sw, 3) or out.shape[0] < n
+            or out.shape[1] < chips or tuple(out.stride()[1:]) != (Sh * Sw * 3, Sw * 3, 3, 1)
+            or (out.shape[0] > 1 and out.stride(0) < out.shape[1] * Sh * Sw * 3)):
+        raise RuntimeError("%s: out must be uint8 [>= n = %d, >= c_off + frames taken = %d, Sh = %d, Sw = %d, 3], each row contiguous and the "
+                           "rows apart" % (name, n, chips, Sh, Sw))
+    if rects is None:
+        rects = torch.empty((n, chips, 4), dtype=torch.int32, device=device)
+    if (not torch.is_tensor(rects) or rects.dtype != torch.int32 or rects.dim() != 3 or int(rects.shape[2]) != 4 or rects.shape[0] < n
+            or rects.shape[1] < chips or tuple(rects.stride()[1:]) != (4, 1) or (rects.shape[0] > 1 and rects.stride(0) < rects.shape[1] * 4)):
+        raise RuntimeError("%s: rects must be int32 [>= n = %d, >= c_off + frames taken = %d, 4], each row contiguous and the rows apart"
+                           % (name, n, chips))
+    for t, what in ((labels, "labels"), (geom, "geom"), (out, "out"), (rects, "rects")):
+        if not t.is_cuda or t.device != torch.device(device):
+            raise RuntimeError("%s: %s must be a CUDA tensor on the frames' device, got %s" % (name, what, t.device))
+    return F, Ho, Wo, Sh, Sw, Fc, fill[0] | fill[1] << 8 | fill[2] << 16, out, rects
+
+
+def _row_stride(t, row_elems):
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1]) * row_elems
+
+
+def track_crops(labels, frames, geom, n, size, out=None, c_off=0, rects=None, first=0, step=1, pad256=0, min_area=0, cutout=False,
+                fill=(0, 0, 0)):
+    """One fixed-size picture per track and frame, cut and resized on the device: for rows k = 0..n-1 (label k + 1) and the window
+    frames f = first, first + step, ... < F, the t-th of them into out[k, c_off + t] (uint8 [>= n, >= c_off + frames taken, Sh, Sw, 3],
+    CUDA, pixel-interleaved, rows any stride apart; None: allocated, [n, c_off + taken, Sh, Sw, 3]) and its source rect (X0, Y0, X1, Y1),
+    inclusive, in output pixels into rects[k, c_off + t] (int32 [>= n, >= c_off + taken, 4]; None: allocated).  labels: uint8 [F, Ho, Wo]
+    (ops.final_label_map's output), frames: [F, 3, h0, w0] uint8 or float32 (ops.render_overlay's: a view into a larger store works),
+    geom: int32 [n * F, 5] or [n, F, 5], the table ops.final_label_map writes.  A row's box grows by pad256/256 of its size per side,
+    clamped to the picture; chip pixel (i, j) is the rounded mean of the source pixels of its footprint in that rect (a smaller rect is
+    replicated) -- with `cutout` of those the track owns, `fill` where it owns none.  A row that is not live (area < max(1, min_area),
+    or no box) gives a chip of `fill` and the rect (0, 0, -1, -1): the integer rule of include/mdqe_hip.h, mdqe_track_crops_u8.  One
+    launch on the current stream, none when n == 0 or no frame is taken.  -> (out, rects)."""
+    if (not torch.is_tensor(frames) or frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4 or int(frames.shape[1]) != 3
+            or frames.shape[2] < 1 or frames.shape[3] < 1):
+        raise RuntimeError("track_crops: frames must be uint8 or float32 [F, 3, h0, w0]")
+    h0, w0 = int(frames.shape[2]), int(frames.shape[3])
+    stride = int(frames.stride(0)) if frames.shape[0] > 1 else 3 * h0 * w0
+    if tuple(frames.stride()[1:]) != (h0 * w0, w0, 1) or stride < 3 * h0 * w0:
+        raise RuntimeError("track_crops: every frame must be contiguous and the frames a stride >= 3*h0*w0 apart, got strides %s"
+                           % (tuple(frames.stride()),))
+    F, Ho, Wo, Sh, Sw, Fc, packed, out, rects = _crop_args("track_crops", labels, int(frames.shape[0]), frames.device, geom, n, size, out,
+                                                           c_off, rects, first, step, pad256, min_area, cutout, fill)
+    if h0 * Ho >= 2 ** 31 - 1 or w0 * Wo >= 2 ** 31 - 1:
+        raise RuntimeError("track_crops: h0*Ho and w0*Wo must stay below 2^31 - 1")
+    with torch.cuda.device(frames.device):
+        check(lib.mdqe_track_crops_u8(ptr(frames), int(frames.dtype == torch.uint8), stride, h0, w0, ptr(labels), F, Ho, Wo, ptr(geom), n,
+                                      first, step, Sh, Sw, pad256, min_area, int(cutout), packed, ptr(out), _row_stride(out, Sh * Sw * 3),
+                                      c_off, ptr(rects), _row_stride(rects, 4), cur_stream(frames.device)), "track_crops")
+    return out, rects
+
+
+def track_crops_yuv(labels, yuv, geom, n, size, out=None, c_off=0, rects=None, first=0, step=1, pad256=0, min_area=0, cutout=False,
+                    fill=(0, 0, 0)):
+    """`track_crops` from decoder surfaces: yuv is a preprocess.YuvFrames of F surfaces on a HIP device (NV12 or P010); a source pixel is
+    the RGB -- in the surfaces' `order` -- that preprocess.yuv_to_rgb gives for that sample, so the chips equal
+    track_crops(labels, yuv_to_rgb(yuv), ...) bit for bit without the converted frames ever being stored: the integer rule of
+    include/mdqe_hip.h, mdqe_track_crops_yuv420sp.  -> (out, rects)."""
+    from .preprocess import YUV_FORMATS, YUV_MATRICES, YuvFrames, _pitch_stride
+    if not isinstance(yuv, YuvFrames):
+        raise RuntimeError("track_crops_yuv: yuv must be a preprocess.YuvFrames, got %s" % type(yuv).__name__)
+    if not yuv.is_cuda:
+        raise RuntimeError("track_crops_yuv: the surfaces must be on a HIP device, got %s (the crops have no host path)" % (yuv.device,))
+    F, Ho, Wo, Sh, Sw, Fc, packed, out, rects = _crop_args("track_crops_yuv", labels, len(yuv), yuv.device, geom, n, size, out, c_off, rects,
+                                                           first, step, pad256, min_area, cutout, fill)
+    H, W = yuv.height, yuv.width
+    if H * Ho >= 2 ** 31 - 1 or W * Wo >= 2 ** 31 - 1:
+        raise RuntimeError("track_crops_yuv: H*Ho and W*Wo must stay below 2^31 - 1")
+    (yp, ys), (cp, cs) = _pitch_stride(yuv.y), _pitch_stride(yuv.uv)
+    with torch.cuda.device(yuv.device):
+        check(lib.mdqe_track_crops_yuv420sp(ptr(yuv.y), yp, ys, ptr(yuv.uv), cp, cs, H, W, YUV_FORMATS.index(yuv.fmt),
+                                            YUV_MATRICES.index(yuv.matrix), int(yuv.full_range), int(yuv.order == "bgr"), ptr(labels), F, Ho,
+                                            Wo, ptr(geom), n, first, step, Sh, Sw, pad256, min_area, int(cutout), packed, ptr(out),
+                                            _row_stride(out, Sh * Sw * 3), c_off, ptr(rects), _row_stride(rects, 4),
+                                            cur_stream(yuv.device)), "track_crops_yuv")
+    return out, rects
+
+
 def _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action=None, cell=None):
     """The surface painters' rule of include/mdqe_hip.h on host planes, in torch integers.  action None: the plain painter, which is the
     table [0, 1, 1, ...] (no label has action 2, so no cell mean is taken) and may paint in place.  -> out."""

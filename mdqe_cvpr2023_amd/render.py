@@ -2,7 +2,8 @@
 ops.render_overlay (csrc/render.hip) behind the label map; merge.overlay_frames puts the two together for a tracker window.  A style
 with a mosaic (redaction) is painted by ops.render_mosaic (csrc/render_mosaic.hip) from the style's per-label action table.  A style
 with a box or a caption has ops.annotate (csrc/annotate.hip) draw them onto the painted picture, from the label map's geometry table,
-the font, the ink colours and the window's caption table made here.
+the font, the ink colours and the window's caption table made here.  `Crops` is the request for the other picture made from the same
+trio of frames, label map and geometry table: one fixed-size chip per track and frame (ops.track_crops, csrc/crops.hip).
 
 A track's colour depends only on its tracker row (label = row + 1), so it keeps its colour across windows and pushes."""
 import dataclasses
@@ -354,3 +355,59 @@ class Style:
             if cache[key].is_cuda:
                 torch.cuda.current_stream(cache[key].device).synchronize()
         return cache[key]
+
+
+@dataclasses.dataclass(frozen=True)
+class Crops:
+    """Per-track crops as a video output (model.crop_output, online_video(crops=...)): one fixed-size picture per track and frame, cut
+    from the frames handed in and resized on the device (ops.track_crops, csrc/crops.hip) from the label map's visible regions.
+    size: (height, width) of a chip, each 1..512; pad: how far the box grows per side, as a fraction 0..1 of its width / height (the
+    kernel uses pad256 = rint(pad * 256), clamped to the picture); cutout: only the pixels the track owns count, the rest of a chip is
+    `fill`; fill: three ints 0..255 in the frames' channel order -- the colour of a chip without a box and of what a cutout leaves
+    out; min_area: visible regions of fewer pixels give a chip of `fill`; every >= 1: the video frames f with f % every == 0 are taken
+    (the buffers shrink by that factor)."""
+    size: tuple = (128, 64)
+    pad: float = 0.0
+    cutout: bool = False
+    fill: tuple = (0, 0, 0)
+    min_area: int = 0
+    every: int = 1
+
+    def __post_init__(self):
+        def ints(v, k, lo, hi):
+            try:
+                t = tuple(v) if not isinstance(v, (str, bytes)) else None
+            except TypeError:
+                t = None
+            return t if t is not None and len(t) == k and all(not isinstance(x, bool) and isinstance(x, int) and lo <= x <= hi for x in t) else None
+        size, fill = ints(self.size, 2, 1, 512), ints(self.fill, 3, 0, 255)
+        if size is None:
+            raise ValueError("crops: size must be (height, width), ints in 1..512, got %r" % (self.size,))
+        if fill is None:
+            raise ValueError("crops: fill must be three ints in 0..255 (the frames' channel order), got %r" % (self.fill,))
+        if isinstance(self.pad, bool) or not isinstance(self.pad, (int, float)) or not 0.0 <= self.pad <= 1.0:
+            raise ValueError("crops: pad must be a number in 0..1 (a fraction of the box per side), got %r" % (self.pad,))
+        if not isinstance(self.cutout, bool):
+            raise ValueError("crops: cutout must be a bool, got %r" % (self.cutout,))
+        if isinstance(self.min_area, bool) or not isinstance(self.min_area, int) or not 0 <= self.min_area < 2 ** 31:
+            raise ValueError("crops: min_area must be an int in 0..2^31 - 1, got %r" % (self.min_area,))
+        if isinstance(self.every, bool) or not isinstance(self.every, int) or self.every < 1:
+            raise ValueError("crops: every must be an int >= 1, got %r" % (self.every,))
+        object.__setattr__(self, "size", size)
+        object.__setattr__(self, "fill", fill)
+
+    @property
+    def pad256(self):
+        return int(round(self.pad * 256))
+
+    def first_in(self, f0):
+        """The first frame taken of a window (or a store piece) that starts at video frame f0, relative to it."""
+        return (-int(f0)) % self.every
+
+    def taken(self, f0, f1):
+        """The video frames taken among [f0, f1)."""
+        return list(range(int(f0) + self.first_in(f0), int(f1), self.every))
+
+    def count(self, n_frames):
+        """Lc = ceil(n_frames / every): the frames taken of a whole video."""
+        return -(-int(n_frames) // self.every)
