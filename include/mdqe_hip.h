@@ -722,6 +722,55 @@ int mdqe_track_crops_yuv420sp(const void* y, long y_pitch, long y_stride, const 
                               int f_first, int f_step, int Sh, int Sw, int pad256, int min_area, int cutout, int fill,
                               unsigned char* out, long out_row_stride, int c_off, int* rects, long rect_row_stride, void* stream);
 
+/* Track paths (csrc/paths.hip): where each track has been.  A third consumer of the label map, beside the annotation pass and the crops:
+ * the centroid of every label's visible region per frame, and the trail of those centroids over the last frames painted onto a picture.
+ * A centroid does not jump when an occluder cuts a mask the way a box centre does.  labels: uint8 [F, Ho, Wo] as mdqe_final_label_map_u8
+ * writes it, row k's label is k + 1.  Integers only, ONE definition, for row k and frame f:
+ *   moments  mom[k*F + f] = (m, SX, SY), int64: m the number of pixels with labels[f, Y, X] == k + 1, SX the sum of their X, SY of their Y
+ *            (labels above n are not counted anywhere);
+ *   present  m >= max(1, min_area);
+ *   point    of a present row (cx, cy) = ((SX + m/2) / m, (SY + m/2) / m), integer divisions (the rounding of the crops and the mosaic);
+ *            of any other row (-1, -1).  With pts != NULL it goes to pts[k*pts_row_stride + 2*(p_off + f) + {0, 1}] (int32, the stride in
+ *            elements): a point table whose columns are frames, which a caller keeps over several windows.
+ * mom and the written pts columns are fully overwritten on every call and need no pre-initialisation; nothing else is written.  Three
+ * launches at most (zero the table; a sweep that gathers runs of equal labels in registers and adds them in closed form to a 64-bit LDS
+ * table, then to the global one with 64-bit atomic adds; the division -- left out with pts == NULL): integer sums do not depend on their
+ * order, identical from run to run.  Never allocates, never synchronises.
+ * MDQE_EINVAL, before any pointer is looked at, for n outside 0..255, min_area < 0, F < 0, Ho or Wo <= 0 or > 16384, F*Ho*Wo >= 2^31 - 1,
+ * p_off < 0, pts_row_stride < 2*(p_off + F) with n > 1 (two writers otherwise).  n == 0 or F == 0 return OK and launch nothing; NULL
+ * labels or mom give MDQE_ENULL.  Nothing needs to be aligned.
+ *
+ * Trails: an ANNOTATION PASS like mdqe_annotate_u8 -- in place on a painted picture, behind any painter, on the same stream; pic and the
+ * surface planes are that entry's (frame f of the call is picture f_off + f).  pts: the point table above; palette: uint8 [256, 3]
+ * (surfaces: uint16 [256, 3], rows (Y, U, V) in sample units).  For frame f and label l = k + 1, with Wo = W, Ho = H for surfaces:
+ *   points   columns j = p_off + f - trail .. p_off + f of row k; a column j < 0 is absent, and so is a point with x < 0, y < 0, x >= Wo
+ *            or y >= Ho: the entries are memory-safe for every table content;
+ *   strokes  each present point P gives the degenerate segment (P, P); each pair of present points A, B with no present point in a
+ *            column between them the segment (A, B) -- gaps are bridged, an occluded track keeps one line;
+ *   hit      with d = B - A, p = (X, Y) - A, L2 = d.d, s = p.d: if L2 == 0 or s <= 0, pixel (X, Y) is hit when 4*(p.p) <= width*width;
+ *            if s >= L2 the same with p = (X, Y) - B; otherwise when 4*c*c <= width*width*L2, c = p.x*d.y - p.y*d.x.  64-bit integers
+ *            (coordinates below 2^14: 4*c*c < 2^61).  Round caps; a width-1 line has a pixel in every column (row, on steep lines);
+ *   pixel    takes palette[l] of the FIRST label in ascending l that hits it.  A pixel that nothing hits is NOT WRITTEN;
+ *   luma     the rule per sample with the Y component;
+ *   chroma   mdqe_annotate_yuv420sp's rule: a pair whose in-picture 2 x 2 block has no hit is not written (P010: it keeps all 16 bits of
+ *            both words); any other pair is Cout = (sum_i px_i + n / 2) >> log2(n) over the block's in-picture pixels, px_i the hit's
+ *            component for a hit pixel and the stored sample's VALUE otherwise, written as value << 6 for P010.
+ * One thread owns each sample and each chroma pair: in place by construction.  A block owns a tile and compacts the segments whose box,
+ * grown by `width`, meets it into LDS in label order, in chunks of 512 that keep that order; a tile without a segment returns without
+ * reading or writing a pixel.  One launch, no atomics: identical from run to run.  Never allocates, never synchronises.
+ * MDQE_EINVAL, before any pointer is looked at, for trail outside 1..64, width outside 1..5, n outside 0..255, F < 0, f_off < 0,
+ * p_off < 0, Ho, Wo, H or W <= 0 or > 16384, F*Ho*Wo >= 2^31 - 1, pts_row_stride < 2*(p_off + F) with n > 1, and for the surface entry
+ * every plane refusal of mdqe_annotate_yuv420sp.  F == 0 and n == 0 return OK and launch nothing; NULL pointers give MDQE_ENULL. */
+int mdqe_label_centroids_u8(const unsigned char* labels, int F, int Ho, int Wo, int n, int min_area, long long* mom /* int64 [n*F, 3] */,
+                            int* pts /* int32 or NULL */, long pts_row_stride, int p_off, void* stream);
+int mdqe_render_trails_u8(unsigned char* pic /* [.., Ho, Wo, 3] */, int F, int Ho, int Wo, int f_off,
+                          const int* pts, long pts_row_stride, int p_off, int n, int trail, int width,
+                          const unsigned char* palette /*[256,3]*/, void* stream);
+int mdqe_render_trails_yuv420sp(void* y, long y_pitch, long y_stride, void* uv, long uv_pitch, long uv_stride,
+                                int F, int H, int W, int fmt /*0 nv12, 1 p010*/, int f_off,
+                                const int* pts, long pts_row_stride, int p_off, int n, int trail, int width,
+                                const unsigned short* palette_yuv, void* stream);
+
 /* ---- COCO single-image branch, after the decoder (MDQE.inference_image, mdqe/mdqe.py:486-556), on the centre frame's
  * low-resolution logits [n,Hm,Wm]; aligned_bilinear x`factor` in closed form, crop [:h,:w].
  * stats[k] = {sum(sigmoid*[sigmoid>0.5]), count(sigmoid>0.5), xmin, ymin, xmax, ymax of (logit > 0)} (:512-516, :526;

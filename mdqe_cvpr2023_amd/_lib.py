@@ -60,6 +60,9 @@ SIGNATURES = {
     "mdqe_annotate_yuv420sp": [p, l, l, p, l, l, i, i, i, i, i, p, i, p, p, p, i, p, i, i, i, p],
     "mdqe_track_crops_u8": [p, i, l, i, i, p, i, i, i, p, i, i, i, i, i, i, i, i, i, p, l, i, p, l, p],
     "mdqe_track_crops_yuv420sp": [p, l, l, p, l, l, i, i, i, i, i, i, p, i, i, i, p, i, i, i, i, i, i, i, i, i, p, l, i, p, l, p],
+    "mdqe_label_centroids_u8": [p, i, i, i, i, i, p, p, l, i, p],
+    "mdqe_render_trails_u8": [p, i, i, i, i, p, l, i, i, i, i, p, p],
+    "mdqe_render_trails_yuv420sp": [p, l, l, p, l, l, i, i, i, i, i, p, l, i, i, i, i, p, p],
     "mdqe_final_masks_overlap": [p, i, p, i, i, i, i, i, i, i, i, p, i, i, p, l, p, p],
     "mdqe_set_gemm_precision": [i],
     "mdqe_set_gemm_precision_thread": [i],

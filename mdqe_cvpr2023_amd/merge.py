@@ -4,7 +4,8 @@ Which forms a video produces is resolved ONCE, into a `Forms` record (from the m
 planes (dense or run boundaries), the label map (one uint8 plane per frame that names the track owning each pixel; its frames are
 disjoint between windows, so it needs no `stitch`), its overlay (that map painted over the frames the caller handed in, `FrameStore`,
 uint8 [F, Ho, Wo, 3]), per-track crops cut from those frames along the map's visible regions (`crop_frames`, render.Crops; offline they
-gather in one device table per video, `CropTable`) and whose geometry.  A flushed window becomes those forms in ONE function,
+gather in one device table per video, `CropTable`), the tracks' paths (the centroid of each visible region per frame, kept over the
+windows in a `PathTable`: an output, and what an overlay's trails are drawn from) and whose geometry.  A flushed window becomes those forms in ONE function,
 `build_window`; the three paths differ in the destination only: per window into per-video pinned memory (`_early_masks`), per window
 as a record (`_online_window`), or all windows into whole-video device buffers with one copy at the end (`video_result`).  Shared
 beside it: `to_host` (the hop on the copy stream), `rle.positions_to_rles`, `stitch`, `result_head` / `track_geometry` (a result's keys).
@@ -31,12 +32,14 @@ class Forms:
     early_always: bool = False            # model.rle_output: the early path even with model.early_masks off, with or without planes
     surface: bool = False                 # the overlay is painted onto the decoder surfaces handed in: a YuvFrames, not RGB pixels
     crops: bool = False                   # per-track chips cut from the frames (render.Crops; the map and its table: a device scratch if not returned)
+    paths: bool = False                   # per-track centroids and moments of the map's visible regions (PathTable; the map: a device scratch if not returned)
 
     @classmethod
-    def _of(cls, model, geometry, planes, labels, overlay, early_always=False, surface=False, crops=False):
+    def _of(cls, model, geometry, planes, labels, overlay, early_always=False, surface=False, crops=False, paths=False):
         """geometry None: the model's flag.  It describes the planes where there are planes, and the labels' regions where the map is returned."""
         g = bool(getattr(model, "geometry_output", False) if geometry is None else geometry)
-        return cls(planes, labels, overlay, g and planes is not None, g and labels, early_always, bool(overlay and surface), bool(crops))
+        return cls(planes, labels, overlay, g and planes is not None, g and labels, early_always, bool(overlay and surface), bool(crops),
+                   bool(paths))
 
     @classmethod
     def of_model(cls, model, emit_masks=True, geometry=None):
@@ -46,14 +49,15 @@ class Forms:
         lab, rle = getattr(model, "label_output", False), bool(getattr(model, "rle_output", False))
         pic = getattr(model, "overlay_output", False)
         return cls._of(model, geometry, None if lab == "only" else "rle" if rle else "dense", bool(lab), bool(pic), rle, pic == "surface",
-                       getattr(model, "crop_output", None) is not None)
+                       getattr(model, "crop_output", None) is not None, bool(getattr(model, "path_output", False)))
 
     @classmethod
-    def of_emit(cls, emit, geometry=False, model=None, surface=False, crops=False):
-        """Online ("masks" | "rle" | "labels" | "overlay"; surface: the overlay onto the surfaces pushed; crops: chips beside it)."""
+    def of_emit(cls, emit, geometry=False, model=None, surface=False, crops=False, paths=False):
+        """Online ("masks" | "rle" | "labels" | "overlay"; surface: the overlay onto the surfaces pushed; crops: chips beside it; paths:
+        centroids and moments beside it)."""
         lab = emit in ("labels", "overlay")
         return cls._of(model, geometry, None if lab else {"masks": "dense", "rle": "rle"}[emit], lab, emit == "overlay", surface=surface,
-                       crops=crops)
+                       crops=crops, paths=paths)
 
 
 def dense_masks(m, idx, stride, frame_hw, out_size, geometry, out, f_off):
@@ -215,7 +219,7 @@ class FrameStore:
         return out
 
 
-def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, source, f0, style, cls, out, o_off):
+def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, source, f0, style, cls, out, o_off, paths=None):
     """A window's overlay: the label map of window logits m [n, F, Hm, Wm] into labels[l_off:l_off + F] (`label_maps`: all n rows
     compete, as in every label path), then that map painted over video frames [f0, f0 + F) of `source` (a FrameStore) into
     out[o_off:o_off + F] (uint8 [>= o_off + F, Ho, Wo, 3], device) in `style` (render.Style) -- one ops.render_overlay launch per
@@ -226,11 +230,16 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
     on the host, is what a style with `classes` builds that table from.  A style that annotates (style.annotates: track boxes,
     captions) takes the geometry table from `label_maps` whether or not `geometry` asks for it and, behind the painter launches, runs
     one ops.annotate / ops.annotate_yuv launch per piece in place on the painted frames, on the same stream, with the captions made
-    from `cls`; nothing is read back.  -> `label_maps`' geometry table where `geometry` asks for it, else None."""
+    from `cls`; nothing is read back.  `paths` (a PathTable whose `begin` has been called for this window): the window's centroids are
+    made behind the label map (`PathTable.run`), and a style with a trail (style.trails) has one ops.render_trails /
+    ops.render_trails_yuv launch per piece draw them between the painter and the annotations, so plates stay legible.
+    -> `label_maps`' geometry table where `geometry` asks for it, else None."""
     from . import ops
     notes = style.annotates and int(m.shape[0]) > 0
     geom = label_maps(m, stride, frame_hw, out_size, geometry or notes, labels, l_off)
     n, nf = int(m.shape[0]), int(m.shape[1])
+    if paths is not None:
+        paths.run(labels, l_off)
     surface = not torch.is_tensor(out)
     pal = style.palette_yuv_on(m.device, *out.meta()[2:]) if surface else style.palette_on(m.device)
     act = style.actions_on(m.device, cls) if style.mosaic is not None else None
@@ -246,6 +255,13 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
             ops.render_overlay_yuv(lab, t, pal, out, o_off + d, style.a256, style.contour)
         else:
             ops.render_overlay(lab, t, pal, out, o_off + d, style.a256, style.contour)
+    if style.trails and n:
+        if paths is None or paths.trail != style.trail:
+            raise RuntimeError("overlay: a style with trail=%d needs the video's PathTable of that trail (merge.path_table)" % style.trail)
+        for t, first in pieces:                                       # (a piece's frame f is column trail + d + f of the table)
+            k, d = len(t), first - int(f0)
+            (ops.render_trails_yuv if surface else ops.render_trails)(out, paths.pts, n, pal, k, o_off + d, paths.trail + d, style.trail,
+                                                                      style.trail_width)
     if notes:
         ink = style.ink_yuv_on(m.device, *out.meta()[2:]) if surface else style.ink_on(m.device)
         text, font = style.captions_on(m.device, cls, n), style.font_on(m.device)
@@ -320,6 +336,86 @@ class CropTable:
         return {"pred_crops": host[0], "pred_crop_rects": host[1], "pred_crop_frames": self.spec.taken(0, self.n_frames)}
 
 
+class PathTable:
+    """Where each tracker row has been: the history a trail is drawn from and the `paths` output.  On the device `pts` int32 [255,
+    trail + Fmax, 2], (-1, -1) = absent: columns [0, trail) hold the `trail` frames before the current window, columns [trail, trail +
+    F) the window's centroids (ops.label_centroids with p_off = trail; `mom`: the window's moments int64 [n, F, 3]).  A label is a
+    tracker row + 1 and rows are stable across windows, so a row of the table is one track's path.  Per window `begin` moves the last
+    `trail` columns to the front (through a copy of them: source and destination overlap) and blanks the window's columns of the rows
+    the window does not hold -- a track that appears later starts without a past -- and `run`, behind the label map, fills in the
+    centroids.  The history is bounded by `trail`: the table does not grow with the video.  keep=True (the offline paths): each
+    window's centroids and moments wait on the device, 32 bytes per track and frame, for one read-back at the end (`result`)."""
+    ROWS = 255
+
+    def __init__(self, trail, min_area, device, keep=False):
+        self.trail, self.min_area, self.device = int(trail), int(min_area), device
+        self.pts = self.mom = self.cen = None
+        self.n = self.nf = 0
+        self.windows = [] if keep else None                            # (f_off, frames, rows, centroids [n, F, 2], moments [n, F, 3]) on the device
+
+    def begin(self, n, nf):
+        """The table made ready for a window of n rows and nf frames, on the current stream.  -> (the window's centroids int32 [n, nf, 2]
+        -- a copy of the table's columns of its own, since the next window moves those while this one may still be on its way to the
+        host -- and its moments int64 [n, nf, 3]): what `run` fills in."""
+        T, held = self.trail, self.nf
+        if self.pts is None or self.pts.shape[1] < T + nf:
+            new = torch.full((self.ROWS, T + max(nf, 1), 2), -1, dtype=torch.int32, device=self.device)
+            if self.pts is not None and T:
+                new[:, :T] = self.pts[:, held:held + T]
+            self.pts = new
+        else:
+            if T and held:
+                self.pts[:, :T] = self.pts[:, held:held + T].clone()
+            if n < self.ROWS and nf:
+                self.pts[n:, T:T + nf] = -1
+        self.n, self.nf = int(n), int(nf)
+        self.mom = torch.empty((self.n, self.nf, 3), dtype=torch.int64, device=self.device)
+        self.cen = torch.empty((self.n, self.nf, 2), dtype=torch.int32, device=self.device)
+        return self.cen, self.mom
+
+    def run(self, labels, l_off):
+        """The centroids of the window `begin` announced, from its label map labels[l_off:l_off + nf], on the current stream."""
+        from . import ops
+        if self.n and self.nf:
+            ops.label_centroids(labels[l_off:l_off + self.nf], self.n, self.min_area, self.mom, self.pts, self.trail)
+            self.cen.copy_(self.pts[:self.n, self.trail:self.trail + self.nf])
+
+    def keep(self, f_off):
+        if self.windows is not None:
+            self.windows.append((int(f_off), self.nf, self.n, self.cen, self.mom))
+
+    def result(self, inst, n_frames):
+        """`path_result` of the windows kept, read back once."""
+        cur = torch.cuda.current_stream(self.device)
+        for _, _, _, p, q in self.windows:
+            p.record_stream(cur)
+            q.record_stream(cur)
+        return path_result(inst, n_frames, [(f, nf, n, p.cpu(), q.cpu()) for f, nf, n, p, q in self.windows])
+
+
+def path_table(forms, style, device, keep=False):
+    """The PathTable of a video with `forms` and overlay style `style`, or None where neither a trail is drawn nor paths are asked
+    for.  An overlay's table has the style's trail and min_area (the one its boxes and captions use); without an overlay: 0 and 0."""
+    drawn = forms.overlay and style is not None
+    trail = style.trail if drawn else 0
+    if not forms.paths and not trail:
+        return None
+    return PathTable(trail, style.min_area if drawn else 0, device, keep)
+
+
+def path_result(rows, n_frames, windows):
+    """{"pred_centroids": int32 [n_out, L, 2], "pred_moments": int64 [n_out, L, 3]}: per output j the path of tracker row rows[j] from
+    the windows' tables (`windows`: (f_off, frames, rows the window holds, centroids [n, F, 2], moments [n, F, 3]) on the host); the
+    frames before a row's first window are absent, (-1, -1) with moments 0 (`stitch`'s rule)."""
+    L = int(n_frames)
+    out = {}
+    for key, at, fill, dtype in (("pred_centroids", 3, -1, torch.int32), ("pred_moments", 4, 0, torch.int64)):
+        wins = [(w[0], w[1], w[2], w[at]) for w in windows]
+        parts = stitch(list(rows), L, wins, lambda k, width=at - 1, v=fill, dt=dtype: torch.full((k, width), v, dtype=dt), torch.cat)
+        out[key] = torch.stack(parts) if parts else torch.zeros((0, L, at - 1), dtype=dtype)
+    return out
+
+
 def surface_kind(source, out_size):
     """What a surface overlay paints on: the kind (YuvFrames.meta()) of the surfaces `source` (a FrameStore) holds, which must be of the
     output size (None: not looked at) -- the painting kernel does not resample.  Raises the two refusals of the form."""
@@ -361,7 +457,7 @@ def rle_positions(m, idx, stride, frame_hw, out_size, geometry):
 
 
 def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels=None, picture=None, paint=None,
-                 hop=lambda stage, geom: geom, crops=None):
+                 hop=lambda stage, geom: geom, crops=None, paths=None):
     """What `forms` asks for of ONE flushed window (logits m [n, F, Hm, Wm]), on the current stream, for every path; the only caller
     of `overlay_frames`, `label_maps`, `dense_masks` and `rle_positions`.  First the label map of ALL n rows into labels = (device
     buffer, frame offset) and, with picture = (buffer, offset), its overlay, painted from paint = (FrameStore, first video frame,
@@ -370,15 +466,21 @@ def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels
     "crops" | "planes") that filled device buffers: the early and the online path send them to the host there, the map under the planes' kernel.
     crops = (render.Crops, FrameStore, first video frame, chips buffer, rects buffer, chip offset): behind the labels stage the window's
     chips (`crop_frames`) from the map and its table, which are then made whether or not `forms` returns them.
+    paths (a PathTable, `begin` called for this window): behind the label map the window's centroids (`PathTable.run`), which the
+    overlay's trail pass draws and, with forms.paths, the stage "paths" sends on; the map is then made whether or not it is returned.
     -> (labels' geometry table [n, F, 5] or None, planes' table [len(rows), F, 5] or None, (pos, n_pos) of `rle_positions` or None)."""
     lgeom = pgeom = runs = None
     if labels is not None:
         table = forms.label_geometry or crops is not None
         if picture is not None:
-            dgeom = overlay_frames(m, stride, frame_hw, out_size, table, *labels, *paint, *picture)
+            dgeom = overlay_frames(m, stride, frame_hw, out_size, table, *labels, *paint, *picture, paths=paths)
         else:
             dgeom = label_maps(m, stride, frame_hw, out_size, table, *labels)
+            if paths is not None:
+                paths.run(*labels)
         lgeom = hop("labels", dgeom if forms.label_geometry else None)
+        if paths is not None and forms.paths:
+            hop("paths", None)
         if crops is not None:
             spec, source, f0, chips, rects, c_off = crops
             crop_frames(int(m.shape[0]), int(m.shape[1]), *labels, dgeom, source, f0, spec, chips, rects, c_off)
@@ -490,7 +592,7 @@ def result_head(model, cls_clips, out_size, n_frames, score=None, track_ids=True
 
 
 def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, early=None, emit_masks=True, frame_source=None, score=None,
-                 forms=None, crops=None):
+                 forms=None, crops=None, paths=None):
     """mdqe/mdqe.py:430-471.  The x4 aligned-bilinear up-sampling, sigmoid, crop (:357-358), nearest resize to the original size and
     the 0.5 threshold (:458-462) run as ONE kernel per window; windows in which an instance did not exist yet stay zero (:442).
     `forms`: the merger's record (ClipMerger.finish); None: resolved from the model here.  `early` (EarlyMasks): every form is on the
@@ -500,7 +602,9 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
     "pred_label_map": uint8 [L, Ho, Wo], host; label t + 1 = tracker row t, 0 = background, so pred_label_map == pred_track_ids[j] + 1
     is output j's exclusive region.  "pred_overlay": uint8 [L, Ho, Wo, 3], pinned host; with forms.surface a YuvFrames of
     L painted surfaces (pinned host, tight pitch).  `crops` (CropTable): the early path's table, filled at every flush; without it and
-    with forms.crops the table is filled here, window by window -> "pred_crops", "pred_crop_rects", "pred_crop_frames"."""
+    with forms.crops the table is filled here, window by window -> "pred_crops", "pred_crop_rects", "pred_crop_frames".  `paths`
+    (PathTable): the early path's table with every window's centroids kept; without it and with forms.paths, or with a style that
+    draws trails, the table is made and filled here -> "pred_centroids" int32 [n_out, L, 2], "pred_moments" int64 [n_out, L, 3]."""
     if forms is None:
         forms = Forms.of_model(model, emit_masks)
         forms = dataclasses.replace(forms, overlay=forms.overlay and frame_source is not None, crops=forms.crops and frame_source is not None)
@@ -523,9 +627,10 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
         rows = [sel.index(i) for i in inst]                        # rows of the planes' buffer = positions in sel
         plane_geoms, label_geoms, u8 = [], [], dict(dtype=torch.uint8, device=model.device)
         # (the windows tile [0, n_frames): every row of the map and the picture is written; a track's planes start at its first window)
-        d_lab = torch.empty(n_frames, Ho, Wo, **u8) if forms.labels or forms.overlay or forms.crops else None
+        d_lab = torch.empty(n_frames, Ho, Wo, **u8) if forms.labels or forms.overlay or forms.crops or forms.paths else None
         if forms.crops:
             crops = CropTable(model.crop_output, n_frames, model.device)
+        paths = path_table(forms, model.overlay_style if forms.overlay else None, model.device, keep=forms.paths)
         d_pic = torch.empty(n_frames, Ho, Wo, 3, **u8) if forms.overlay and not forms.surface else None
         if forms.surface:
             d_pic = surface_picture(frame_source, n_frames, out_size, model.device)
@@ -535,9 +640,14 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
             n, nf = int(m.shape[0]), int(m.shape[1])
             cnt = sum(1 for i in sel if i < n)                     # sel is ascending: these are its first `cnt` entries
             at = [None if t is None else (t, f_off) for t in (d_planes, d_lab, d_pic)]
+            if paths is not None:
+                paths.begin(n, nf)
             lg, pg, _ = build_window(m, forms, sel_dev[:cnt] if forms.planes else None, model.cfg.match_stride, frame_hw, out_size, *at,
                                      paint=(frame_source, f_off, model.overlay_style, cls_clips[i]) if forms.overlay else None,
-                                     crops=(crops.spec, frame_source, f_off, *crops.rows(n), crops.spec.count(f_off)) if forms.crops else None)
+                                     crops=(crops.spec, frame_source, f_off, *crops.rows(n), crops.spec.count(f_off)) if forms.crops else None,
+                                     paths=paths)
+            if paths is not None:
+                paths.keep(f_off)
             label_geoms.append((f_off, nf, n, lg))
             if cnt:
                 plane_geoms.append((f_off, nf, cnt, pg))
@@ -561,10 +671,12 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
                 planes_res = {"pred_rles": [enc[p] for p in rows]}
             else:
                 planes_res = {"pred_masks": [planes[p] for p in rows]}
-    if forms.labels or forms.overlay or forms.crops:
+    if forms.labels or forms.overlay or forms.crops or forms.paths:
         res.setdefault("pred_track_ids", list(inst))
     if forms.crops:
         res.update(crops.result(inst))
+    if forms.paths:
+        res.update(paths.result(inst, n_frames))
     if forms.labels:
         res["pred_label_map"] = host["labels"][:n_frames]
     if forms.overlay:
@@ -586,7 +698,7 @@ class ClipMerger:
     EARLY_TRACKS = 48                       # tracks per video the early-mask path budgets pinned memory for
 
     def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True, online=None, geometry=None, frame_source=None,
-                 style=None, ground_truth=None, surface=False, surface_pitch_align=1, crops=None):
+                 style=None, ground_truth=None, surface=False, surface_pitch_align=1, crops=None, paths=False):
         self.model, self.frame_hw, self.out_size, self.mask_hw = model, frame_hw, out_size, mask_hw
         self.emit_masks = emit_masks                # False: scores / labels only (ranks > 0 of a sharded video)
         # online ("masks" | "rle" | "labels" | "overlay"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their
@@ -597,9 +709,11 @@ class ClipMerger:
         # (surface, surface_pitch_align: an online session's; offline the model's overlay_output == "surface", at a tight pitch)
         # crops (render.Crops): an online session's; offline the model's crop_output
         self.crop_spec = crops if online else (getattr(model, "crop_output", None) if emit_masks else None)
-        self.forms = forms = (Forms.of_emit(online, geometry, model, surface, self.crop_spec is not None) if online
+        # paths: an online session's; offline the model's path_output
+        self.forms = forms = (Forms.of_emit(online, geometry, model, surface, self.crop_spec is not None, bool(paths)) if online
                               else Forms.of_model(model, emit_masks, geometry))
         self.crop_table = None                      # the early path's CropTable, from its first window
+        self.path_table = None                      # the early and the online path's PathTable, from their first window
         self.surface_pitch_align = surface_pitch_align
         self.geometry = forms.plane_geometry or forms.label_geometry
         # False | True | "only" (model.label_output): the label map next to -- or, "only", instead of -- the per-track planes
@@ -718,17 +832,19 @@ class ClipMerger:
         """The early and the online path: the forms of ALL n rows of the window just flushed (m: [n, F, Hm, Wm] mean logits) into
         per-window device scratch (`build_window`), each stage sent to the host behind it (`to_host`): pairs(kind, buffer) -> its (pinned
         destination, source) pairs, kind = "labels" | "overlay" | "planes"; `event()` is recorded behind each hop; c: the window's class rows on the host (an
-        overlay's mosaic of classes).  -> build_window's."""
+        overlay's mosaic of classes).  The video's PathTable (`path_table`: for paths or a style with a trail) is made at the first
+        window and announced each window (`PathTable.begin`); online its window's centroids and moments are the stage "paths".
+        -> build_window's."""
         forms, u8 = self.forms, dict(dtype=torch.uint8, device=self.dev)
         n, nf, Ho, Wo = int(m.shape[0]), int(m.shape[1]), int(self.out_size[0]), int(self.out_size[1])
-        lab = torch.empty(nf, Ho, Wo, **u8) if forms.labels or forms.overlay or forms.crops else None    # (an overlay or crops alone: a scratch, not copied)
+        lab = torch.empty(nf, Ho, Wo, **u8) if forms.labels or forms.overlay or forms.crops or forms.paths else None    # (an overlay, crops or paths alone: a scratch, not copied)
         pic = torch.empty(nf, Ho, Wo, 3, **u8) if forms.overlay and not forms.surface else None
         if forms.surface:                           # (the host's pitch: the window copy is then two plain copies, padding and all)
             pic = surface_picture(self.frame_source, nf, self.out_size, self.dev, self.surface_pitch_align)
         rows = torch.arange(n, dtype=torch.int32, device=self.dev) if n and forms.planes else None
         planes = torch.empty(n, nf, Ho, Wo, **u8) if rows is not None and forms.planes == "dense" else None
         copies = {"labels": (pairs("labels", lab) if forms.labels else []) + (pairs("overlay", pic) if forms.overlay else []),
-                  "planes": pairs("planes", planes) if planes is not None else [], "crops": []}
+                  "planes": pairs("planes", planes) if planes is not None else [], "crops": [], "paths": []}
         crop = None
         if forms.crops:
             spec = self.crop_spec
@@ -744,12 +860,22 @@ class ClipMerger:
                 crop = (spec, self.frame_source, self.f_off, *self.crop_table.rows(n), spec.count(self.f_off))
         # (the copy stream is created BEFORE the window's kernels are launched, and only by a window that copies, as ever: the order
         # streams are first used in decides their queues)
-        cs = copy_stream(self.model) if copies["labels"] or copies["planes"] or copies["crops"] else None
+        sends_paths = bool(forms.paths and self.online and n)        # (offline the windows' tables wait on the device: PathTable.keep)
+        cs = copy_stream(self.model) if copies["labels"] or copies["planes"] or copies["crops"] or sends_paths else None
+        if self.path_table is None:
+            self.path_table = path_table(forms, self.style, self.dev, keep=forms.paths and not self.online)
+        if self.path_table is not None:
+            views = self.path_table.begin(n, nf)
+            if forms.paths and self.online:
+                copies["paths"] = pairs("centroids", views[0]) + pairs("moments", views[1])
         at = [None if t is None else (t, 0) for t in (planes, lab, pic)]
-        return build_window(m, forms, rows, self.model.cfg.match_stride, self.frame_hw, self.out_size, *at,
-                            paint=(self.frame_source, self.f_off, self.style, c), crops=crop,
-                            hop=lambda stage, geom: (to_host(cs, self.side, copies[stage], geom, event())
-                                                     if copies[stage] or geom is not None else None))   # (a scratch stage: nothing to send)
+        out = build_window(m, forms, rows, self.model.cfg.match_stride, self.frame_hw, self.out_size, *at,
+                           paint=(self.frame_source, self.f_off, self.style, c), crops=crop, paths=self.path_table,
+                           hop=lambda stage, geom: (to_host(cs, self.side, copies[stage], geom, event())
+                                                    if copies[stage] or geom is not None else None))   # (a scratch stage: nothing to send)
+        if self.path_table is not None:
+            self.path_table.keep(self.f_off)
+        return out
 
     def _early_masks(self, m, c=None):
         """Every form of EVERY instance tracked so far goes to pinned host memory while later windows compute; finish() then only
@@ -800,7 +926,7 @@ class ClipMerger:
             if not torch.is_tensor(buf):            # a surface picture: pinned surfaces of the same pitch, both planes
                 host = rec["overlay"] = surface_picture(self.frame_source, nf, out_size, "cpu", self.surface_pitch_align, pin_memory=True)
                 return [(host.y, buf.y), (host.uv, buf.uv)]
-            if kind in ("crops", "crop_rects"):     # (their shape changes with the tracks: not the mask pool's kind of buffer)
+            if kind in ("crops", "crop_rects", "centroids", "moments"):     # (their shape changes with the tracks: not the mask pool's kind of buffer)
                 rec[kind] = torch.empty(tuple(buf.shape), dtype=buf.dtype, pin_memory=bool(buf.numel()))
                 return [(rec[kind], buf)] if buf.numel() else []
             host = self.model.pinned_mask_buffer(tuple(buf.shape))
@@ -840,4 +966,5 @@ class ClipMerger:
                 m.record_stream(self.main)
         return self.model.inference_video(self.out_size, self.cls_clips, self.windows, self.frame_hw, self.f_off, early=self.early,
                                           emit_masks=self.emit_masks, frame_source=self.frame_source, score=self.score, forms=self.forms,
-                                          **({"crops": self.crop_table} if self.forms.crops else {}))
+                                          **({"crops": self.crop_table} if self.forms.crops else {}),
+                                          **({"paths": self.path_table} if self.forms.paths and self.path_table is not None else {}))

@@ -121,7 +121,10 @@ class MDQE(nn.Module):
         # A render.Crops: forward() on a video adds "pred_crops" / "pred_crop_rects" / "pred_crop_frames", one fixed-size picture per
         # output and taken frame, cut and resized on the device (ops.track_crops).  None: nothing changes.  (A property: see below.)
         self.crop_output = None
-        self.merge_on_cpu = None                   # None: cfg.merge_on_cpu (MODEL.MDQE.MERGE_ON_CPU); True / False override it
+        # True: forward() on a video adds "pred_centroids" / "pred_moments", where each output's track is in every frame, summed on the
+        # device from the label map (ops.label_centroids).  False: nothing changes.  (A property: see below.)
+        self.path_output = False
+        self.merge_on_cpu = None                  # None: cfg.merge_on_cpu (MODEL.MDQE.MERGE_ON_CPU); True / False override it
         # Final masks of a tracker window leave the device when the window is flushed (pinned host buffers, copied under the later
         # windows' compute) instead of in one pass + one 100-MB copy after the last window.  Independent of MERGE_ON_CPU, which in the
         # reference only picks the device the window results wait on (mdqe/mdqe.py:185-186,337,354-355) and never changes an output.
@@ -311,6 +314,23 @@ class MDQE(nn.Module):
         if value is not None:
             self.check_label_capacity()
         self.__dict__["_crop_output"] = value
+
+    @property
+    def path_output(self):
+        """False or True: forward() on a video adds "pred_centroids" (int32 [n_out, L, 2]: per output and frame the centroid (x, y) of
+        the track's visible region of the label map, ((SX + m/2) / m, (SY + m/2) / m) in integers, ops.label_centroids; (-1, -1) where
+        the track has no region, the frames before its first window included), "pred_moments" (int64 [n_out, L, 3]: that region's
+        pixels m and the sums SX, SY of their coordinates) and "pred_track_ids".  Beside every other output form, on either mask path;
+        the label map is then made whether or not it is returned.  Videos only, one device (sharding.py refuses it)."""
+        return self.__dict__.get("_path_output", False)
+
+    @path_output.setter
+    def path_output(self, value):
+        if not isinstance(value, bool):
+            raise ValueError("path_output must be False or True, got %r" % (value,))
+        if value:
+            self.check_label_capacity()
+        self.__dict__["_path_output"] = value
 
     @property
     def overlay_style(self):
@@ -1054,7 +1074,7 @@ class MDQE(nn.Module):
             yield guarded(step)
 
     def online_video(self, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None,
-                     surface=False, surface_pitch_align=1, crops=None):
+                     surface=False, surface_pitch_align=1, crops=None, paths=False):
         """An online session over ONE video whose frames arrive in pushes (a camera, a stream, a video too long to hold): push()
         returns each tracker window as soon as it is final, close() the rest, result() the video-level scores / labels / tracks.
         height / width: output mask size (default: the frame size); emit: "masks" (bool [n, F, H, W] per window), "rle" or "labels" (one
@@ -1066,10 +1086,12 @@ class MDQE(nn.Module):
         "ground_truth" (a push past its length raises); surface (with emit="overlay", pushes of preprocess.YuvFrames): `win.overlay` is
         a YuvFrames of painted surfaces of the pushed format instead of RGB pixels (surface_pitch_align: its row pitch in bytes is
         rounded up to a multiple of it); crops (render.Crops, beside any emit): every window carries `crops` / `crop_rects` /
-        `crop_frames`, one fixed-size picture per track and taken frame (`crop_output`'s).  See online.py."""
+        `crop_frames`, one fixed-size picture per track and taken frame (`crop_output`'s); paths (a bool, beside any emit): every
+        window carries `centroids` / `moments` of its tracks' visible regions and, with keep, result() "pred_centroids" /
+        "pred_moments" (`path_output`'s).  See online.py."""
         from .online import OnlineVideo
         return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep, geometry=geometry, style=style, ground_truth=ground_truth,
-                           surface=surface, surface_pitch_align=surface_pitch_align, crops=crops)
+                           surface=surface, surface_pitch_align=surface_pitch_align, crops=crops, paths=paths)
 
     def inference_image(self, batched_inputs):
         """COCO single-image branch: MDQE.forward :213-236 -> mdqe.forward (models/mdqe.py:62-70) -> decoder
@@ -1089,6 +1111,9 @@ class MDQE(nn.Module):
         if getattr(self, "crop_output", None) is not None:
             raise ValueError("crop_output: the COCO image branch has no crops (per-track crops are a video output: use a video config, or "
                              "set crop_output = None)")
+        if getattr(self, "path_output", False):
+            raise ValueError("path_output: the COCO image branch has no paths (track centroids are a video output: use a video config, or "
+                             "set path_output = False)")
         from .preprocess import YuvFrames
         if isinstance(item["image"], YuvFrames):
             raise ValueError("YuvFrames: the COCO image branch takes RGB tensors (decoder surfaces are a video input; convert one with "

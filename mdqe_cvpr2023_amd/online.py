@@ -57,6 +57,13 @@ include/mdqe_hip.h): `win.crops` uint8 [n, Fc, Sh, Sw, 3] (pinned host, channel 
 device scratch where the emit does not return them), and the session keeps the pushed frames under the `frames_held` bound above
 whatever the emit.  keep=True adds "pred_crops" / "pred_crop_rects" / "pred_crop_frames" to result(), equal to forward()'s with
 model.crop_output.
+
+paths=True, beside ANY emit: every window also carries where its tracks are -- `win.centroids` int32 [n, F, 2] (pinned host: (x, y) of
+the track's visible region of the label map, ((SX + m/2) / m, (SY + m/2) / m) in integers, (-1, -1) where it has none) and
+`win.moments` int64 [n, F, 3] = (m, SX, SY) -- summed on the device from the label map (ops.label_centroids; the map is then made for
+every emit).  keep=True adds "pred_centroids" / "pred_moments" to result(), equal to forward()'s with model.path_output.  The trails of
+Style(trail=...) are drawn from the same points and need no `paths`; their history is a device table of `trail` columns
+(merge.PathTable), so lines continue across windows and pushes and nothing grows with the video.
 """
 import contextlib
 import dataclasses
@@ -145,7 +152,9 @@ class Window:
     of the labels' visible regions.  With emit="overlay": `labels` as above and `overlay`, uint8 [f1-f0, H, W, 3] on the host, the
     frames with that map painted on -- or, in a surface=True session, a preprocess.YuvFrames of f1-f0 painted surfaces.  (`labels` and `overlay` are init-only pseudo-fields stored as plain attributes:
     dataclasses.fields(Window) is what it was.)  In a session with crops=: `crops` uint8 [n, Fc, Sh, Sw, 3], `crop_rects` int32 [n, Fc, 4]
-    and `crop_frames`, the Fc video frames taken (pseudo-fields of the same kind)."""
+    and `crop_frames`, the Fc video frames taken (pseudo-fields of the same kind).  In a session with paths=True: `centroids` int32 [n,
+    f1-f0, 2], (x, y) of each track's visible region of the label map per frame, (-1, -1) where it has none, and `moments` int64 [n,
+    f1-f0, 3], its (pixels, sum of X, sum of Y) (pseudo-fields of the same kind)."""
     frames: tuple
     track_ids: list
     cls_probs: torch.Tensor
@@ -158,16 +167,19 @@ class Window:
     crops: dataclasses.InitVar[torch.Tensor] = None
     crop_rects: dataclasses.InitVar[torch.Tensor] = None
     crop_frames: dataclasses.InitVar[list] = None
+    centroids: dataclasses.InitVar[torch.Tensor] = None
+    moments: dataclasses.InitVar[torch.Tensor] = None
 
-    def __post_init__(self, labels, overlay, crops, crop_rects, crop_frames):
+    def __post_init__(self, labels, overlay, crops, crop_rects, crop_frames, centroids, moments):
         self.labels = labels
         self.overlay = overlay
         self.crops, self.crop_rects, self.crop_frames = crops, crop_rects, crop_frames
+        self.centroids, self.moments = centroids, moments
 
 
 class OnlineVideo:
     def __init__(self, model, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None,
-                 surface=False, surface_pitch_align=1, crops=None):
+                 surface=False, surface_pitch_align=1, crops=None, paths=False):
         if emit not in ("masks", "rle", "labels", "overlay"):
             raise ValueError("online_video: emit must be 'masks', 'rle', 'labels' or 'overlay'")
         if not isinstance(surface, bool):
@@ -187,7 +199,12 @@ class OnlineVideo:
             if model.cfg.is_coco:
                 raise ValueError("online_video: crops with a COCO image config: per-track crops are a video output (use a video config)")
         self.crops = crops
-        if emit in ("labels", "overlay") or crops is not None:
+        if not isinstance(paths, bool):
+            raise ValueError("online_video: paths must be a bool, got %r" % (paths,))
+        if paths and model.cfg.is_coco:
+            raise ValueError("online_video: paths with a COCO image config: track centroids are a video output (use a video config)")
+        self.paths = paths
+        if emit in ("labels", "overlay") or crops is not None or paths:
             model.check_label_capacity()
         from .render import Style
         if style is not None and (emit != "overlay" or not isinstance(style, Style)):
@@ -254,7 +271,7 @@ class OnlineVideo:
             self.store = FrameStore()
         self.merger = ClipMerger(model, self.hw, self.out_size, self.mask_hw, n_frames=None, online=self.emit,
                                  geometry=self.geometry, frame_source=self.store, style=self.style, ground_truth=self.ground_truth,
-                                 surface=self.surface, surface_pitch_align=self.surface_pitch_align, crops=self.crops)
+                                 surface=self.surface, surface_pitch_align=self.surface_pitch_align, crops=self.crops, paths=self.paths)
         shapes = model.engine.cache_shapes(self.geo)
         per_frame = 4 * sum(int(np.prod(sh)) for sh in shapes.values())
         forced = int(os.environ.get("MDQE_CACHE_FRAMES", "0"))
@@ -287,7 +304,7 @@ class OnlineVideo:
             out.append(Window(frames=r["frames"], track_ids=list(range(n)), cls_probs=r["cls_probs"],
                               masks=r.get("masks"), rles=r.get("rles"), boxes=boxes, areas=areas, labels=r.get("labels"),
                               overlay=r.get("overlay"), crops=r.get("crops"), crop_rects=r.get("crop_rects"),
-                              crop_frames=r.get("crop_frames")))
+                              crop_frames=r.get("crop_frames"), centroids=r.get("centroids"), moments=r.get("moments")))
         del self.merger.emitted[:]
         if self.store is not None:
             # the chunks that lie wholly before the first frame no window has emitted are done with; what stays and may be the caller's
@@ -400,5 +417,8 @@ class OnlineVideo:
                                     lambda k, e=empty: e.expand((k,) + tuple(e.shape)), torch.cat)
                 res[key] = torch.stack(rows) if rows else torch.zeros((0, lc) + tuple(empty.shape), dtype=empty.dtype)
             res["pred_crop_frames"] = spec.taken(0, self.received)
+        if self.keep and forms.paths:             # (per output the track's path; absent before its first window)
+            res.update(merge.path_result(inst, self.received, [(w.frames[0], w.frames[1] - w.frames[0], len(w.track_ids), w.centroids, w.moments)
+                                                               for w in self.kept]))
         self._result = res
         return res

@@ -1016,6 +1016,118 @@ def track_crops_yuv(labels, yuv, geom, n, size, out=None, c_off=0, rects=None, f
     return out, rects
 
 
+def _point_table(name, pts, n, cols):
+    """The checks of a point table (ops.label_centroids writes it, ops.render_trails reads it): int32 [>= n, >= cols, 2], each row
+    contiguous and the rows apart.  -> its row stride in elements."""
+    if (not torch.is_tensor(pts) or pts.dtype != torch.int32 or pts.dim() != 3 or int(pts.shape[2]) != 2 or pts.shape[0] < n
+            or pts.shape[1] < cols or tuple(pts.stride()[1:]) != (2, 1) or (pts.shape[0] > 1 and pts.stride(0) < pts.shape[1] * 2)):
+        raise RuntimeError("%s: pts must be int32 [>= n = %d, >= p_off + F = %d, 2], each row contiguous and the rows apart" % (name, n, cols))
+    return _row_stride(pts, 2)
+
+
+def label_centroids(labels, n, min_area=0, mom=None, pts=None, p_off=0):
+    """Where each track is: for rows k = 0..n-1 (label k + 1) and the frames f of labels (uint8 [F, Ho, Wo], CUDA, contiguous:
+    ops.final_label_map's output), mom[k, f] = (m, SX, SY) (int64 [n, F, 3] or [n * F, 3], contiguous; None: allocated): the pixels
+    that hold the label, the sum of their X and of their Y; and the centroid of the visible region, ((SX + m/2) / m, (SY + m/2) / m) in
+    integer division where m >= max(1, min_area) and (-1, -1) elsewhere, into pts[k, p_off + f] (int32 [>= n, >= p_off + F, 2], rows any
+    stride apart -- a table whose columns are frames, kept over several windows; None: allocated, [n, p_off + F, 2], the columns below
+    p_off -1; False: the moments alone).  Both are fully overwritten; integers only, identical from run to run: the rule of
+    include/mdqe_hip.h, mdqe_label_centroids_u8.  At most three launches on the current stream, none when n == 0 or F == 0.
+    -> (mom, pts or None)."""
+    # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
+    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        raise RuntimeError("label_centroids: labels must be contiguous uint8 [F, Ho, Wo]")
+    F, Ho, Wo = (int(v) for v in labels.shape)
+    if Ho < 1 or Wo < 1 or Ho > 16384 or Wo > 16384 or F * Ho * Wo >= 2 ** 31 - 1:
+        raise RuntimeError("label_centroids: Ho, Wo must be in 1..16384 with F*Ho*Wo < 2^31 - 1, got %s" % (tuple(labels.shape),))
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= 255:
+        raise RuntimeError("label_centroids: n must be an int in 0..255, got %r" % (n,))
+    for what, v in (("min_area", min_area), ("p_off", p_off)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 2 ** 31 - 1:
+            raise RuntimeError("label_centroids: %s must be an int in 0..%d, got %r" % (what, 2 ** 31 - 1, v))
+    if mom is None:
+        mom = torch.empty((n, F, 3), dtype=torch.int64, device=labels.device)
+    if (not torch.is_tensor(mom) or mom.dtype != torch.int64 or not mom.is_contiguous() or mom.dim() not in (2, 3) or mom.shape[-1] != 3
+            or mom.numel() != n * F * 3 or (mom.dim() == 3 and int(mom.shape[0]) != n)):
+        raise RuntimeError("label_centroids: mom must be contiguous int64 [n * F = %d, 3] or [n = %d, F = %d, 3]" % (n * F, n, F))
+    stride = 2 * (p_off + F)
+    if pts is None:
+        pts = torch.full((n, p_off + F, 2), -1, dtype=torch.int32, device=labels.device)
+    if pts is not False:
+        stride = _point_table("label_centroids", pts, n, p_off + F)
+    for t, what in ((labels, "labels"), (mom, "mom"), (pts, "pts")):
+        if t is not False and (not t.is_cuda or t.device != labels.device):
+            raise RuntimeError("label_centroids: %s must be a CUDA tensor on the labels' device, got %s" % (what, t.device))
+    with torch.cuda.device(labels.device):
+        check(lib.mdqe_label_centroids_u8(ptr(labels), F, Ho, Wo, n, min_area, ptr(mom), ptr(pts) if pts is not False and n else None,
+                                          stride, p_off, cur_stream(labels.device)), "label_centroids")
+    return mom, (None if pts is False else pts)
+
+
+def _trail_args(name, pts, n, palette, F, f_off, p_off, trail, width, table_dtypes):
+    """The checks render_trails and render_trails_yuv share.  -> the point table's row stride."""
+    # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= 255:
+        raise RuntimeError("%s: n must be an int in 0..255, got %r" % (name, n))
+    for what, v, lo, hi in (("trail", trail, 1, 64), ("width", width, 1, 5), ("F", F, 0, 2 ** 31 - 1), ("f_off", f_off, 0, 2 ** 31 - 1),
+                            ("p_off", p_off, 0, 2 ** 31 - 1)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise RuntimeError("%s: %s must be an int in %d..%d, got %r" % (name, what, lo, hi, v))
+    stride = _point_table(name, pts, n, p_off + F)
+    if not torch.is_tensor(palette) or palette.dtype not in table_dtypes or tuple(palette.shape) != (256, 3) or not palette.is_contiguous():
+        raise RuntimeError("%s: palette must be contiguous %s [256, 3]" % (name, str(table_dtypes[0]).replace("torch.", "")))
+    return stride
+
+
+def render_trails(pic, pts, n, palette, F, f_off=0, p_off=0, trail=16, width=2):
+    """Motion trails drawn onto a painted picture, in place: pic (uint8 [>= f_off + F, Ho, Wo, 3], CUDA, contiguous) gets, in its frames
+    f_off .. f_off + F - 1 and for each label l = 1..n, the line through the points of row l - 1 of pts (int32 [>= n, >= p_off + F, 2]:
+    ops.label_centroids' table) in columns p_off + f - trail .. p_off + f, `width` pixels wide with round caps, in palette[l] (uint8
+    [256, 3]).  A column below 0 and a point outside the picture are absent; the present points are joined in column order, gaps
+    bridged; a lone point is a disc.  Lower labels lie over higher ones; a pixel that nothing hits is not written: the integer rule of
+    include/mdqe_hip.h, mdqe_render_trails_u8.  trail in 1..64, width in 1..5.  One launch on the current stream, none when F == 0 or
+    n == 0.  -> pic."""
+    stride = _trail_args("render_trails", pts, n, palette, F, f_off, p_off, trail, width, (torch.uint8,))
+    if not torch.is_tensor(pic) or pic.dtype != torch.uint8 or pic.dim() != 4 or int(pic.shape[3]) != 3 or not pic.is_contiguous():
+        raise RuntimeError("render_trails: pic must be contiguous uint8 [frames, Ho, Wo, 3]")
+    Ho, Wo = int(pic.shape[1]), int(pic.shape[2])
+    if Ho < 1 or Wo < 1 or Ho > 16384 or Wo > 16384 or f_off + F > pic.shape[0] or F * Ho * Wo >= 2 ** 31 - 1:
+        raise RuntimeError("render_trails: pic %s must hold frames f_off .. f_off + F = %d of a size in 1..16384, F*Ho*Wo < 2^31 - 1"
+                           % (tuple(pic.shape), f_off + F))
+    for t, what in ((pic, "pic"), (pts, "pts"), (palette, "palette")):
+        if not t.is_cuda or t.device != pic.device:
+            raise RuntimeError("render_trails: %s must be a CUDA tensor on pic's device, got %s" % (what, t.device))
+    with torch.cuda.device(pic.device):
+        check(lib.mdqe_render_trails_u8(ptr(pic), F, Ho, Wo, f_off, ptr(pts), stride, p_off, n, trail, width, ptr(palette),
+                                        cur_stream(pic.device)), "render_trails")
+    return pic
+
+
+def render_trails_yuv(yuv, pts, n, palette_yuv, F, f_off=0, p_off=0, trail=16, width=2):
+    """`render_trails` on painted decoder surfaces, in place: yuv (a preprocess.YuvFrames on a HIP device, NV12 or P010) gets the same
+    lines in its surfaces f_off .. f_off + F - 1, with palette_yuv (uint16 [256, 3], rows (Y, U, V) in sample units:
+    render.palette_yuv).  Luma follows the rule per sample; chroma is ops.annotate_yuv's rule: the integer rule of include/mdqe_hip.h,
+    mdqe_render_trails_yuv420sp.  -> yuv."""
+    from .preprocess import YUV_FORMATS, YuvFrames, _pitch_stride
+    stride = _trail_args("render_trails_yuv", pts, n, palette_yuv, F, f_off, p_off, trail, width, (torch.uint16, torch.int16))
+    if not isinstance(yuv, YuvFrames):
+        raise RuntimeError("render_trails_yuv: yuv must be a preprocess.YuvFrames, got %s" % type(yuv).__name__)
+    H, W = yuv.height, yuv.width
+    if H > 16384 or W > 16384 or f_off + F > len(yuv) or F * H * W >= 2 ** 31 - 1:
+        raise RuntimeError("render_trails_yuv: yuv holds %d surfaces of %d x %d, the call needs f_off + F = %d of a size up to 16384, "
+                           "F*H*W < 2^31 - 1" % (len(yuv), H, W, f_off + F))
+    if not yuv.is_cuda:
+        raise RuntimeError("render_trails_yuv: the surfaces must be on a HIP device, got %s (the trail pass has no host path)" % (yuv.device,))
+    for t, what in ((pts, "pts"), (palette_yuv, "palette_yuv")):
+        if t.device != yuv.device:
+            raise RuntimeError("render_trails_yuv: %s must be on the surfaces' device %s, got %s" % (what, yuv.device, t.device))
+    (yp, ys), (cp, cs) = _pitch_stride(yuv.y), _pitch_stride(yuv.uv)
+    with torch.cuda.device(yuv.device):
+        check(lib.mdqe_render_trails_yuv420sp(ptr(yuv.y), yp, ys, ptr(yuv.uv), cp, cs, F, H, W, YUV_FORMATS.index(yuv.fmt), f_off, ptr(pts),
+                                              stride, p_off, n, trail, width, ptr(palette_yuv), cur_stream(yuv.device)), "render_trails_yuv")
+    return yuv
+
+
 def _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action=None, cell=None):
     """The surface painters' rule of include/mdqe_hip.h on host planes, in torch integers.  action None: the plain painter, which is the
     table [0, 1, 1, ...] (no label has action 2, so no cell mean is taken) and may paint in place.  -> out."""

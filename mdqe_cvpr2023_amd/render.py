@@ -211,7 +211,10 @@ class Style:
     pixels, 0..4, of a frame around each track's visible region per frame (0: none); caption: None or which fields are written on a
     plate at the box's top left corner -- "id", "class", "id+class", "id+class+score", "class+score" (`captions`); class_names: None or
     a sequence of names by class id (a caption then shows the name, upper-cased, instead of the number); text_scale: pixels per font
-    pixel, 1..4; min_area: regions of fewer pixels get neither box nor caption."""
+    pixel, 1..4; min_area: regions of fewer pixels get neither box nor caption.
+    Trails (ops.render_trails, csrc/paths.hip: a pass between the painter and the annotations, so plates stay legible): trail: 0..64,
+    the number of past frames whose centroids (ops.label_centroids: of each track's visible region, the ones of at least min_area
+    pixels) are joined to the current frame's by a line in the track's colour, 0: none; trail_width: that line's width in pixels, 1..5."""
     alpha: float = 0.5
     contour: int = 1
     palette: torch.Tensor = None
@@ -223,8 +226,14 @@ class Style:
     class_names: tuple = None
     text_scale: int = 1
     min_area: int = 0
+    trail: int = 0
+    trail_width: int = 2
 
     def __post_init__(self):
+        if isinstance(self.trail, bool) or not isinstance(self.trail, int) or not 0 <= self.trail <= 64:
+            raise ValueError("overlay style: trail must be an int in 0..64, got %r" % (self.trail,))
+        if isinstance(self.trail_width, bool) or not isinstance(self.trail_width, int) or not 1 <= self.trail_width <= 5:
+            raise ValueError("overlay style: trail_width must be an int in 1..5, got %r" % (self.trail_width,))
         if isinstance(self.box, bool) or not isinstance(self.box, int) or not 0 <= self.box <= 4:
             raise ValueError("overlay style: box must be an int in 0..4, got %r" % (self.box,))
         if self.caption not in CAPTIONS:
@@ -272,6 +281,12 @@ class Style:
     def annotates(self):
         """Whether an annotation pass follows the painter (with the defaults: no, and exactly the painter's launches are made)."""
         return self.box > 0 or self.caption is not None
+
+    @property
+    def trails(self):
+        """Whether a trail pass runs between the painter and the annotations (with the defaults: no, and exactly the painter's launches
+        are made)."""
+        return self.trail > 0
 
     def _cached_on(self, slot, key, make):
         """A small host-made table on a device, made once per `key` (as `palette_on` keeps the palette)."""

@@ -566,6 +566,9 @@ class _Job:
         if getattr(model, "crop_output", None) is not None:
             raise ValueError("crop_output is not offered by the sharded driver: rank 0 does not hold every frame of the video (cut the crops "
                              "from pred_label_map and the frames on the host, or run the video on one device)")
+        if getattr(model, "path_output", False):
+            raise ValueError("path_output is not offered by the sharded driver: the centroids are summed from the label map where it is made, "
+                             "window by window on one device (sum them from pred_label_map on the host, or run the video on one device)")
         if ground_truth is not None:
             raise ValueError("ground_truth is not offered by the sharded driver: the overlap counts would have to follow the tracker replay on "
                              "rank 0 with the whole video's ground truth there (score the video on one device: model([{..., 'ground_truth': gt}]))")
