@@ -633,6 +633,50 @@ int mdqe_render_mosaic_yuv420sp(const void* y, long y_pitch, long y_stride, cons
                                 void* out_y, long out_y_pitch, long out_y_stride,
                                 void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream);
 
+/* The blur overlay (csrc/render_blur.hip): the same two painters with a PER-LABEL action, one of them a Gaussian redaction blur.  Every
+ * argument the two entries share with mdqe_render_mosaic_u8 / mdqe_render_mosaic_yuv420sp means what it means there; `cell` is replaced by
+ *   taps     uint16 [radius + 1], device, radius in 0..32: the weight of a sample d away is taps[|d|], in units of 1/4096, and
+ *            taps[0] + 2 * sum(taps[1..radius]) == 4096 (the caller's duty; render.blur_taps makes such tables).  The table is an input of
+ *            the rule, as the palette is.  radius = 0 with taps = {4096}: the blur is the identity;
+ *   taps_c   (surfaces) a second such table of radius_c in 0..16, for the chroma plane;
+ *   action   uint8 [256], device: 0 keep, 1 tint, 3 blur; ANY other value acts as 0.  action[0] is the background's.
+ * Integers only, ONE definition:
+ *   edge     exactly mdqe_render_overlay_u8's definition on the LABELS, whatever the actions are;
+ *   source   s_c(Y, X) is exactly mdqe_render_overlay_u8's source value: nearest-sampled onto the OUTPUT grid, float32 by the rint / clamp
+ *            / NaN rule, no frames: 0.  The blur acts on the output grid, as the mosaic's cells do;
+ *   blur     clamped coordinates replicate the picture's border: X' = min(max(X + d, 0), Wo - 1), Y' likewise.
+ *              h_c(Y, X)    = (sum_{d = -R..R} taps[|d|] * s_c(Y, X') + 128) >> 8         (at most 16368: 14 bits)
+ *              blur_c(Y, X) = (sum_{d = -R..R} taps[|d|] * h_c(Y', X) + 32768) >> 16      (the sum stays below 2^26)
+ *            A constant picture is therefore unchanged.  The taps take in ALL pixels under the kernel whatever their labels: a sharp
+ *            (kept or tinted) object next to a blurred background bleeds into it, and a blurred object takes in its surroundings --
+ *            the behaviour of a plain Gaussian blur; the blur does not stop at region borders;
+ *   RGB      with l the pixel's label:  action 1: out_c = palette[l][c] if edge, else (s_c*(256 - a256) + palette[l][c]*a256 + 128) >> 8;
+ *                                       action 3: out_c = blur_c(Y, X);
+ *                                       else:     out_c = s_c;
+ *   YUV      (values: word >> 6 for P010.)  Luma follows the RGB rule on the luma plane with `taps`.  Chroma is blurred on its own
+ *            ceil(H/2) x ceil(W/2) grid of pairs, U and V separately, with taps_c and coordinates clamped to that plane.  The chroma rule
+ *            of mdqe_render_overlay_yuv420sp stays: Cout = (sum_i px_i + n / 2) >> log2(n) over the n in-picture pixels i of the pair's
+ *            2 x 2 block, where px_i is C for a kept pixel, the palette or blend value for action 1 and the pair's blurred C for action 3;
+ *   P010     a luma word whose pixel is kept is copied with all 16 bits, and so is a chroma pair whose block's pixels are all kept; every
+ *            other word is written as value << 6.
+ * With action = {0, 1, 1, ..., 1} both entries are, by this definition, bit-identical to the plain painters.
+ * MDQE_EINVAL for a radius outside 0..32 or a radius_c outside 0..16; every other check is that of the mosaic entries, made before any
+ * pointer is looked at; F == 0 returns OK and launches nothing; a null or odd tap table is refused as the palette is.
+ * mdqe_render_blur_yuv420sp does NOT paint in place: the taps read samples that other threads write, so an output plane that meets an
+ * input plane in any way (or the other output plane, the labels, the palette, the action table, either tap table) is MDQE_EINVAL.
+ * Nothing needs to be aligned.  Only tiles (16 x 64 pixels) that hold a pixel of action 3 are filtered.  One launch, no global scratch,
+ * no atomics: identical from run to run.  Never allocates, never synchronises. */
+int mdqe_render_blur_u8(const void* frames, int is_u8, long frame_stride, int h0, int w0,
+                        const unsigned char* labels, int F, int Ho, int Wo,
+                        const unsigned char* palette, const unsigned char* action, int a256, int contour,
+                        const unsigned short* taps, int radius, unsigned char* out, int f_off, void* stream);
+int mdqe_render_blur_yuv420sp(const void* y, long y_pitch, long y_stride, const void* uv, long uv_pitch, long uv_stride,
+                              int F, int H, int W, int fmt /*0 nv12, 1 p010*/, const unsigned char* labels,
+                              const unsigned short* palette_yuv, const unsigned char* action, int a256, int contour,
+                              const unsigned short* taps, int radius, const unsigned short* taps_c, int radius_c,
+                              void* out_y, long out_y_pitch, long out_y_stride,
+                              void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream);
+
 /* Track boxes and captions on a painted picture (csrc/annotate.hip): the box and the text plate per instance that the demo's
  * visualiser draws on the host (demo/clip/visualizer.py:162,205; captions "[id] class score%", demo/visualizer.py:72-91).  An
  * ANNOTATION PASS: it runs behind any of the four painters above, IN PLACE on the painted picture, on the same stream; the painters

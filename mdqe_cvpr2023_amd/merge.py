@@ -227,7 +227,8 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
     YuvFrames; the pieces are then the surfaces handed in, of the output size): painted in the YUV domain, one
     ops.render_overlay_yuv launch per piece, with the palette in the surfaces' samples.  A style with a mosaic (style.mosaic): the
     same launches of ops.render_mosaic / ops.render_mosaic_yuv with the style's action table; `cls`, the window's class rows [n, K]
-    on the host, is what a style with `classes` builds that table from.  A style that annotates (style.annotates: track boxes,
+    on the host, is what a style with `classes` builds that table from.  A style with a blur (style.blur): the same launches of
+    ops.render_blur / ops.render_blur_yuv with that table and the style's tap tables (style.taps_on, style.taps_c_on).  A style that annotates (style.annotates: track boxes,
     captions) takes the geometry table from `label_maps` whether or not `geometry` asks for it and, behind the painter launches, runs
     one ops.annotate / ops.annotate_yuv launch per piece in place on the painted frames, on the same stream, with the captions made
     from `cls`; nothing is read back.  `paths` (a PathTable whose `begin` has been called for this window): the window's centroids are
@@ -242,12 +243,18 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
         paths.run(labels, l_off)
     surface = not torch.is_tensor(out)
     pal = style.palette_yuv_on(m.device, *out.meta()[2:]) if surface else style.palette_on(m.device)
-    act = style.actions_on(m.device, cls) if style.mosaic is not None else None
+    act = style.actions_on(m.device, cls) if style.mosaic is not None or style.blur is not None else None
+    taps = style.taps_on(m.device) if style.blur is not None else None
+    taps_c = style.taps_c_on(m.device) if taps is not None and surface else None
     pieces = source.pieces(int(f0), int(f0) + nf, stream=torch.cuda.current_stream(m.device))
     for t, first in pieces:
         k, d = len(t), first - int(f0)
         lab = labels[l_off + d:l_off + d + k]
-        if act is not None and surface:
+        if taps is not None and surface:
+            ops.render_blur_yuv(lab, t, pal, act, taps, taps_c, out, o_off + d, style.a256, style.contour)
+        elif taps is not None:
+            ops.render_blur(lab, t, pal, act, taps, out, o_off + d, style.a256, style.contour)
+        elif act is not None and surface:
             ops.render_mosaic_yuv(lab, t, pal, act, out, o_off + d, style.a256, style.contour, style.cell)
         elif act is not None:
             ops.render_mosaic(lab, t, pal, act, out, o_off + d, style.a256, style.contour, style.cell)

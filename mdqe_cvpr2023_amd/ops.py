@@ -668,8 +668,19 @@ def _mosaic_args(name, action, cell):
         raise RuntimeError("%s: cell must be an even int in 2..64, got %r" % (name, cell))
 
 
-def _rgb_paint_args(name, labels, frames, palette, out, f_off, a256, contour, mosaic=None):
-    """The checks of render_overlay and of render_mosaic (mosaic = (action, cell)).  -> (F, Ho, Wo, h0, w0, frame stride)."""
+def _blur_args(name, action, taps, taps_c=None, surface=False):
+    """The action table and the tap tables of the blur painters (render.blur_taps): luma / RGB radius 0..32, chroma 0..16."""
+    if not torch.is_tensor(action) or action.dtype != torch.uint8 or tuple(action.shape) != (256,) or not action.is_contiguous():
+        raise RuntimeError("%s: action must be contiguous uint8 [256] (render.Style.actions)" % name)
+    for t, what, top in ((taps, "taps", 32),) + (((taps_c, "taps_c", 16),) if surface else ()):
+        if (not torch.is_tensor(t) or t.dtype not in (torch.uint16, torch.int16) or t.dim() != 1 or not 1 <= t.numel() <= top + 1
+                or not t.is_contiguous()):
+            raise RuntimeError("%s: %s must be contiguous uint16 [radius + 1], radius in 0..%d (render.blur_taps)" % (name, what, top))
+
+
+def _rgb_paint_args(name, labels, frames, palette, out, f_off, a256, contour, mosaic=None, blur=None):
+    """The checks of render_overlay, of render_mosaic (mosaic = (action, cell)) and of render_blur (blur = (action, taps)).
+    -> (F, Ho, Wo, h0, w0, frame stride)."""
     # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
     if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
         raise RuntimeError("%s: labels must be contiguous uint8 [F, Ho, Wo]" % name)
@@ -678,6 +689,8 @@ def _rgb_paint_args(name, labels, frames, palette, out, f_off, a256, contour, mo
         raise RuntimeError("%s: a256 must be an int in 0..256 and contour an int in 0..3, got %r, %r" % (name, a256, contour))
     if mosaic is not None:
         _mosaic_args(name, *mosaic)
+    if blur is not None:
+        _blur_args(name, *blur)
     if Ho < 1 or Wo < 1 or Ho * Wo * 3 >= 2 ** 31 or F * Ho * Wo >= 2 ** 31:
         raise RuntimeError("%s: Ho, Wo must be positive with Ho*Wo*3 < 2^31 and F*Ho*Wo < 2^31, got %s" % (name, tuple(labels.shape)))
     if not torch.is_tensor(palette) or palette.dtype != torch.uint8 or tuple(palette.shape) != (256, 3) or not palette.is_contiguous():
@@ -695,7 +708,8 @@ def _rgb_paint_args(name, labels, frames, palette, out, f_off, a256, contour, mo
         if tuple(frames.stride()[1:]) != (h0 * w0, w0, 1) or stride < 3 * h0 * w0 or h0 * Ho >= 2 ** 31 or w0 * Wo >= 2 ** 31:
             raise RuntimeError("%s: every frame must be contiguous and the frames a stride >= 3*h0*w0 apart, got strides %s"
                                % (name, tuple(frames.stride())))
-    tensors = [(labels, "labels"), (palette, "palette")] + ([(mosaic[0], "action")] if mosaic is not None else []) + [(out, "out"), (frames, "frames")]
+    tensors = [(labels, "labels"), (palette, "palette")] + ([(mosaic[0], "action")] if mosaic is not None else [])
+    tensors += ([(blur[0], "action"), (blur[1], "taps")] if blur is not None else []) + [(out, "out"), (frames, "frames")]
     for t, what in tensors:
         if t is not None and (not t.is_cuda or t.device != out.device):
             raise RuntimeError("%s: %s must be a CUDA tensor on out's device, got %s" % (name, what, t.device))
@@ -729,9 +743,9 @@ def render_mosaic(labels, frames, palette, action, out, f_off=0, a256=128, conto
     return out
 
 
-def _yuv_paint_args(name, labels, yuv, palette_yuv, out, f_off, a256, contour, mosaic=None):
-    """The checks of render_overlay_yuv and of render_mosaic_yuv (mosaic = (action, cell)); allocates `out` when None.
-    -> (F, H, W, out)."""
+def _yuv_paint_args(name, labels, yuv, palette_yuv, out, f_off, a256, contour, mosaic=None, blur=None):
+    """The checks of render_overlay_yuv, of render_mosaic_yuv (mosaic = (action, cell)) and of render_blur_yuv (blur = (action, taps,
+    taps_c)); allocates `out` when None.  -> (F, H, W, out)."""
     from .preprocess import YuvFrames
     if not isinstance(yuv, YuvFrames):
         raise RuntimeError("%s: yuv must be a preprocess.YuvFrames, got %s" % (name, type(yuv).__name__))
@@ -742,6 +756,8 @@ def _yuv_paint_args(name, labels, yuv, palette_yuv, out, f_off, a256, contour, m
         raise RuntimeError("%s: a256 must be an int in 0..256 and contour an int in 0..3, got %r, %r" % (name, a256, contour))
     if mosaic is not None:
         _mosaic_args(name, *mosaic)
+    if blur is not None:
+        _blur_args(name, *blur, surface=True)
     if F * H * W >= 2 ** 31 - 1:
         raise RuntimeError("%s: F*H*W must stay below 2^31 - 1, got %s" % (name, (F, H, W)))
     if (not torch.is_tensor(palette_yuv) or palette_yuv.dtype not in (torch.uint16, torch.int16) or tuple(palette_yuv.shape) != (256, 3)
@@ -752,7 +768,8 @@ def _yuv_paint_args(name, labels, yuv, palette_yuv, out, f_off, a256, contour, m
     if (not isinstance(out, YuvFrames) or (out.height, out.width, out.fmt) != (H, W, yuv.fmt) or not isinstance(f_off, int) or f_off < 0
             or f_off + F > len(out)):
         raise RuntimeError("%s: out must be a YuvFrames of >= f_off + F = %d surfaces of %d x %d %s" % (name, f_off + F, H, W, yuv.fmt))
-    tensors = [(labels, "labels"), (palette_yuv, "palette_yuv")] + ([(mosaic[0], "action")] if mosaic is not None else []) + [(out, "out")]
+    tensors = [(labels, "labels"), (palette_yuv, "palette_yuv")] + ([(mosaic[0], "action")] if mosaic is not None else [])
+    tensors += ([(blur[0], "action"), (blur[1], "taps"), (blur[2], "taps_c")] if blur is not None else []) + [(out, "out")]
     for t, what in tensors:
         if t.device != yuv.device:
             raise RuntimeError("%s: %s must be on the surfaces' device %s, got %s" % (name, what, yuv.device, t.device))
@@ -817,15 +834,69 @@ def render_mosaic_yuv(labels, yuv, palette_yuv, action, out=None, f_off=0, a256=
         return out
     if F == 0:
         return out
+    _host_planes_apart("render_mosaic_yuv", "mosaic", yuv, out, f_off, F)
+    return _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action, cell)
 
+
+def _host_planes_apart(name, what, yuv, out, f_off, F):
+    """The host paths' refusal of an `out` that shares memory with `yuv` (a mosaic and a blur are not painted in place)."""
     def span(t):                                    # the bytes a plane's view reaches
         return t.data_ptr(), t.data_ptr() + (sum((s - 1) * st for s, st in zip(t.shape, t.stride())) + 1) * t.element_size()
     for src in (yuv.y, yuv.uv):
         for dst in (out.y[f_off:f_off + F], out.uv[f_off:f_off + F]):
             (a0, a1), (b0, b1) = span(src), span(dst)
             if a0 < b1 and b0 < a1:
-                raise RuntimeError("render_mosaic_yuv: out must not share memory with yuv (the mosaic is not painted in place)")
-    return _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action, cell)
+                raise RuntimeError("%s: out must not share memory with yuv (the %s is not painted in place)" % (name, what))
+
+
+def render_blur(labels, frames, palette, action, taps, out, f_off=0, a256=128, contour=1):
+    """`render_overlay` with a per-label action (uint8 [256], action[l]: 0 keep the source, 1 tint as render_overlay does, 3 blur, any
+    other value as 0; action[0] is the background's): a blur pixel becomes the separable Gaussian of the OUTPUT grid's source values
+    with the integer taps `taps` (uint16 [radius + 1], radius 0..32, taps[0] + 2 * sum(taps[1:]) == 4096: render.blur_taps), the
+    picture's border replicated, over all pixels under the kernel whatever their labels.  Every other argument is render_overlay's;
+    with action = [0, 1, 1, ...] the picture is render_overlay's bit for bit: the integer rule of include/mdqe_hip.h,
+    mdqe_render_blur_u8.  -> out."""
+    F, Ho, Wo, h0, w0, stride = _rgb_paint_args("render_blur", labels, frames, palette, out, f_off, a256, contour, blur=(action, taps))
+    check(lib.mdqe_render_blur_u8(ptr(frames) if frames is not None else None, int(frames is not None and frames.dtype == torch.uint8),
+                                  stride, h0, w0, ptr(labels), F, Ho, Wo, ptr(palette), ptr(action), a256, contour, ptr(taps),
+                                  int(taps.numel()) - 1, ptr(out), f_off, cur_stream()), "render_blur")
+    return out
+
+
+def render_blur_yuv(labels, yuv, palette_yuv, action, taps, taps_c, out=None, f_off=0, a256=128, contour=1):
+    """`render_overlay_yuv` with a per-label action (as `render_blur`): a blur pixel's luma is the Gaussian of the luma plane with
+    `taps`, and it enters its chroma pair's block mean with the pair's U / V blurred on the chroma plane's own ceil(H/2) x ceil(W/2)
+    grid with `taps_c` (uint16 [radius_c + 1], radius_c 0..16); a pixel that is kept keeps the decoder's bits (P010: all 16 of a word;
+    a chroma pair when its whole block is kept): the integer rule of include/mdqe_hip.h, mdqe_render_blur_yuv420sp.  Not in place:
+    `out` must not share memory with `yuv` (the taps read samples other threads write).  On a HIP device one launch on the current
+    stream; on host planes the same rule in torch integers.  -> out."""
+    F, H, W, out = _yuv_paint_args("render_blur_yuv", labels, yuv, palette_yuv, out, f_off, a256, contour, blur=(action, taps, taps_c))
+    if yuv.is_cuda:
+        src, dst = _surface_call_args(labels, yuv, palette_yuv, out, F, H, W)
+        with torch.cuda.device(yuv.device):
+            check(lib.mdqe_render_blur_yuv420sp(*src, ptr(action), a256, contour, ptr(taps), int(taps.numel()) - 1, ptr(taps_c),
+                                                int(taps_c.numel()) - 1, *dst, f_off, cur_stream(yuv.device)), "render_blur_yuv")
+        return out
+    if F == 0:
+        return out
+    _host_planes_apart("render_blur_yuv", "blur", yuv, out, f_off, F)
+    return _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action, taps=(taps, taps_c))
+
+
+def _blur_plane(v, taps):
+    """v int64 [F, h, w] -> the blur of include/mdqe_hip.h: rows first, (sum + 128) >> 8, then columns, (sum + 32768) >> 16, the
+    border replicated."""
+    w = (taps.view(torch.int16).to(torch.int64) & 0xFFFF).tolist()
+    R = len(w) - 1
+
+    def one(t, dim, add, shift):
+        n = t.shape[dim]
+        idx = torch.arange(n)
+        acc = torch.zeros_like(t)
+        for d in range(-R, R + 1):
+            acc += w[abs(d)] * t.index_select(dim, (idx + d).clamp(0, n - 1))
+        return (acc + add) >> shift
+    return one(one(v, 2, 128, 8), 1, 32768, 16)
 
 
 def _annotate_args(name, geom, n, palette, ink, captions, font, f_off, box, scale, min_area, table_dtypes):
@@ -1128,9 +1199,10 @@ def render_trails_yuv(yuv, pts, n, palette_yuv, F, f_off=0, p_off=0, trail=16, w
     return yuv
 
 
-def _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action=None, cell=None):
+def _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action=None, cell=None, taps=None):
     """The surface painters' rule of include/mdqe_hip.h on host planes, in torch integers.  action None: the plain painter, which is the
-    table [0, 1, 1, ...] (no label has action 2, so no cell mean is taken) and may paint in place.  -> out."""
+    table [0, 1, 1, ...] (no label has action 2, so no cell mean is taken) and may paint in place.  taps = (taps, taps_c): the blur
+    painter, whose special action is 3 and whose special value is the blurred plane's; every action but 1 and 3 then keeps.  -> out."""
     F, H, W = len(yuv), yuv.height, yuv.width
     p010 = yuv.fmt == "p010"
     ch, cw = (H + 1) // 2, (W + 1) // 2
@@ -1146,10 +1218,14 @@ def _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action=
         return t.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)[:, :H, :W]
 
     def means(v, sub):                              # cell means of a plane sub-sampled by `sub`; never looked at without an action 2
+        if taps is not None:                        # (the blur: the plane's own taps; what px calls action 2 is action 3 here)
+            return _blur_plane(v, taps[sub - 1])
         return v if action is None else _cell_means(v, cell // sub)
 
     lab = labels.to(torch.int64)
     act = (lab != 0).to(torch.int64) if action is None else action.to(torch.int64)[lab]
+    if taps is not None:
+        act = torch.where(act == 3, 2, torch.where(act == 1, 1, 0))
     edge = torch.zeros(lab.shape, dtype=torch.bool)
     for d in range(1, contour + 1):
         if d < H:

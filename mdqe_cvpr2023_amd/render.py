@@ -1,12 +1,14 @@
 """How an overlay is painted (model.overlay_output, online_video(emit="overlay")): the palette and the style.  The painting itself is
 ops.render_overlay (csrc/render.hip) behind the label map; merge.overlay_frames puts the two together for a tracker window.  A style
-with a mosaic (redaction) is painted by ops.render_mosaic (csrc/render_mosaic.hip) from the style's per-label action table.  A style
+with a mosaic (redaction) is painted by ops.render_mosaic (csrc/render_mosaic.hip) from the style's per-label action table, one with a
+blur by ops.render_blur (csrc/render_blur.hip) from the same table and the tap tables of `blur_taps`.  A style
 with a box or a caption has ops.annotate (csrc/annotate.hip) draw them onto the painted picture, from the label map's geometry table,
 the font, the ink colours and the window's caption table made here.  `Crops` is the request for the other picture made from the same
 trio of frames, label map and geometry table: one fixed-size chip per track and frame (ops.track_crops, csrc/crops.hip).
 
 A track's colour depends only on its tracker row (label = row + 1), so it keeps its colour across windows and pushes."""
 import dataclasses
+import math
 
 import torch
 
@@ -197,6 +199,22 @@ def captions(style, cls_probs, n):
     return table
 
 
+def blur_taps(radius):
+    """The taps of the blur painters (ops.render_blur, csrc/render_blur.hip), uint16 [radius + 1] on the host, a pure function: a
+    Gaussian of sigma = radius / 2 cut at `radius`, g[d] = exp(-2 d^2 / radius^2), in units of 1/4096 -- w[d] = rint(4096 g[d] / G) for
+    d >= 1 with G = g[0] + 2 sum(g[1:]), and the centre takes the residue, w[0] = 4096 - 2 sum(w[1:]), so the taps of a row add up to
+    4096 exactly and a constant picture stays as it is.  radius 0..32; 0 gives [4096], the identity.  (For every radius the products
+    4096 g[d] / G stay at least 1.5e-3 away from a rounding tie: the table does not depend on the host's libm.)"""
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= 32:
+        raise ValueError("blur_taps: radius must be an int in 0..32, got %r" % (radius,))
+    if radius == 0:
+        return torch.tensor([4096], dtype=torch.int32).to(torch.uint16)
+    g = [math.exp(-2.0 * d * d / (radius * radius)) for d in range(radius + 1)]
+    total = g[0] + 2.0 * sum(g[1:])
+    w = [int(round(4096.0 * v / total)) for v in g[1:]]
+    return torch.tensor([4096 - 2 * sum(w)] + w, dtype=torch.int32).to(torch.uint16)
+
+
 @dataclasses.dataclass
 class Style:
     """alpha: weight of the track colour inside a region, 0..1 (the kernel blends with a256 = round(alpha * 256) in 1/256 steps);
@@ -206,7 +224,13 @@ class Style:
     `classes` the tracks of those classes, the others tinted as ever; the background stays as decoded -- or "background" -- everything
     but the tracks, which are tinted as alpha / contour say (alpha=0, contour=0: left exactly as decoded).  cell: the side of a mosaic
     cell in output pixels, an even int in 2..64.  classes: None or a collection of class ids >= 0 (kept as a sorted tuple), only with
-    mosaic="tracks".
+    mosaic="tracks" or blur="tracks".
+    blur: None, or what is blurred instead of tinted (ops.render_blur, csrc/render_blur.hip), with `mosaic`'s meanings: "tracks" --
+    every track, or with `classes` the tracks of those classes, the others tinted; the background stays as decoded -- or "background"
+    -- everything but the tracks, which are tinted as alpha / contour say.  Not together with a mosaic.  blur_radius: the reach of the
+    Gaussian in output pixels, an int in 1..32 (sigma = blur_radius / 2, `blur_taps`; a surface's chroma planes, half as wide, are
+    blurred with radius (blur_radius + 1) // 2).  The blur takes in ALL pixels under the kernel whatever their labels: a sharp object
+    next to a blurred background bleeds into it, as with any plain Gaussian blur.
     Annotations (ops.annotate, csrc/annotate.hip: a pass behind whichever painter the fields above choose): box: the thickness in
     pixels, 0..4, of a frame around each track's visible region per frame (0: none); caption: None or which fields are written on a
     plate at the box's top left corner -- "id", "class", "id+class", "id+class+score", "class+score" (`captions`); class_names: None or
@@ -221,6 +245,8 @@ class Style:
     mosaic: str = None
     cell: int = 16
     classes: tuple = None
+    blur: str = None
+    blur_radius: int = 8
     box: int = 0
     caption: str = None
     class_names: tuple = None
@@ -261,6 +287,12 @@ class Style:
             raise ValueError("overlay style: mosaic must be None, 'tracks' or 'background', got %r" % (self.mosaic,))
         if isinstance(self.cell, bool) or not isinstance(self.cell, int) or not 2 <= self.cell <= 64 or self.cell % 2:
             raise ValueError("overlay style: cell must be an even int in 2..64, got %r" % (self.cell,))
+        if self.blur not in (None, "tracks", "background"):
+            raise ValueError("overlay style: blur must be None, 'tracks' or 'background', got %r" % (self.blur,))
+        if isinstance(self.blur_radius, bool) or not isinstance(self.blur_radius, int) or not 1 <= self.blur_radius <= 32:
+            raise ValueError("overlay style: blur_radius must be an int in 1..32, got %r" % (self.blur_radius,))
+        if self.mosaic is not None and self.blur is not None:
+            raise ValueError("overlay style: a style has a mosaic or a blur, not both; got mosaic=%r with blur=%r" % (self.mosaic, self.blur))
         if self.classes is not None:
             try:
                 cls = tuple(self.classes) if not isinstance(self.classes, (str, bytes)) else None
@@ -268,9 +300,9 @@ class Style:
                 cls = None
             if cls is None or any(isinstance(c, bool) or not isinstance(c, int) or c < 0 for c in cls):
                 raise ValueError("overlay style: classes must be None or a collection of ints >= 0, got %r" % (self.classes,))
-            if self.mosaic != "tracks":
-                raise ValueError("overlay style: classes selects the tracks that mosaic='tracks' pixelates; got classes with mosaic=%r"
-                                 % (self.mosaic,))
+            if self.mosaic != "tracks" and self.blur != "tracks":
+                raise ValueError("overlay style: classes selects the tracks that mosaic='tracks' pixelates or blur='tracks' blurs; got "
+                                 "classes with mosaic=%r, blur=%r" % (self.mosaic, self.blur))
             self.classes = tuple(sorted(set(cls)))
 
     @property
@@ -317,23 +349,26 @@ class Style:
         return None if self.caption is None else captions(self, cls_probs, n).to(device)
 
     def actions(self, cls_probs=None):
-        """The per-label action table of ops.render_mosaic, uint8 [256] on the host (0 keep, 1 tint, 2 mosaic; entry 0 is the
-        background's), a pure function.  mosaic=None: [0, 1, 1, ...] (the plain overlay); "background": [2, 1, 1, ...]; "tracks":
-        [0, 2, 2, ...], or with `classes`, from the window's class rows cls_probs [n, K] (win.cls_probs): label t + 1 gets 2 when the
-        first maximum of row t is a class in `classes` and 1 otherwise, and so do the labels above n."""
+        """The per-label action table of ops.render_mosaic / ops.render_blur, uint8 [256] on the host (0 keep, 1 tint, 2 mosaic, 3 blur;
+        entry 0 is the background's), a pure function.  With r = 2 for a mosaic and 3 for a blur: neither: [0, 1, 1, ...] (the plain
+        overlay); "background": [r, 1, 1, ...]; "tracks": [0, r, r, ...], or with `classes`, from the window's class rows cls_probs
+        [n, K] (win.cls_probs): label t + 1 gets r when the first maximum of row t is a class in `classes` and 1 otherwise, and so do
+        the labels above n."""
+        what, r = (self.blur, 3) if self.blur is not None else (self.mosaic, 2)
         act = torch.ones(256, dtype=torch.uint8)
-        act[0] = 2 if self.mosaic == "background" else 0
-        if self.mosaic == "tracks" and self.classes is None:
-            act[1:] = 2
-        elif self.mosaic == "tracks":
+        act[0] = r if what == "background" else 0
+        if what == "tracks" and self.classes is None:
+            act[1:] = r
+        elif what == "tracks":
             if not torch.is_tensor(cls_probs) or cls_probs.dim() != 2:
-                raise ValueError("overlay style: a mosaic of classes needs the window's class rows [n, K], got %r" % (type(cls_probs).__name__,))
+                raise ValueError("overlay style: a %s of classes needs the window's class rows [n, K], got %r"
+                                 % ("blur" if r == 3 else "mosaic", type(cls_probs).__name__))
             n = min(int(cls_probs.shape[0]), 255)
             if n and cls_probs.shape[1]:
                 rows = cls_probs[:n].detach().cpu()
                 first = rows.argmax(1)                  # (of several maxima the first: torch.argmax's rule)
                 hit = torch.isin(first, torch.tensor(self.classes, dtype=first.dtype))
-                act[1:n + 1] = torch.where(hit, 2, 1).to(torch.uint8)
+                act[1:n + 1] = torch.where(hit, r, 1).to(torch.uint8)
         return act
 
     def actions_on(self, device, cls_probs=None):
@@ -348,6 +383,14 @@ class Style:
             if cache[key].is_cuda:
                 torch.cuda.current_stream(cache[key].device).synchronize()
         return cache[key]
+
+    def taps_on(self, device):
+        """`blur_taps(blur_radius)` on `device` (cached per device, as `palette_on` keeps the palette)."""
+        return self._cached_on("_taps_on", (str(device), self.blur_radius), lambda: blur_taps(self.blur_radius))
+
+    def taps_c_on(self, device):
+        """The chroma planes' taps of a surface, `blur_taps((blur_radius + 1) // 2)`, on `device` (cached per device)."""
+        return self._cached_on("_taps_c_on", (str(device), self.blur_radius), lambda: blur_taps((self.blur_radius + 1) // 2))
 
     def palette_on(self, device):
         """The palette on `device`, contiguous (cached per device: one tiny upload per session, not per window)."""
