@@ -514,6 +514,24 @@ int mdqe_final_masks_rle_geom(const float* logits, int n_sel, const int* inst_id
 int mdqe_final_label_map_u8(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
                             int h, int w, int Ho, int Wo, unsigned char* out, int f_off, int* geom, void* stream);
 
+/* The soft form of the same sweep: ONE plane per frame that holds a WEIGHT, the matte that compositing takes, instead of a name.
+ * logits .. Wo are the label map's.  Row k takes part iff take == NULL or take[inst_idx_dev[k] + 1] != 0: take is uint8 [256] on the
+ * device, indexed by the row's label as in the label map (entry 0 is unused; the kernel masks the index to 0..255, so an index the
+ * caller should not have passed -- inst_idx_dev[k] >= 255 -- reads entry (index & 255) and never memory outside the table).  Per output pixel, with v_k the up-sampled logit and b_k
+ * the final-mask bit of row k (the expressions of the entry points above: one definition of both), over the participating rows:
+ *   vmax = the largest v_k;   U = the OR of the b_k;
+ *   x = gain * vmax (fp32);   p = 1 / (1 + expf(-x));   a = (int)rintf(255 * p);
+ *   out[f_off + f, Y, X] = U ? max(a, 128) : min(a, 127);   no participating row: 0.
+ * So out >= 128 exactly on the union of the participating rows' dense masks, bit for bit, whatever gain is and whatever the last ulp
+ * of expf is; away from that edge the plane is the rounded sigmoid, to the last ulp of expf.  out uint8 [>= f_off + Fw, Ho, Wo].
+ * MDQE_EINVAL, before any pointer is looked at: the label map's checks (n_sel <= 255, (long)Ho*Wo < 2^31, Hm*Wm < 2^31, f_off >= 0)
+ * and a gain that is not finite or outside (0, 64].  Fw == 0 returns OK and launches nothing; n_sel == 0 with Fw > 0 writes zeros.
+ * Any Wo and any f_off (4 bytes per store where the address allows, single bytes otherwise).  One launch, no atomics: identical from
+ * run to run.  Never allocates, never synchronises. */
+int mdqe_final_matte_u8(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
+                        int h, int w, int Ho, int Wo, const unsigned char* take, float gain, unsigned char* out, int f_off,
+                        void* stream);
+
 /* A window's final masks scored against ground truth without leaving the device: the integers behind the video IoU of the YTVIS
  * evaluator (mdqe/data/pycocotools/ytvoseval.py:173-219).  logits, n_sel, inst_idx_dev, Fw, Hm, Wm, factor, h, w, Ho, Wo are exactly
  * mdqe_final_masks_u8's, and b_k(f, Y, X), the bit of selected row k at window frame f and output pixel (Y, X), is that entry point's
@@ -676,6 +694,52 @@ int mdqe_render_blur_yuv420sp(const void* y, long y_pitch, long y_stride, const 
                               const unsigned short* taps, int radius, const unsigned short* taps_c, int radius_c,
                               void* out_y, long out_y_pitch, long out_y_stride,
                               void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream);
+
+/* The compositing painter (csrc/render_replace.hip): the overlay's picture mixed with a backdrop by a soft matte, so that tracks or the
+ * background are REPLACED with an anti-aliased edge.  Every argument the entry shares with mdqe_render_mosaic_u8 means what it means
+ * there (there is no `cell`); new are
+ *   matte             uint8 [F, Ho, Wo], device: what mdqe_final_matte_u8 writes for the frames of `labels`;
+ *   backdrop          uint8 [3], device: one colour in the frames' channel order -- or, with backdrop_picture = 1, uint8 [Ho, Wo, 3],
+ *                     pixel-interleaved: one picture of the output's size, the same for every frame;
+ *   mode              0 "background": the matte is the foreground that is kept; 1 "tracks": the matte covers what is replaced;
+ *   action            uint8 [256], device: 0 keep, 1 tint, 4 replace; ANY other value acts as 0.  For this painter 4 acts as 0 too: WHAT
+ *                     is replaced is said by the matte (made from the rows the caller's table selects), the action only says how the
+ *                     pixel under it looks.
+ * Integers only, ONE definition:
+ *   base    mdqe_render_overlay_u8's pixel with the action deciding: action 1: palette[l][c] if edge, else (s_c*(256 - a256) +
+ *           palette[l][c]*a256 + 128) >> 8; else s_c.  Source value, edge (on the LABELS) and blend are that entry's, unchanged;
+ *   weight  Wt = matte[f, Y, X] (mode 0) or 255 - matte[f, Y, X] (mode 1);
+ *   mix     mix(s, b, w) = (s*w + b*(255 - w) + 127) / 255, integer division (255 is odd: no ties; w = 255 gives s, w = 0 gives b);
+ *   pixel   out_c = mix(base_c, B_c, Wt) with B = backdrop[c], or backdrop[Y][X][c] of the picture.
+ * A pixel with Wt == 255 and a kept label therefore keeps the source byte.  MDQE_EINVAL for a mode or a backdrop_picture outside
+ * {0, 1}; every other check is that of mdqe_render_mosaic_u8, made before any pointer is looked at; F == 0 returns OK and launches
+ * nothing; a null matte or backdrop is refused as the labels are.  Nothing needs to be aligned.  One launch, no atomics: identical from
+ * run to run.  Never allocates, never synchronises. */
+int mdqe_render_replace_u8(const void* frames, int is_u8, long frame_stride, int h0, int w0,
+                           const unsigned char* labels, int F, int Ho, int Wo,
+                           const unsigned char* palette, const unsigned char* action, int a256, int contour,
+                           const unsigned char* matte, const unsigned char* backdrop, int backdrop_picture, int mode,
+                           unsigned char* out, int f_off, void* stream);
+/* ... and on decoder surfaces: mdqe_render_mosaic_yuv420sp's arguments without `cell`, plus matte (uint8 [F, H, W]), mode, and the
+ * backdrop as EITHER backdrop_yuv (uint16 [3]: Y, U, V in sample units; only the 8 / 10 bits are used) OR, with backdrop_yuv == NULL,
+ * one surface (by, by_pitch, buv, buv_pitch) of the same H, W and fmt, the same for every frame.  Values are word >> 6 for P010.
+ *   luma    Yout = mix(baseY, BY, Wt) with baseY the rule of mdqe_render_overlay_yuv420sp under the action (1 tints, else the sample);
+ *   chroma  Cout = (sum_i mix(px_i(C), BC, Wt_i) + n / 2) >> log2(n) over the n in-picture pixels i of the pair's 2 x 2 block, px_i(C)
+ *           being C or its tint by pixel i's action, label and edge, BC the colour's component or the backdrop surface's pair of
+ *           that block;
+ *   P010    a word the rule leaves unchanged -- a luma word whose label is kept (action != 1) with Wt == 255, a chroma pair whose whole
+ *           block is such pixels -- is copied with all 16 bits; every other word is written as value << 6 (NV12: the same bytes).
+ * In place is allowed under mdqe_render_overlay_yuv420sp's conditions: every sample is read and written by the thread that owns it.
+ * Any other overlap of an output plane -- with an input plane, the labels, palette, action table, the matte or the backdrop -- is
+ * MDQE_EINVAL, as is a backdrop pitch smaller than a row and (P010) an odd backdrop pointer or pitch.  mode outside {0, 1} is
+ * MDQE_EINVAL before any pointer is looked at.  One launch, single samples at any alignment, no atomics. */
+int mdqe_render_replace_yuv420sp(const void* y, long y_pitch, long y_stride, const void* uv, long uv_pitch, long uv_stride,
+                                 int F, int H, int W, int fmt /*0 nv12, 1 p010*/, const unsigned char* labels,
+                                 const unsigned short* palette_yuv, const unsigned char* action, int a256, int contour,
+                                 const unsigned char* matte, const unsigned short* backdrop_yuv,
+                                 const void* by, long by_pitch, const void* buv, long buv_pitch, int mode,
+                                 void* out_y, long out_y_pitch, long out_y_stride,
+                                 void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream);
 
 /* Track boxes and captions on a painted picture (csrc/annotate.hip): the box and the text plate per instance that the demo's
  * visualiser draws on the host (demo/clip/visualizer.py:162,205; captions "[id] class score%", demo/visualizer.py:72-91).  An

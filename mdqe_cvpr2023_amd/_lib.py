@@ -52,6 +52,9 @@ SIGNATURES = {
     "mdqe_final_masks_rle_geom": [p, i, p, i, i, i, i, i, i, i, i, i, p, p, p, p],
     "mdqe_final_masks_u8_geom": [p, i, p, i, i, i, i, i, i, i, i, p, l, i, p, p],
     "mdqe_final_label_map_u8": [p, i, p, i, i, i, i, i, i, i, i, p, i, p, p],
+    "mdqe_final_matte_u8": [p, i, p, i, i, i, i, i, i, i, i, p, f, p, i, p],
+    "mdqe_render_replace_u8": [p, i, l, i, i, p, i, i, i, p, p, i, i, p, p, i, i, p, i, p],
+    "mdqe_render_replace_yuv420sp": [p, l, l, p, l, l, i, i, i, i, p, p, p, i, i, p, p, p, l, p, l, i, p, l, l, p, l, l, i, p],
     "mdqe_render_overlay_u8": [p, i, l, i, i, p, i, i, i, p, i, i, p, i, p],
     "mdqe_render_overlay_yuv420sp": [p, l, l, p, l, l, i, i, i, i, p, p, i, i, p, l, l, p, l, l, i, p],
     "mdqe_render_mosaic_u8": [p, i, l, i, i, p, i, i, i, p, p, i, i, i, p, i, p],

@@ -1,5 +1,5 @@
 #include "common.h"
-extern "C" int mdqe_version(void) { return 100; }
+extern "C" int mdqe_version(void) { return 101; }
 extern "C" int mdqe_abi_version(void) { return MDQE_ABI_VERSION; }
 extern "C" const char* mdqe_strerror(int code) {
   switch (code) {

@@ -37,6 +37,15 @@ __device__ __forceinline__ int final_mask_pixel(const float* __restrict__ m, int
   return final_mask_bit(final_mask_value(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, Y, X));
 }
 
+// The matte's level 0..255 from x = gain * (the largest up-sampled logit of the participating rows) and U = the OR of their final-mask
+// bits: the rounded sigmoid, held at >= 128 where a bit is set and at <= 127 where none is.  So level >= 128 exactly where U is set,
+// whatever gain is and whatever the last ulp of expf is.  Every form that needs a level calls this.
+__device__ __forceinline__ int final_matte_level(float x, int U) {
+  const float p = 1.f / (1.f + expf(-x));
+  const int a = (int)rintf(255.f * p);
+  return U ? max(a, 128) : min(a, 127);
+}
+
 // ---- host only: what the six entry points of the family share (final_mask.hip, score_ops.hip) ------------------------------------------
 #define MDQE_TRY(e) do { const int rc_ = (e); if (rc_ != MDQE_OK) return rc_; } while (0)
 

@@ -431,3 +431,93 @@ extern "C" int mdqe_final_label_map_u8(const float* logits, int n_sel, const int
 #undef MDQE_LABEL_LAUNCH
   return mdqe_launch_status();
 }
+
+// ------------------------------------------------------------------------------------------------
+// Soft matte: ONE uint8 plane per frame again, but a weight instead of a name -- the rounded sigmoid of gain * (the largest up-sampled
+// logit among the participating rows), final_matte_level: >= 128 exactly where one of their final-mask bits is set, so thresholding the
+// matte at 128 gives the union of those rows' dense masks bit for bit.  Row k takes part iff take == NULL or take[inst_idx[k] + 1] != 0
+// (the row's label, as in the label map).  Shaped like final_mask_band_kernel: a block owns a band of output rows of one frame for all
+// rows, a thread takes 4 consecutive pixels of an output row, final_mask_taps runs once per pixel and the loop over k only reads, blends
+// (final_mask_value_at) and thresholds (final_mask_bit); one expf more per PIXEL for the level.  The participating rows' indices are
+// packed into LDS first (order kept; 256 threads >= n_sel), so a row `take` drops costs nothing in the sweep.  The four levels leave as
+// one dword where the group is whole and its address 4-byte aligned, byte by byte otherwise.  No atomics: identical from run to run.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+final_matte_kernel(const float* __restrict__ lg, int n_sel, int Fw, int Hm, int Wm, int factor, int h, int w, int Ho, int Wo,
+                   unsigned char* __restrict__ out, int f_off, const int* __restrict__ inst_idx, const unsigned char* __restrict__ take,
+                   float gain, int band, int n_bands) {
+  __shared__ int ids[256];
+  __shared__ int wave_rows[4];
+  const int tid = (int)threadIdx.x;
+  bool on = false;
+  int id = 0;
+  if (tid < n_sel) {
+    id = inst_idx[tid];
+    on = take == nullptr || take[(id + 1) & 255] != 0;                // (the table has 256 entries: the index never leaves it)
+  }
+  const unsigned long long votes = __ballot(on);
+  if ((tid & 63) == 0) wave_rows[tid >> 6] = __popcll(votes);
+  __syncthreads();
+  int first = 0, n_part = 0;
+#pragma unroll
+  for (int wv = 0; wv < 4; ++wv) { first += wv < (tid >> 6) ? wave_rows[wv] : 0; n_part += wave_rows[wv]; }
+  if (on) ids[first + __popcll(votes & ((1ull << (tid & 63)) - 1ull))] = id;
+  __syncthreads();
+  const int f = blockIdx.x / n_bands, b = blockIdx.x - f * n_bands;
+  const float sy_scale = (float)h / (float)Ho, sx_scale = (float)w / (float)Wo;
+  const int Y0 = b * band, rows = min(band, Ho - Y0);
+  const long map_stride = (long)Hm * Wm;
+  const int Wg = (Wo + 3) >> 2;                        // groups of 4 pixels per output row
+  const int ngrp = rows * Wg;
+  unsigned char* o = out + ((long)(f_off + f) * Ho + Y0) * Wo;
+  for (int i = tid; i < ngrp; i += 256) {
+    const int y = i / Wg, X0 = (i - y * Wg) << 2, Y = Y0 + y;
+    const int nx = min(4, Wo - X0);                    // pixels of the group inside the row
+    MaskTaps t[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) t[j] = final_mask_taps(Hm, Wm, factor, h, w, sy_scale, sx_scale, Y, min(X0 + j, Wo - 1));
+    float vmax[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    int U[4] = {0, 0, 0, 0};
+    for (int k = 0; k < n_part; ++k) {
+      const float* m = lg + ((long)ids[k] * Fw + f) * map_stride;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float v = final_mask_value_at(m, Wm, t[j]);
+        U[j] |= final_mask_bit(v);
+        vmax[j] = v > vmax[j] ? v : vmax[j];
+      }
+    }
+    unsigned int lv = 0;
+    if (n_part > 0) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) lv |= (unsigned int)final_matte_level(gain * vmax[j], U[j]) << (8 * j);
+    }
+    unsigned char* p = o + (long)y * Wo + X0;
+    if (nx == 4 && (reinterpret_cast<unsigned long>(p) & 3) == 0) {
+      *reinterpret_cast<unsigned int*>(p) = lv;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < nx) p[j] = (unsigned char)(lv >> (8 * j));
+    }
+  }
+}
+
+extern "C" int mdqe_final_matte_u8(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
+                                   int h, int w, int Ho, int Wo, const unsigned char* take, float gain, unsigned char* out, int f_off,
+                                   void* stream) {
+  MDQE_TRY(final_mask_args(n_sel, Fw, Hm, Wm, factor, h, w, Ho, Wo));
+  MDQE_REQUIRE(n_sel <= 255 && f_off >= 0 && (long)Ho * Wo < 0x7FFFFFFFL && (long)Hm * Wm < 0x7FFFFFFFL);
+  MDQE_REQUIRE(gain > 0.f && gain <= 64.f);                           // (false for a NaN)
+  if (Fw == 0) return MDQE_OK;
+  MDQE_CHECK_PTR(out);
+  if (n_sel > 0) { MDQE_CHECK_PTR(logits); MDQE_CHECK_PTR(inst_idx_dev); }
+  // bands per frame as the label map's: about 8 blocks of 256 threads per CU over the window, at least ~1024 pixels a block
+  const int band = final_mask_band(2048, Fw, Ho, Wo);
+  const int n_bands = (Ho + band - 1) / band;
+  MDQE_REQUIRE((long)Fw * n_bands < 0x7FFFFFFFL && (long)band * ((Wo + 3) / 4) < 0x7FFFFFFFL);
+  mdqe_clear_error();
+  hipLaunchKernelGGL(final_matte_kernel, dim3((unsigned)(Fw * n_bands)), dim3(256), 0, (hipStream_t)stream, logits, n_sel, Fw, Hm, Wm,
+                     factor, h, w, Ho, Wo, out, f_off, inst_idx_dev, take, gain, band, n_bands);
+  return mdqe_launch_status();
+}

@@ -33,13 +33,14 @@ class Forms:
     surface: bool = False                 # the overlay is painted onto the decoder surfaces handed in: a YuvFrames, not RGB pixels
     crops: bool = False                   # per-track chips cut from the frames (render.Crops; the map and its table: a device scratch if not returned)
     paths: bool = False                   # per-track centroids and moments of the map's visible regions (PathTable; the map: a device scratch if not returned)
+    matte: bool = False                   # the soft matte of the window's tracks, one uint8 plane per frame (render.Matte), beside any other form
 
     @classmethod
-    def _of(cls, model, geometry, planes, labels, overlay, early_always=False, surface=False, crops=False, paths=False):
+    def _of(cls, model, geometry, planes, labels, overlay, early_always=False, surface=False, crops=False, paths=False, matte=False):
         """geometry None: the model's flag.  It describes the planes where there are planes, and the labels' regions where the map is returned."""
         g = bool(getattr(model, "geometry_output", False) if geometry is None else geometry)
         return cls(planes, labels, overlay, g and planes is not None, g and labels, early_always, bool(overlay and surface), bool(crops),
-                   bool(paths))
+                   bool(paths), bool(matte))
 
     @classmethod
     def of_model(cls, model, emit_masks=True, geometry=None):
@@ -49,15 +50,16 @@ class Forms:
         lab, rle = getattr(model, "label_output", False), bool(getattr(model, "rle_output", False))
         pic = getattr(model, "overlay_output", False)
         return cls._of(model, geometry, None if lab == "only" else "rle" if rle else "dense", bool(lab), bool(pic), rle, pic == "surface",
-                       getattr(model, "crop_output", None) is not None, bool(getattr(model, "path_output", False)))
+                       getattr(model, "crop_output", None) is not None, bool(getattr(model, "path_output", False)),
+                       getattr(model, "matte_output", None) is not None)
 
     @classmethod
-    def of_emit(cls, emit, geometry=False, model=None, surface=False, crops=False, paths=False):
+    def of_emit(cls, emit, geometry=False, model=None, surface=False, crops=False, paths=False, matte=False):
         """Online ("masks" | "rle" | "labels" | "overlay"; surface: the overlay onto the surfaces pushed; crops: chips beside it; paths:
         centroids and moments beside it)."""
         lab = emit in ("labels", "overlay")
         return cls._of(model, geometry, None if lab else {"masks": "dense", "rle": "rle"}[emit], lab, emit == "overlay", surface=surface,
-                       crops=crops, paths=paths)
+                       crops=crops, paths=paths, matte=matte)
 
 
 def dense_masks(m, idx, stride, frame_hw, out_size, geometry, out, f_off):
@@ -228,7 +230,10 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
     ops.render_overlay_yuv launch per piece, with the palette in the surfaces' samples.  A style with a mosaic (style.mosaic): the
     same launches of ops.render_mosaic / ops.render_mosaic_yuv with the style's action table; `cls`, the window's class rows [n, K]
     on the host, is what a style with `classes` builds that table from.  A style with a blur (style.blur): the same launches of
-    ops.render_blur / ops.render_blur_yuv with that table and the style's tap tables (style.taps_on, style.taps_c_on).  A style that annotates (style.annotates: track boxes,
+    ops.render_blur / ops.render_blur_yuv with that table and the style's tap tables (style.taps_on, style.taps_c_on).  A style that
+    replaces (style.replace): behind the label map one ops.final_matte launch sweeps the same logits into a device scratch [F, Ho, Wo]
+    -- the matte of the rows the style's `takes` table selects, with the style's matte_gain -- and the painter launches are
+    ops.render_replace / ops.render_replace_yuv with that matte and the style's backdrop (a backdrop picture must have the output's size).  A style that annotates (style.annotates: track boxes,
     captions) takes the geometry table from `label_maps` whether or not `geometry` asks for it and, behind the painter launches, runs
     one ops.annotate / ops.annotate_yuv launch per piece in place on the painted frames, on the same stream, with the captions made
     from `cls`; nothing is read back.  `paths` (a PathTable whose `begin` has been called for this window): the window's centroids are
@@ -243,14 +248,22 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
         paths.run(labels, l_off)
     surface = not torch.is_tensor(out)
     pal = style.palette_yuv_on(m.device, *out.meta()[2:]) if surface else style.palette_on(m.device)
-    act = style.actions_on(m.device, cls) if style.mosaic is not None or style.blur is not None else None
+    act = style.actions_on(m.device, cls) if style.mosaic is not None or style.blur is not None or style.replace is not None else None
+    matte = back = None
+    if style.replace is not None:
+        matte = replace_matte(m, stride, frame_hw, out_size, style, cls)
+        back = style.backdrop_yuv_on(m.device, *out.meta()[2:]) if surface else style.backdrop_on(m.device)
     taps = style.taps_on(m.device) if style.blur is not None else None
     taps_c = style.taps_c_on(m.device) if taps is not None and surface else None
     pieces = source.pieces(int(f0), int(f0) + nf, stream=torch.cuda.current_stream(m.device))
     for t, first in pieces:
         k, d = len(t), first - int(f0)
         lab = labels[l_off + d:l_off + d + k]
-        if taps is not None and surface:
+        if matte is not None and surface:
+            ops.render_replace_yuv(lab, t, pal, act, matte[d:d + k], back, out, o_off + d, style.a256, style.contour, style.replace)
+        elif matte is not None:
+            ops.render_replace(lab, t, pal, act, matte[d:d + k], back, out, o_off + d, style.a256, style.contour, style.replace)
+        elif taps is not None and surface:
             ops.render_blur_yuv(lab, t, pal, act, taps, taps_c, out, o_off + d, style.a256, style.contour)
         elif taps is not None:
             ops.render_blur(lab, t, pal, act, taps, out, o_off + d, style.a256, style.contour)
@@ -278,6 +291,42 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
             (ops.annotate_yuv if surface else ops.annotate)(out, g, n, pal, ink, text, font, o_off + d, style.box, style.text_scale,
                                                             style.min_area)
     return geom if geometry else None
+
+
+def check_replace(style, out_size, surface):
+    """What a replace style cannot be painted with, refused with the remedy (a ClipMerger asks before the first clip runs).  surface:
+    False, True, or the surfaces' format where it is known."""
+    from .preprocess import YuvFrames
+    Ho, Wo = (int(v) for v in out_size)
+    b = style.backdrop
+    if isinstance(b, YuvFrames):
+        if not surface:
+            raise ValueError("overlay style: the backdrop is a YuvFrames surface but the session paints RGB pictures; give a uint8 "
+                             "tensor [Ho, Wo, 3] or three ints, or run the session with surface=True")
+        if (b.height, b.width) != (Ho, Wo) or (isinstance(surface, str) and b.fmt != surface):
+            raise ValueError("overlay style: the backdrop surface is %d x %d %s but the output is %d x %d%s; resize the picture to the "
+                             "output's size (height, width) and convert it to the session's format"
+                             % (b.height, b.width, b.fmt, Ho, Wo, " " + surface if isinstance(surface, str) else ""))
+    elif torch.is_tensor(b):
+        if surface:
+            raise ValueError("overlay style: the backdrop is an RGB picture but the session paints decoder surfaces; give a "
+                             "preprocess.YuvFrames of one surface of the session's kind or three ints, or run the session with surface=False")
+        if tuple(b.shape[:2]) != (Ho, Wo):
+            raise ValueError("overlay style: the backdrop picture is %d x %d but the output is %d x %d; resize the picture to the output's "
+                             "size (height, width)" % (b.shape[0], b.shape[1], Ho, Wo))
+
+
+def replace_matte(m, stride, frame_hw, out_size, style, cls):
+    """The matte a replace style composites with: of window logits m [n, F, Hm, Wm], the rows `style.takes` selects (`cls`: the window's
+    class rows on the host, for a style with `classes`), with style.matte_gain, into a fresh device scratch uint8 [F, Ho, Wo] on the
+    current stream (ops.final_matte: one more sweep of the logits the label map was made from).  What the style cannot be painted with
+    was refused when the merger was made (`check_replace`)."""
+    from . import ops
+    (fh, fw), (Ho, Wo) = frame_hw, out_size
+    n, nf = int(m.shape[0]), int(m.shape[1])
+    idx = torch.arange(n, dtype=torch.int32, device=m.device)
+    matte = torch.empty((nf, Ho, Wo), dtype=torch.uint8, device=m.device)
+    return ops.final_matte(m, idx, stride, fh, fw, Ho, Wo, matte, 0, style.takes_on(m.device, cls), style.matte_gain)
 
 
 def crop_frames(n, nf, labels, l_off, geom, source, f0, spec, out, rects, c_off):
@@ -463,8 +512,19 @@ def rle_positions(m, idx, stride, frame_hw, out_size, geometry):
     return pos[:, :max(mx, 1)].cpu().numpy(), n_pos.cpu().numpy(), geom.view(int(idx.numel()), int(m.shape[1]), 5).cpu() if geometry else None
 
 
+def matte_planes(m, stride, frame_hw, out_size, spec, cls, out, f_off):
+    """The matte output of window logits m [n, F, Hm, Wm] into out[f_off:f_off + F] (uint8 [>= f_off + F, Ho, Wo], device): the union
+    matte of ALL n rows, or with spec.classes (render.Matte) of the rows those classes select by the window's class rows `cls`; n = 0:
+    zeros (ops.final_matte)."""
+    from . import ops
+    (fh, fw), (Ho, Wo) = frame_hw, out_size
+    idx = torch.arange(int(m.shape[0]), dtype=torch.int32, device=m.device)
+    take = spec.takes(cls)
+    ops.final_matte(m, idx, stride, fh, fw, Ho, Wo, out, f_off, None if take is None else take.to(m.device), spec.gain)
+
+
 def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels=None, picture=None, paint=None,
-                 hop=lambda stage, geom: geom, crops=None, paths=None):
+                 hop=lambda stage, geom: geom, crops=None, paths=None, matte=None):
     """What `forms` asks for of ONE flushed window (logits m [n, F, Hm, Wm]), on the current stream, for every path; the only caller
     of `overlay_frames`, `label_maps`, `dense_masks` and `rle_positions`.  First the label map of ALL n rows into labels = (device
     buffer, frame offset) and, with picture = (buffer, offset), its overlay, painted from paint = (FrameStore, first video frame,
@@ -475,6 +535,7 @@ def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels
     chips (`crop_frames`) from the map and its table, which are then made whether or not `forms` returns them.
     paths (a PathTable, `begin` called for this window): behind the label map the window's centroids (`PathTable.run`), which the
     overlay's trail pass draws and, with forms.paths, the stage "paths" sends on; the map is then made whether or not it is returned.
+    matte = (render.Matte, the window's class rows on the host, buffer, offset): the window's matte (`matte_planes`), stage "matte".
     -> (labels' geometry table [n, F, 5] or None, planes' table [len(rows), F, 5] or None, (pos, n_pos) of `rle_positions` or None)."""
     lgeom = pgeom = runs = None
     if labels is not None:
@@ -492,6 +553,9 @@ def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels
             spec, source, f0, chips, rects, c_off = crops
             crop_frames(int(m.shape[0]), int(m.shape[1]), *labels, dgeom, source, f0, spec, chips, rects, c_off)
             hop("crops", None)
+    if matte is not None:
+        matte_planes(m, stride, frame_hw, out_size, *matte)
+        hop("matte", None)
     if rows is not None and int(rows.numel()):
         if planes is not None:
             pgeom = hop("planes", dense_masks(m, rows, stride, frame_hw, out_size, forms.plane_geometry, *planes))
@@ -583,6 +647,7 @@ class EarlyMasks:
     labels: object = None                                             # label map: ONE pinned uint8 [L, Ho, Wo] per video (model.label_output)
     label_geom: list = dataclasses.field(default_factory=list)        # per window, as `geom`, of the labels' visible regions
     overlay: object = None                                            # overlay: ONE pinned uint8 [L, Ho, Wo, 3] per video (model.overlay_output)
+    matte: object = None                                              # matte: ONE pinned uint8 [L, Ho, Wo] per video (model.matte_output)
 
 
 def result_head(model, cls_clips, out_size, n_frames, score=None, track_ids=True):
@@ -628,7 +693,7 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
                                                                               for f, nf, n, pos, n_pos in early.rle])}
         elif forms.planes:
             planes_res = {"pred_masks": [early.hosts[i].view(torch.bool)[:n_frames] for i in inst]}
-        host = {"labels": early.labels, "overlay": early.overlay}
+        host = {"labels": early.labels, "overlay": early.overlay, "matte": early.matte}
     else:
         sel = sorted(set(inst))
         rows = [sel.index(i) for i in inst]                        # rows of the planes' buffer = positions in sel
@@ -642,6 +707,7 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
         if forms.surface:
             d_pic = surface_picture(frame_source, n_frames, out_size, model.device)
         d_planes = torch.zeros(len(sel), n_frames, Ho, Wo, **u8) if forms.planes else None
+        d_mat = torch.empty(n_frames, Ho, Wo, **u8) if forms.matte else None
         sel_dev = torch.tensor(sel, dtype=torch.int32, device=model.device) if forms.planes else None
         for i, (f_off, m) in enumerate(windows):
             n, nf = int(m.shape[0]), int(m.shape[1])
@@ -652,14 +718,14 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
             lg, pg, _ = build_window(m, forms, sel_dev[:cnt] if forms.planes else None, model.cfg.match_stride, frame_hw, out_size, *at,
                                      paint=(frame_source, f_off, model.overlay_style, cls_clips[i]) if forms.overlay else None,
                                      crops=(crops.spec, frame_source, f_off, *crops.rows(n), crops.spec.count(f_off)) if forms.crops else None,
-                                     paths=paths)
+                                     paths=paths, matte=(model.matte_output, cls_clips[i], d_mat, f_off) if forms.matte else None)
             if paths is not None:
                 paths.keep(f_off)
             label_geoms.append((f_off, nf, n, lg))
             if cnt:
                 plane_geoms.append((f_off, nf, cnt, pg))
         # one D2H each into pinned memory (pageable copies run at a fraction of PCIe), one sync behind them
-        for k, t in (("overlay", d_pic), ("labels", d_lab if forms.labels else None), ("planes", d_planes)):
+        for k, t in (("overlay", d_pic), ("labels", d_lab if forms.labels else None), ("planes", d_planes), ("matte", d_mat)):
             if t is not None and not torch.is_tensor(t):           # a surface picture: both planes
                 host[k] = surface_picture(frame_source, n_frames, out_size, "cpu", pin_memory=True)
                 host[k].y.copy_(t.y, non_blocking=True)
@@ -678,8 +744,10 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
                 planes_res = {"pred_rles": [enc[p] for p in rows]}
             else:
                 planes_res = {"pred_masks": [planes[p] for p in rows]}
-    if forms.labels or forms.overlay or forms.crops or forms.paths:
+    if forms.labels or forms.overlay or forms.crops or forms.paths or forms.matte:
         res.setdefault("pred_track_ids", list(inst))
+    if forms.matte:
+        res["pred_matte"] = host["matte"][:n_frames]
     if forms.crops:
         res.update(crops.result(inst))
     if forms.paths:
@@ -705,7 +773,7 @@ class ClipMerger:
     EARLY_TRACKS = 48                       # tracks per video the early-mask path budgets pinned memory for
 
     def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True, online=None, geometry=None, frame_source=None,
-                 style=None, ground_truth=None, surface=False, surface_pitch_align=1, crops=None, paths=False):
+                 style=None, ground_truth=None, surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None):
         self.model, self.frame_hw, self.out_size, self.mask_hw = model, frame_hw, out_size, mask_hw
         self.emit_masks = emit_masks                # False: scores / labels only (ranks > 0 of a sharded video)
         # online ("masks" | "rle" | "labels" | "overlay"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their
@@ -717,7 +785,9 @@ class ClipMerger:
         # crops (render.Crops): an online session's; offline the model's crop_output
         self.crop_spec = crops if online else (getattr(model, "crop_output", None) if emit_masks else None)
         # paths: an online session's; offline the model's path_output
-        self.forms = forms = (Forms.of_emit(online, geometry, model, surface, self.crop_spec is not None, bool(paths)) if online
+        # matte (render.Matte): an online session's; offline the model's matte_output
+        self.matte_spec = matte if online else (getattr(model, "matte_output", None) if emit_masks else None)
+        self.forms = forms = (Forms.of_emit(online, geometry, model, surface, self.crop_spec is not None, bool(paths), matte is not None) if online
                               else Forms.of_model(model, emit_masks, geometry))
         self.crop_table = None                      # the early path's CropTable, from its first window
         self.path_table = None                      # the early and the online path's PathTable, from their first window
@@ -734,6 +804,8 @@ class ClipMerger:
         if forms.overlay and frame_source is None:
             raise ValueError("overlay output needs the frames of the whole video on this device; this path does not hold them (the sharded "
                              "driver does not offer it: rank 0 does not hold every frame)")
+        if forms.overlay and self.style is not None and self.style.replace is not None:
+            check_replace(self.style, out_size, forms.surface)
         # a vis_score.GroundTruth: every flushed window's final masks are counted against it (OverlapTables); None: nothing is
         self.score = None
         if ground_truth is not None:
@@ -850,8 +922,10 @@ class ClipMerger:
             pic = surface_picture(self.frame_source, nf, self.out_size, self.dev, self.surface_pitch_align)
         rows = torch.arange(n, dtype=torch.int32, device=self.dev) if n and forms.planes else None
         planes = torch.empty(n, nf, Ho, Wo, **u8) if rows is not None and forms.planes == "dense" else None
+        mat = torch.empty(nf, Ho, Wo, **u8) if forms.matte else None
         copies = {"labels": (pairs("labels", lab) if forms.labels else []) + (pairs("overlay", pic) if forms.overlay else []),
-                  "planes": pairs("planes", planes) if planes is not None else [], "crops": [], "paths": []}
+                  "planes": pairs("planes", planes) if planes is not None else [], "crops": [], "paths": [],
+                  "matte": pairs("matte", mat) if mat is not None else []}
         crop = None
         if forms.crops:
             spec = self.crop_spec
@@ -868,7 +942,7 @@ class ClipMerger:
         # (the copy stream is created BEFORE the window's kernels are launched, and only by a window that copies, as ever: the order
         # streams are first used in decides their queues)
         sends_paths = bool(forms.paths and self.online and n)        # (offline the windows' tables wait on the device: PathTable.keep)
-        cs = copy_stream(self.model) if copies["labels"] or copies["planes"] or copies["crops"] or sends_paths else None
+        cs = copy_stream(self.model) if copies["labels"] or copies["planes"] or copies["crops"] or copies["matte"] or sends_paths else None
         if self.path_table is None:
             self.path_table = path_table(forms, self.style, self.dev, keep=forms.paths and not self.online)
         if self.path_table is not None:
@@ -878,6 +952,7 @@ class ClipMerger:
         at = [None if t is None else (t, 0) for t in (planes, lab, pic)]
         out = build_window(m, forms, rows, self.model.cfg.match_stride, self.frame_hw, self.out_size, *at,
                            paint=(self.frame_source, self.f_off, self.style, c), crops=crop, paths=self.path_table,
+                           matte=(self.matte_spec, c, mat, 0) if mat is not None else None,
                            hop=lambda stage, geom: (to_host(cs, self.side, copies[stage], geom, event())
                                                     if copies[stage] or geom is not None else None))   # (a scratch stage: nothing to send)
         if self.path_table is not None:

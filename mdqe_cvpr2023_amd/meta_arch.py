@@ -316,6 +316,24 @@ class MDQE(nn.Module):
         self.__dict__["_crop_output"] = value
 
     @property
+    def matte_output(self):
+        """None, or a render.Matte: forward() on a video adds "pred_matte" (uint8 [L, Ho, Wo], pinned host: per frame the soft matte of
+        the window's tracks -- of the spec's classes, by the window's class rows -- rint(255 * sigmoid(gain * the largest up-sampled
+        logit)), >= 128 exactly on the union of their final masks, ops.final_matte) and "pred_track_ids".  Beside every other output
+        form, on both mask paths; the bits of the other outputs are left alone.  Videos only, one device (sharding.py refuses it).
+        None: nothing changes."""
+        return self.__dict__.get("_matte_output", None)
+
+    @matte_output.setter
+    def matte_output(self, value):
+        from .render import Matte
+        if value is not None and not isinstance(value, Matte):
+            raise ValueError("matte_output must be None or a render.Matte, got %r" % (value,))
+        if value is not None:
+            self.check_label_capacity()
+        self.__dict__["_matte_output"] = value
+
+    @property
     def path_output(self):
         """False or True: forward() on a video adds "pred_centroids" (int32 [n_out, L, 2]: per output and frame the centroid (x, y) of
         the track's visible region of the label map, ((SX + m/2) / m, (SY + m/2) / m) in integers, ops.label_centroids; (-1, -1) where
@@ -1074,7 +1092,7 @@ class MDQE(nn.Module):
             yield guarded(step)
 
     def online_video(self, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None,
-                     surface=False, surface_pitch_align=1, crops=None, paths=False):
+                     surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None):
         """An online session over ONE video whose frames arrive in pushes (a camera, a stream, a video too long to hold): push()
         returns each tracker window as soon as it is final, close() the rest, result() the video-level scores / labels / tracks.
         height / width: output mask size (default: the frame size); emit: "masks" (bool [n, F, H, W] per window), "rle" or "labels" (one
@@ -1088,10 +1106,11 @@ class MDQE(nn.Module):
         rounded up to a multiple of it); crops (render.Crops, beside any emit): every window carries `crops` / `crop_rects` /
         `crop_frames`, one fixed-size picture per track and taken frame (`crop_output`'s); paths (a bool, beside any emit): every
         window carries `centroids` / `moments` of its tracks' visible regions and, with keep, result() "pred_centroids" /
-        "pred_moments" (`path_output`'s).  See online.py."""
+        "pred_moments" (`path_output`'s); matte (render.Matte, beside any emit): every window carries `matte`, uint8 [F, H, W], the soft
+        matte of its tracks, and with keep result() "pred_matte" (`matte_output`'s).  See online.py."""
         from .online import OnlineVideo
         return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep, geometry=geometry, style=style, ground_truth=ground_truth,
-                           surface=surface, surface_pitch_align=surface_pitch_align, crops=crops, paths=paths)
+                           surface=surface, surface_pitch_align=surface_pitch_align, crops=crops, paths=paths, matte=matte)
 
     def inference_image(self, batched_inputs):
         """COCO single-image branch: MDQE.forward :213-236 -> mdqe.forward (models/mdqe.py:62-70) -> decoder
@@ -1111,6 +1130,9 @@ class MDQE(nn.Module):
         if getattr(self, "crop_output", None) is not None:
             raise ValueError("crop_output: the COCO image branch has no crops (per-track crops are a video output: use a video config, or "
                              "set crop_output = None)")
+        if getattr(self, "matte_output", None) is not None:
+            raise ValueError("matte_output: the COCO image branch has no matte (the soft matte is a video output: use a video config, or "
+                             "set matte_output = None)")
         if getattr(self, "path_output", False):
             raise ValueError("path_output: the COCO image branch has no paths (track centroids are a video output: use a video config, or "
                              "set path_output = False)")

@@ -58,6 +58,10 @@ device scratch where the emit does not return them), and the session keeps the p
 whatever the emit.  keep=True adds "pred_crops" / "pred_crop_rects" / "pred_crop_frames" to result(), equal to forward()'s with
 model.crop_output.
 
+matte=render.Matte(classes=None, gain=1.0), beside ANY emit: every window also carries `win.matte`, uint8 [F, H, W] on pinned host, the
+soft matte of its tracks (with `classes`: of the tracks those classes select by the window's class rows) from one more sweep of the
+window's logits (ops.final_matte): >= 128 exactly on the union of their masks.  keep=True adds "pred_matte" [L, H, W] to result(),
+equal to forward()'s with model.matte_output.
 paths=True, beside ANY emit: every window also carries where its tracks are -- `win.centroids` int32 [n, F, 2] (pinned host: (x, y) of
 the track's visible region of the label map, ((SX + m/2) / m, (SY + m/2) / m) in integers, (-1, -1) where it has none) and
 `win.moments` int64 [n, F, 3] = (m, SX, SY) -- summed on the device from the label map (ops.label_centroids; the map is then made for
@@ -154,7 +158,8 @@ class Window:
     dataclasses.fields(Window) is what it was.)  In a session with crops=: `crops` uint8 [n, Fc, Sh, Sw, 3], `crop_rects` int32 [n, Fc, 4]
     and `crop_frames`, the Fc video frames taken (pseudo-fields of the same kind).  In a session with paths=True: `centroids` int32 [n,
     f1-f0, 2], (x, y) of each track's visible region of the label map per frame, (-1, -1) where it has none, and `moments` int64 [n,
-    f1-f0, 3], its (pixels, sum of X, sum of Y) (pseudo-fields of the same kind)."""
+    f1-f0, 3], its (pixels, sum of X, sum of Y) (pseudo-fields of the same kind).  In a session with matte=: `matte` uint8 [f1-f0, H, W]
+    on pinned host, the soft matte of the window's tracks (render.Matte; a pseudo-field of the same kind)."""
     frames: tuple
     track_ids: list
     cls_probs: torch.Tensor
@@ -169,8 +174,10 @@ class Window:
     crop_frames: dataclasses.InitVar[list] = None
     centroids: dataclasses.InitVar[torch.Tensor] = None
     moments: dataclasses.InitVar[torch.Tensor] = None
+    matte: dataclasses.InitVar[torch.Tensor] = None
 
-    def __post_init__(self, labels, overlay, crops, crop_rects, crop_frames, centroids, moments):
+    def __post_init__(self, labels, overlay, crops, crop_rects, crop_frames, centroids, moments, matte):
+        self.matte = matte
         self.labels = labels
         self.overlay = overlay
         self.crops, self.crop_rects, self.crop_frames = crops, crop_rects, crop_frames
@@ -179,7 +186,7 @@ class Window:
 
 class OnlineVideo:
     def __init__(self, model, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None,
-                 surface=False, surface_pitch_align=1, crops=None, paths=False):
+                 surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None):
         if emit not in ("masks", "rle", "labels", "overlay"):
             raise ValueError("online_video: emit must be 'masks', 'rle', 'labels' or 'overlay'")
         if not isinstance(surface, bool):
@@ -204,7 +211,14 @@ class OnlineVideo:
         if paths and model.cfg.is_coco:
             raise ValueError("online_video: paths with a COCO image config: track centroids are a video output (use a video config)")
         self.paths = paths
-        if emit in ("labels", "overlay") or crops is not None or paths:
+        if matte is not None:
+            from .render import Matte
+            if not isinstance(matte, Matte):
+                raise ValueError("online_video: matte must be a render.Matte, got %s" % type(matte).__name__)
+            if model.cfg.is_coco:
+                raise ValueError("online_video: matte with a COCO image config: the soft matte is a video output (use a video config)")
+        self.matte = matte
+        if emit in ("labels", "overlay") or crops is not None or paths or matte is not None:
             model.check_label_capacity()
         from .render import Style
         if style is not None and (emit != "overlay" or not isinstance(style, Style)):
@@ -271,7 +285,8 @@ class OnlineVideo:
             self.store = FrameStore()
         self.merger = ClipMerger(model, self.hw, self.out_size, self.mask_hw, n_frames=None, online=self.emit,
                                  geometry=self.geometry, frame_source=self.store, style=self.style, ground_truth=self.ground_truth,
-                                 surface=self.surface, surface_pitch_align=self.surface_pitch_align, crops=self.crops, paths=self.paths)
+                                 surface=self.surface, surface_pitch_align=self.surface_pitch_align, crops=self.crops, paths=self.paths,
+                                 matte=self.matte)
         shapes = model.engine.cache_shapes(self.geo)
         per_frame = 4 * sum(int(np.prod(sh)) for sh in shapes.values())
         forced = int(os.environ.get("MDQE_CACHE_FRAMES", "0"))
@@ -304,7 +319,8 @@ class OnlineVideo:
             out.append(Window(frames=r["frames"], track_ids=list(range(n)), cls_probs=r["cls_probs"],
                               masks=r.get("masks"), rles=r.get("rles"), boxes=boxes, areas=areas, labels=r.get("labels"),
                               overlay=r.get("overlay"), crops=r.get("crops"), crop_rects=r.get("crop_rects"),
-                              crop_frames=r.get("crop_frames"), centroids=r.get("centroids"), moments=r.get("moments")))
+                              crop_frames=r.get("crop_frames"), centroids=r.get("centroids"), moments=r.get("moments"),
+                              matte=r.get("matte")))
         del self.merger.emitted[:]
         if self.store is not None:
             # the chunks that lie wholly before the first frame no window has emitted are done with; what stays and may be the caller's
@@ -417,6 +433,8 @@ class OnlineVideo:
                                     lambda k, e=empty: e.expand((k,) + tuple(e.shape)), torch.cat)
                 res[key] = torch.stack(rows) if rows else torch.zeros((0, lc) + tuple(empty.shape), dtype=empty.dtype)
             res["pred_crop_frames"] = spec.taken(0, self.received)
+        if self.keep and forms.matte:             # (the windows tile the video: their planes in a row)
+            res["pred_matte"] = torch.cat([w.matte for w in self.kept])
         if self.keep and forms.paths:             # (per output the track's path; absent before its first window)
             res.update(merge.path_result(inst, self.received, [(w.frames[0], w.frames[1] - w.frames[0], len(w.track_ids), w.centroids, w.moments)
                                                                for w in self.kept]))

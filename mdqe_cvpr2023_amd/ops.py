@@ -626,6 +626,35 @@ def final_label_map(logits, inst_idx, factor, h, w, Ho, Wo, out, f_off, geom=Non
     return out, geom
 
 
+def final_matte(logits, inst_idx, factor, h, w, Ho, Wo, out, f_off, take=None, gain=1.0):
+    """The soft form of `final_label_map`: out[f_off + f] (uint8 [>= f_off + Fw, Ho, Wo], CUDA, contiguous) = the matte of the rows
+    `inst_idx` (int32 CUDA [n_sel]) of logits [n <= 255, Fw, Hm, Wm] that take part -- all of them, or with `take` (uint8 CUDA [256],
+    indexed by the row's label inst_idx[k] + 1) those whose entry is not 0: rint(255 * sigmoid(gain * the largest up-sampled logit
+    among them)), held at >= 128 where one of their final-mask bits is set and at <= 127 where none is, 0 without a participating
+    row.  So out >= 128 exactly on the union of those rows' dense masks.  gain in (0, 64] sharpens (> 1) or softens (< 1) the edge:
+    the rule of include/mdqe_hip.h, mdqe_final_matte_u8.  n_sel == 0 writes zeros to the Fw frames.  -> out."""
+    # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
+    if not torch.is_tensor(logits) or logits.dim() != 4 or int(logits.shape[0]) > 255:
+        raise RuntimeError("final_matte: logits must be [n <= 255, Fw, Hm, Wm], got %s" % (tuple(getattr(logits, "shape", ())),))
+    if not torch.is_tensor(inst_idx) or inst_idx.dtype != torch.int32 or inst_idx.dim() != 1:
+        raise RuntimeError("final_matte: inst_idx must be int32 [n_sel]")
+    if isinstance(gain, bool) or not isinstance(gain, (int, float)) or not 0.0 < float(gain) <= 64.0:
+        raise RuntimeError("final_matte: gain must be a finite number in (0, 64], got %r" % (gain,))
+    if take is not None and (not torch.is_tensor(take) or take.dtype != torch.uint8 or tuple(take.shape) != (256,) or not take.is_contiguous()):
+        raise RuntimeError("final_matte: take must be contiguous uint8 [256] (render.Style.takes) or None")
+    Fw = int(logits.shape[1])
+    if (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 3 or tuple(out.shape[1:]) != (Ho, Wo)
+            or not isinstance(f_off, int) or f_off < 0 or f_off + Fw > out.shape[0] or not out.is_contiguous()):
+        raise RuntimeError("final_matte: out must be contiguous CUDA uint8 [>= f_off + Fw = %d, Ho, Wo]" % (f_off + Fw))
+    for name, t in (("out", out), ("take", take)):
+        if t is not None and (not t.is_cuda or t.device != logits.device):
+            raise RuntimeError("final_matte: %s must be a CUDA tensor on the logits' device, got %s" % (name, t.device))
+    k, Fw, Hm, Wm = _final_mask_args(logits, inst_idx, True)
+    check(lib.mdqe_final_matte_u8(ptr(logits), k, ptr(inst_idx), Fw, Hm, Wm, factor, h, w, Ho, Wo, ptr(take), float(gain), ptr(out), f_off,
+                                  cur_stream()), "final_matte")
+    return out
+
+
 def final_masks_overlap(logits, inst_idx, factor, h, w, Ho, Wo, gt_bits, G, f_off, inter, area=None):
     """A window's final masks scored against ground truth on the device (vis_score.py): for the rows `inst_idx` (int32 CUDA [n_sel]) of
     logits [n, Fw, Hm, Wm], with b_k the final-mask bit of row k (ops.final_masks' own bit), inter[k, g] (int64 CUDA [>= n_sel, >= G],
@@ -678,9 +707,21 @@ def _blur_args(name, action, taps, taps_c=None, surface=False):
             raise RuntimeError("%s: %s must be contiguous uint16 [radius + 1], radius in 0..%d (render.blur_taps)" % (name, what, top))
 
 
-def _rgb_paint_args(name, labels, frames, palette, out, f_off, a256, contour, mosaic=None, blur=None):
-    """The checks of render_overlay, of render_mosaic (mosaic = (action, cell)) and of render_blur (blur = (action, taps)).
-    -> (F, Ho, Wo, h0, w0, frame stride)."""
+def _replace_args(name, action, matte, backdrop, F, H, W):
+    """The action table, the matte and an RGB backdrop of the compositing painter."""
+    if not torch.is_tensor(action) or action.dtype != torch.uint8 or tuple(action.shape) != (256,) or not action.is_contiguous():
+        raise RuntimeError("%s: action must be contiguous uint8 [256] (render.Style.actions)" % name)
+    if not torch.is_tensor(matte) or matte.dtype != torch.uint8 or tuple(matte.shape) != (F, H, W) or not matte.is_contiguous():
+        raise RuntimeError("%s: matte must be contiguous uint8 [F = %d, %d, %d], the labels' shape (ops.final_matte)" % (name, F, H, W))
+    if (not torch.is_tensor(backdrop) or backdrop.dtype != torch.uint8 or tuple(backdrop.shape) not in ((3,), (H, W, 3))
+            or not backdrop.is_contiguous()):
+        raise RuntimeError("%s: backdrop must be contiguous uint8 [3] (a colour) or [%d, %d, 3] (a picture of the output's size), got %s"
+                           % (name, H, W, tuple(getattr(backdrop, "shape", ()))))
+
+
+def _rgb_paint_args(name, labels, frames, palette, out, f_off, a256, contour, mosaic=None, blur=None, replace=None):
+    """The checks of render_overlay, of render_mosaic (mosaic = (action, cell)), of render_blur (blur = (action, taps)) and of
+    render_replace (replace = (action, matte, backdrop)).  -> (F, Ho, Wo, h0, w0, frame stride)."""
     # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
     if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
         raise RuntimeError("%s: labels must be contiguous uint8 [F, Ho, Wo]" % name)
@@ -691,6 +732,8 @@ def _rgb_paint_args(name, labels, frames, palette, out, f_off, a256, contour, mo
         _mosaic_args(name, *mosaic)
     if blur is not None:
         _blur_args(name, *blur)
+    if replace is not None:
+        _replace_args(name, *replace, F, Ho, Wo)
     if Ho < 1 or Wo < 1 or Ho * Wo * 3 >= 2 ** 31 or F * Ho * Wo >= 2 ** 31:
         raise RuntimeError("%s: Ho, Wo must be positive with Ho*Wo*3 < 2^31 and F*Ho*Wo < 2^31, got %s" % (name, tuple(labels.shape)))
     if not torch.is_tensor(palette) or palette.dtype != torch.uint8 or tuple(palette.shape) != (256, 3) or not palette.is_contiguous():
@@ -709,7 +752,9 @@ def _rgb_paint_args(name, labels, frames, palette, out, f_off, a256, contour, mo
             raise RuntimeError("%s: every frame must be contiguous and the frames a stride >= 3*h0*w0 apart, got strides %s"
                                % (name, tuple(frames.stride())))
     tensors = [(labels, "labels"), (palette, "palette")] + ([(mosaic[0], "action")] if mosaic is not None else [])
-    tensors += ([(blur[0], "action"), (blur[1], "taps")] if blur is not None else []) + [(out, "out"), (frames, "frames")]
+    tensors += [(blur[0], "action"), (blur[1], "taps")] if blur is not None else []
+    tensors += [(replace[0], "action"), (replace[1], "matte"), (replace[2], "backdrop")] if replace is not None else []
+    tensors += [(out, "out"), (frames, "frames")]
     for t, what in tensors:
         if t is not None and (not t.is_cuda or t.device != out.device):
             raise RuntimeError("%s: %s must be a CUDA tensor on out's device, got %s" % (name, what, t.device))
@@ -740,6 +785,133 @@ def render_mosaic(labels, frames, palette, action, out, f_off=0, a256=128, conto
     check(lib.mdqe_render_mosaic_u8(ptr(frames) if frames is not None else None, int(frames is not None and frames.dtype == torch.uint8),
                                     stride, h0, w0, ptr(labels), F, Ho, Wo, ptr(palette), ptr(action), a256, contour, cell, ptr(out),
                                     f_off, cur_stream()), "render_mosaic")
+    return out
+
+
+REPLACE_MODES = ("background", "tracks")     # mode 0: the matte is the foreground that is kept; 1: the matte covers what is replaced
+
+
+def render_replace(labels, frames, palette, action, matte, backdrop, out, f_off=0, a256=128, contour=1, mode="background"):
+    """`render_overlay` composited over a backdrop by a soft matte: with `base` the pixel of render_overlay under the per-label action
+    (uint8 [256], action[l]: 1 tint as render_overlay does, anything else -- 0 keep, 4 replace -- the source), Wt = matte (uint8
+    [F, Ho, Wo], ops.final_matte's output) in mode "background" and 255 - matte in mode "tracks",
+    out_c = (base_c * Wt + B_c * (255 - Wt) + 127) // 255, where B is `backdrop`: uint8 [3], one colour in the frames' channel order, or
+    uint8 [Ho, Wo, 3], one picture for every frame.  Every other argument is render_overlay's: the integer rule of include/mdqe_hip.h,
+    mdqe_render_replace_u8.  -> out."""
+    if mode not in REPLACE_MODES:
+        raise RuntimeError("render_replace: mode must be 'background' or 'tracks', got %r" % (mode,))
+    F, Ho, Wo, h0, w0, stride = _rgb_paint_args("render_replace", labels, frames, palette, out, f_off, a256, contour,
+                                                replace=(action, matte, backdrop))
+    check(lib.mdqe_render_replace_u8(ptr(frames) if frames is not None else None, int(frames is not None and frames.dtype == torch.uint8),
+                                     stride, h0, w0, ptr(labels), F, Ho, Wo, ptr(palette), ptr(action), a256, contour, ptr(matte),
+                                     ptr(backdrop), int(backdrop.dim() == 3), REPLACE_MODES.index(mode), ptr(out), f_off, cur_stream()),
+          "render_replace")
+    return out
+
+
+def render_replace_yuv(labels, yuv, palette_yuv, action, matte, backdrop, out=None, f_off=0, a256=128, contour=1, mode="background"):
+    """`render_replace` on decoder surfaces: `render_overlay_yuv` under the per-label action (1 tints, anything else keeps the sample)
+    mixed with a backdrop by the matte (uint8 [F, H, W]).  backdrop: uint16 [3], (Y, U, V) in sample units (render.backdrop_yuv), or a
+    preprocess.YuvFrames of ONE surface of yuv's size and fmt.  Luma: mix(baseY, BY, Wt); a chroma pair: the rounded mean over its 2 x 2
+    block's in-picture pixels of mix(px_i(C), BC, Wt_i); a kept sample at full weight keeps the decoder's bits (P010: all 16 of a word;
+    a chroma pair when its whole block is such): the integer rule of include/mdqe_hip.h, mdqe_render_replace_yuv420sp.  `out` may be
+    `yuv` itself (in place), nothing else that overlaps it.  On a HIP device one launch on the current stream; on host planes the same
+    rule in torch integers.  -> out."""
+    from .preprocess import YuvFrames
+    name = "render_replace_yuv"
+    if mode not in REPLACE_MODES:
+        raise RuntimeError("%s: mode must be 'background' or 'tracks', got %r" % (name, mode))
+    if not isinstance(yuv, YuvFrames):
+        raise RuntimeError("%s: yuv must be a preprocess.YuvFrames, got %s" % (name, type(yuv).__name__))
+    F, H, W = len(yuv), yuv.height, yuv.width
+    if not torch.is_tensor(action) or action.dtype != torch.uint8 or tuple(action.shape) != (256,) or not action.is_contiguous():
+        raise RuntimeError("%s: action must be contiguous uint8 [256] (render.Style.actions)" % name)
+    if not torch.is_tensor(matte) or matte.dtype != torch.uint8 or tuple(matte.shape) != (F, H, W) or not matte.is_contiguous():
+        raise RuntimeError("%s: matte must be contiguous uint8 [F = %d, %d, %d], the surfaces' own size (ops.final_matte)" % (name, F, H, W))
+    surf = isinstance(backdrop, YuvFrames)
+    if surf:
+        if len(backdrop) != 1 or (backdrop.height, backdrop.width, backdrop.fmt) != (H, W, yuv.fmt):
+            raise RuntimeError("%s: a backdrop surface must be a YuvFrames of ONE surface of %d x %d %s" % (name, H, W, yuv.fmt))
+    elif (not torch.is_tensor(backdrop) or backdrop.dtype not in (torch.uint16, torch.int16) or tuple(backdrop.shape) != (3,)
+          or not backdrop.is_contiguous()):
+        raise RuntimeError("%s: backdrop must be contiguous uint16 [3] (render.backdrop_yuv) or a YuvFrames of one surface" % name)
+    F, H, W, out = _yuv_paint_args(name, labels, yuv, palette_yuv, out, f_off, a256, contour)
+    for t, what in ((action, "action"), (matte, "matte"), (backdrop, "backdrop")):
+        if t.device != yuv.device:
+            raise RuntimeError("%s: %s must be on the surfaces' device %s, got %s" % (name, what, yuv.device, t.device))
+    if yuv.is_cuda:
+        from .preprocess import _pitch_stride
+        src, dst = _surface_call_args(labels, yuv, palette_yuv, out, F, H, W)
+        back = (None, ptr(backdrop.y), _pitch_stride(backdrop.y)[0], ptr(backdrop.uv), _pitch_stride(backdrop.uv)[0]) if surf \
+            else (ptr(backdrop), None, 0, None, 0)
+        with torch.cuda.device(yuv.device):
+            check(lib.mdqe_render_replace_yuv420sp(*src, ptr(action), a256, contour, ptr(matte), *back, REPLACE_MODES.index(mode), *dst, f_off,
+                                                   cur_stream(yuv.device)), name)
+        return out
+    if F == 0:
+        return out
+    return _replace_yuv_host(labels, yuv, palette_yuv, action, matte, backdrop, out, f_off, a256, contour, REPLACE_MODES.index(mode))
+
+
+def _replace_yuv_host(labels, yuv, palette_yuv, action, matte, backdrop, out, f_off, a256, contour, mode):
+    """mdqe_render_replace_yuv420sp's rule on host planes, in torch integers."""
+    F, H, W = len(yuv), yuv.height, yuv.width
+    p010 = yuv.fmt == "p010"
+    ch, cw = (H + 1) // 2, (W + 1) // 2
+    mask = 0x3FF if p010 else 0xFF
+
+    def raw(t):
+        v = t.to(torch.int64)
+        return v & 0xFFFF if p010 else v
+
+    def store(dst, word):
+        dst.copy_(((word + 0x8000) & 0xFFFF) - 0x8000 if p010 else word)
+
+    def up(t):                                      # a chroma-plane quantity at every pixel of its block
+        return t.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)[:, :H, :W]
+
+    def mix(s, b, w):
+        return (s * w + b * (255 - w) + 127) // 255
+    lab = labels.to(torch.int64)
+    tinted = action.to(torch.int64)[lab] == 1
+    edge = torch.zeros(lab.shape, dtype=torch.bool)
+    for d in range(1, contour + 1):
+        if d < H:
+            edge[:, d:] |= lab[:, d:] != lab[:, :-d]
+            edge[:, :-d] |= lab[:, :-d] != lab[:, d:]
+        if d < W:
+            edge[:, :, d:] |= lab[:, :, d:] != lab[:, :, :-d]
+            edge[:, :, :-d] |= lab[:, :, :-d] != lab[:, :, d:]
+    col = (palette_yuv.view(torch.int16).to(torch.int64) & mask)[lab]
+    wt = matte.to(torch.int64)
+    wt = 255 - wt if mode else wt
+    if torch.is_tensor(backdrop):
+        B = backdrop.view(torch.int16).to(torch.int64) & mask
+        BY, BC = B[0], [B[1], B[2]]
+    else:
+        by, bc = raw(backdrop.y[:, :H, :W]), raw(backdrop.uv[:, :ch, :2 * cw]).reshape(1, ch, cw, 2)
+        BY, BC = (by >> 6 if p010 else by), [up((bc[..., k] >> 6 if p010 else bc[..., k]).expand(F, ch, cw)) for k in (0, 1)]
+
+    def base(s, p):
+        return torch.where(tinted, torch.where(edge, p, (s * (256 - a256) + p * a256 + 128) >> 8), s)
+    kept = ~tinted & (wt == 255)
+    ry = raw(yuv.y[:, :H, :W])
+    Y = ry >> 6 if p010 else ry
+    yo = mix(base(Y, col[..., 0]), BY, wt)
+    rc = raw(yuv.uv[:, :ch, :2 * cw]).reshape(F, ch, cw, 2)
+    C = rc >> 6 if p010 else rc
+
+    def blocks(t):                                  # [F, H, W] -> the sum over each 2 x 2 block's in-picture pixels, [F, ch, cw]
+        full = torch.zeros((F, 2 * ch, 2 * cw), dtype=torch.int64)
+        full[:, :H, :W] = t
+        return full.reshape(F, ch, 2, cw, 2).sum((2, 4))
+    n = blocks(torch.ones((F, H, W), dtype=torch.int64))
+    sh = n >> 1                                     # n = 1, 2, 4: n / 2 = log2(n) = 0, 1, 2
+    same = blocks((~kept).to(torch.int64)) == 0
+    oc = torch.stack([(blocks(mix(base(up(C[..., k]), col[..., k + 1]), BC[k], wt)) + sh) >> sh for k in (0, 1)], -1)
+    # (everything is computed before anything is stored: `out` may be `yuv`)
+    store(out.y[f_off:f_off + F, :H, :W], torch.where(kept, ry, yo << 6 if p010 else yo))
+    store(out.uv[f_off:f_off + F, :ch, :2 * cw], torch.where(same[..., None], rc, oc << 6 if p010 else oc).reshape(F, ch, 2 * cw))
     return out
 
 

@@ -74,6 +74,18 @@ def palette_yuv(palette_rgb, fmt="nv12", matrix="bt709", full_range=False, order
     return torch.stack(rows, 1).to(torch.uint16)
 
 
+def backdrop_yuv(colour, fmt="nv12", matrix="bt709", full_range=False, order="rgb"):
+    """A backdrop colour (three ints 0..255 in the frames' channel order `order`) in the samples of a decoder surface: uint16 [3] on the
+    host, (Y, U, V) -- what ops.render_replace_yuv mixes with.  `palette_yuv`'s integers: a grey has exactly neutral chroma."""
+    c = _backdrop(colour, "backdrop_yuv")
+    if torch.is_tensor(c):
+        raise ValueError("backdrop_yuv: colour must be three ints 0..255, got a tensor (a picture backdrop of a surface session is a "
+                         "YuvFrames of one surface)")
+    pal = torch.zeros(256, 3, dtype=torch.uint8)
+    pal[0] = torch.tensor(c, dtype=torch.uint8)
+    return palette_yuv(pal, fmt, matrix, full_range, order)[0].contiguous()
+
+
 # The annotation pass's font (ops.annotate, csrc/annotate.hip): 5 x 7 glyphs for 0x20..0x5F drawn for this project, one per line, 7 rows
 # top to bottom as hex, bit 4 the leftmost pixel of a row.
 _FONT = """
@@ -215,6 +227,28 @@ def blur_taps(radius):
     return torch.tensor([4096 - 2 * sum(w)] + w, dtype=torch.int32).to(torch.uint16)
 
 
+def _backdrop(v, who):
+    """A backdrop as the painters take it: a tuple of three ints 0..255, or a contiguous uint8 tensor [Ho, Wo, 3] (kept as handed in)."""
+    from .preprocess import YuvFrames
+    if isinstance(v, YuvFrames):
+        if len(v) != 1:
+            raise ValueError("%s: a backdrop surface must be a YuvFrames of ONE surface, got %d -- slice one, frames[i:i + 1]" % (who, len(v)))
+        return v
+    if torch.is_tensor(v):
+        if v.dtype != torch.uint8 or v.dim() != 3 or v.shape[2] != 3 or v.shape[0] < 1 or v.shape[1] < 1:
+            raise ValueError("%s: a backdrop picture must be a uint8 tensor [Ho, Wo, 3] of the output's size, got %s %s -- convert it, "
+                             "or give three ints 0..255" % (who, v.dtype, tuple(v.shape)))
+        return v
+    try:
+        t = tuple(v) if not isinstance(v, (str, bytes)) else None
+    except TypeError:
+        t = None
+    if t is None or len(t) != 3 or any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c <= 255 for c in t):
+        raise ValueError("%s: backdrop must be three ints 0..255 in the frames' channel order or a uint8 tensor [Ho, Wo, 3], got %r"
+                         % (who, v))
+    return t
+
+
 @dataclasses.dataclass
 class Style:
     """alpha: weight of the track colour inside a region, 0..1 (the kernel blends with a256 = round(alpha * 256) in 1/256 steps);
@@ -238,7 +272,16 @@ class Style:
     pixel, 1..4; min_area: regions of fewer pixels get neither box nor caption.
     Trails (ops.render_trails, csrc/paths.hip: a pass between the painter and the annotations, so plates stay legible): trail: 0..64,
     the number of past frames whose centroids (ops.label_centroids: of each track's visible region, the ones of at least min_area
-    pixels) are joined to the current frame's by a line in the track's colour, 0: none; trail_width: that line's width in pixels, 1..5."""
+    pixels) are joined to the current frame's by a line in the track's colour, 0: none; trail_width: that line's width in pixels, 1..5.
+    replace: None, or what is replaced by `backdrop` through a soft matte (ops.final_matte behind the label map, then ops.render_replace,
+    csrc/render_replace.hip, in place of the other painters): "tracks" -- every track, or with `classes` the tracks of those classes,
+    the others tinted; the background stays as decoded -- or "background" -- everything but the tracks, which are tinted as alpha /
+    contour say (alpha=0, contour=0: left as decoded); with `classes` only the tracks of those classes are kept and every other track
+    goes with the background: the virtual-background case.  Not together with a mosaic or a blur.  backdrop: three ints 0..255 in the
+    frames' channel order, or a uint8 tensor [Ho, Wo, 3], one picture of the output's size for every frame, or, in a surface=True
+    session, a preprocess.YuvFrames of one surface of the session's kind.  matte_gain: in (0, 64],
+    the factor on the logit under the matte's sigmoid: above 1 a sharper edge, below 1 a softer one; the matte's 128 level, the hard
+    mask's edge, does not move."""
     alpha: float = 0.5
     contour: int = 1
     palette: torch.Tensor = None
@@ -254,6 +297,9 @@ class Style:
     min_area: int = 0
     trail: int = 0
     trail_width: int = 2
+    replace: str = None
+    backdrop: object = (0, 255, 0)
+    matte_gain: float = 1.0
 
     def __post_init__(self):
         if isinstance(self.trail, bool) or not isinstance(self.trail, int) or not 0 <= self.trail <= 64:
@@ -293,6 +339,15 @@ class Style:
             raise ValueError("overlay style: blur_radius must be an int in 1..32, got %r" % (self.blur_radius,))
         if self.mosaic is not None and self.blur is not None:
             raise ValueError("overlay style: a style has a mosaic or a blur, not both; got mosaic=%r with blur=%r" % (self.mosaic, self.blur))
+        if self.replace not in (None, "tracks", "background"):
+            raise ValueError("overlay style: replace must be None, 'tracks' or 'background', got %r" % (self.replace,))
+        if self.replace is not None and (self.mosaic is not None or self.blur is not None):
+            raise ValueError("overlay style: a style has at most one of mosaic, blur and replace -- drop two of them; got mosaic=%r, "
+                             "blur=%r, replace=%r" % (self.mosaic, self.blur, self.replace))
+        if (isinstance(self.matte_gain, bool) or not isinstance(self.matte_gain, (int, float))
+                or not 0.0 < float(self.matte_gain) <= 64.0):
+            raise ValueError("overlay style: matte_gain must be a number in (0, 64] (1.0: the model's own sigmoid), got %r" % (self.matte_gain,))
+        self.backdrop = _backdrop(self.backdrop, "overlay style")
         if self.classes is not None:
             try:
                 cls = tuple(self.classes) if not isinstance(self.classes, (str, bytes)) else None
@@ -300,7 +355,7 @@ class Style:
                 cls = None
             if cls is None or any(isinstance(c, bool) or not isinstance(c, int) or c < 0 for c in cls):
                 raise ValueError("overlay style: classes must be None or a collection of ints >= 0, got %r" % (self.classes,))
-            if self.mosaic != "tracks" and self.blur != "tracks":
+            if self.mosaic != "tracks" and self.blur != "tracks" and self.replace is None:
                 raise ValueError("overlay style: classes selects the tracks that mosaic='tracks' pixelates or blur='tracks' blurs; got "
                                  "classes with mosaic=%r, blur=%r" % (self.mosaic, self.blur))
             self.classes = tuple(sorted(set(cls)))
@@ -349,27 +404,67 @@ class Style:
         return None if self.caption is None else captions(self, cls_probs, n).to(device)
 
     def actions(self, cls_probs=None):
-        """The per-label action table of ops.render_mosaic / ops.render_blur, uint8 [256] on the host (0 keep, 1 tint, 2 mosaic, 3 blur;
-        entry 0 is the background's), a pure function.  With r = 2 for a mosaic and 3 for a blur: neither: [0, 1, 1, ...] (the plain
-        overlay); "background": [r, 1, 1, ...]; "tracks": [0, r, r, ...], or with `classes`, from the window's class rows cls_probs
-        [n, K] (win.cls_probs): label t + 1 gets r when the first maximum of row t is a class in `classes` and 1 otherwise, and so do
-        the labels above n."""
-        what, r = (self.blur, 3) if self.blur is not None else (self.mosaic, 2)
+        """The per-label action table of ops.render_mosaic / ops.render_blur / ops.render_replace, uint8 [256] on the host (0 keep, 1 tint,
+        2 mosaic, 3 blur, 4 replace; entry 0 is the background's), a pure function.  With r = 2 for a mosaic, 3 for a blur and 4 for a
+        replacement: none of them: [0, 1, 1, ...] (the plain overlay); "background": [r, 1, 1, ...]; "tracks": [0, r, r, ...], or with
+        `classes`, from the window's class rows cls_probs [n, K] (win.cls_probs): label t + 1 gets r when the first maximum of row t
+        is a class in `classes` and 1 otherwise, and so do the labels above n.  replace="background" with `classes` (the only
+        "background" that takes them): [4, then 1 for the tracks of the listed classes and 4 for the others, 4 above n]."""
+        what, r = (self.replace, 4) if self.replace is not None else (self.blur, 3) if self.blur is not None else (self.mosaic, 2)
         act = torch.ones(256, dtype=torch.uint8)
         act[0] = r if what == "background" else 0
         if what == "tracks" and self.classes is None:
             act[1:] = r
-        elif what == "tracks":
+        elif what == "tracks" or (r == 4 and self.classes is not None):
             if not torch.is_tensor(cls_probs) or cls_probs.dim() != 2:
                 raise ValueError("overlay style: a %s of classes needs the window's class rows [n, K], got %r"
-                                 % ("blur" if r == 3 else "mosaic", type(cls_probs).__name__))
+                                 % ({2: "mosaic", 3: "blur", 4: "replacement"}[r], type(cls_probs).__name__))
+            # replace="background" with classes: the listed tracks are kept (tinted), every other label goes with the background
+            hit_as, miss_as = (1, 4) if what == "background" else (r, 1)
+            act[1:] = miss_as
             n = min(int(cls_probs.shape[0]), 255)
             if n and cls_probs.shape[1]:
                 rows = cls_probs[:n].detach().cpu()
                 first = rows.argmax(1)                  # (of several maxima the first: torch.argmax's rule)
                 hit = torch.isin(first, torch.tensor(self.classes, dtype=first.dtype))
-                act[1:n + 1] = torch.where(hit, r, 1).to(torch.uint8)
+                act[1:n + 1] = torch.where(hit, hit_as, miss_as).to(torch.uint8)
         return act
+
+    def takes(self, cls_probs=None):
+        """The matte's row table of ops.final_matte for a replace style, uint8 [256] on the host, from `actions(cls_probs)`: entry l says
+        whether the track of label l takes part in the matte -- "background": the tracks that are kept (action != 4, labels >= 1: the
+        matte is the foreground); "tracks": the tracks that are replaced (action == 4: the matte covers them).  Entry 0 is 0 (unused)."""
+        if self.replace is None:
+            raise ValueError("overlay style: takes() is the matte's table of a style with replace='tracks' or 'background'")
+        act = self.actions(cls_probs)
+        take = (act != 4) if self.replace == "background" else (act == 4)
+        take[0] = False
+        return take.to(torch.uint8)
+
+    def takes_on(self, device, cls_probs=None):
+        """`takes` on `device`: cached per device where the table does not depend on the window (no `classes`), as `actions_on` is."""
+        if self.classes is not None:
+            return self.takes(cls_probs).to(device)
+        return self._cached_on("_take_on", (str(device),), self.takes)
+
+    def backdrop_on(self, device):
+        """The backdrop on `device`, contiguous uint8 [3] or [Ho, Wo, 3] (cached per device, as the palette is)."""
+        return self._cached_on("_backdrop_on", (str(device),),
+                               lambda: self.backdrop if torch.is_tensor(self.backdrop) else torch.tensor(self.backdrop, dtype=torch.uint8))
+
+    def backdrop_yuv_on(self, device, fmt, matrix, full_range, order):
+        """The backdrop of a surface session on `device` (cached per device and kind of surface): `backdrop_yuv` of a colour, or the
+        backdrop surface itself moved there."""
+        from .preprocess import YuvFrames
+        key = (str(device), fmt, matrix, bool(full_range), order)
+        if not isinstance(self.backdrop, YuvFrames):
+            return self._cached_on("_backdrop_yuv_on", key, lambda: backdrop_yuv(self.backdrop, fmt, matrix, bool(full_range), order))
+        cache = self.__dict__.setdefault("_backdrop_yuv_on", {})
+        if key not in cache:
+            cache[key] = self.backdrop.to(device)
+            if cache[key].is_cuda:
+                torch.cuda.current_stream(cache[key].device).synchronize()
+        return cache[key]
 
     def actions_on(self, device, cls_probs=None):
         """`actions` on `device`: cached per device as the palette is where the table does not depend on the window (no `classes`);
@@ -413,6 +508,43 @@ class Style:
             if cache[key].is_cuda:
                 torch.cuda.current_stream(cache[key].device).synchronize()
         return cache[key]
+
+
+@dataclasses.dataclass(frozen=True)
+class Matte:
+    """The soft matte as a video output of its own (model.matte_output, online_video(matte=...)), beside any other output: per frame one
+    uint8 plane, rint(255 * sigmoid(gain * the largest up-sampled logit among the window's tracks)), held at >= 128 exactly where one
+    of their final masks is set (ops.final_matte, csrc/final_mask.hip) -- the union matte of the tracks, what compositing and
+    rotoscoping take.  classes: None (every track) or a collection of class ids >= 0 (kept as a sorted tuple): only the tracks whose
+    window class row has its first maximum in one of them; gain: in (0, 64], above 1 a sharper edge, below 1 a softer one."""
+    classes: tuple = None
+    gain: float = 1.0
+
+    def __post_init__(self):
+        if isinstance(self.gain, bool) or not isinstance(self.gain, (int, float)) or not 0.0 < float(self.gain) <= 64.0:
+            raise ValueError("matte: gain must be a number in (0, 64] (1.0: the model's own sigmoid), got %r" % (self.gain,))
+        if self.classes is not None:
+            try:
+                cls = tuple(self.classes) if not isinstance(self.classes, (str, bytes)) else None
+            except TypeError:
+                cls = None
+            if cls is None or any(isinstance(c, bool) or not isinstance(c, int) or c < 0 for c in cls):
+                raise ValueError("matte: classes must be None or a collection of ints >= 0, got %r" % (self.classes,))
+            object.__setattr__(self, "classes", tuple(sorted(set(cls))))
+
+    def takes(self, cls_probs=None):
+        """ops.final_matte's row table, uint8 [256] on the host by label, or None without `classes` (every row takes part): label
+        t + 1 is 1 when the first maximum of row t of the window's class rows cls_probs [n, K] is a listed class."""
+        if self.classes is None:
+            return None
+        if not torch.is_tensor(cls_probs) or cls_probs.dim() != 2:
+            raise ValueError("matte: classes need the window's class rows [n, K], got %r" % type(cls_probs).__name__)
+        take = torch.zeros(256, dtype=torch.uint8)
+        n = min(int(cls_probs.shape[0]), 255)
+        if n and cls_probs.shape[1]:
+            first = cls_probs[:n].detach().cpu().argmax(1)
+            take[1:n + 1] = torch.isin(first, torch.tensor(self.classes, dtype=first.dtype)).to(torch.uint8)
+        return take
 
 
 @dataclasses.dataclass(frozen=True)

@@ -566,6 +566,9 @@ class _Job:
         if getattr(model, "crop_output", None) is not None:
             raise ValueError("crop_output is not offered by the sharded driver: rank 0 does not hold every frame of the video (cut the crops "
                              "from pred_label_map and the frames on the host, or run the video on one device)")
+        if getattr(model, "matte_output", None) is not None:
+            raise ValueError("matte_output is not offered by the sharded driver: the matte is swept from every window's logits where the "
+                             "window is flushed, on one device (run the video on one device)")
         if getattr(model, "path_output", False):
             raise ValueError("path_output is not offered by the sharded driver: the centroids are summed from the label map where it is made, "
                              "window by window on one device (sum them from pred_label_map on the host, or run the video on one device)")
