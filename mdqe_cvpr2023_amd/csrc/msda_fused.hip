@@ -731,7 +731,12 @@ extern "C" int mdqe_msda_fused_f32(const float* value, long ldv, long v_brows, c
       // alone 72.5 us, levels 2 + 3 = 115 KB 79.8 us, tools/msda_dec_640p.py); the encoder's long query runs take what fits
       const long budget = (long)(dec_form && g_msda_stage_kb > g_msda_dec_stage_kb ? g_msda_dec_stage_kb : g_msda_stage_kb) * 1024;
       while (LS > 1 && ((px + (long)lv.H[LS - 1] * lv.W[LS - 1] + 1) * D * 4 + desc) <= budget) { --LS; px += (long)lv.H[LS] * lv.W[LS]; }
-      if (LS < L) {
+      // the kernel stages ONE run of tokens, start[LS] .. start[LS] + px, and addresses level l at start[l] - start[LS] inside it: the
+      // levels [LS, L) must lie back to back in ascending order.  Any other table (a gap between coarse levels, the fine level last --
+      // both legal for v1 / v2) falls through to v2, as the temporal branch's `ok` does below
+      bool contig = true;
+      for (int l = LS; l + 1 < L; ++l) contig = contig && (long)lv.start[l + 1] == (long)lv.start[l] + (long)lv.H[l] * lv.W[l];
+      if (LS < L && contig) {
         const size_t smem = (size_t)((px + 1) * D * 4 + desc);
         // queries per block, by what a block stages (tools/pmc_msda.py variants, us per launch): 38 KB (360p, 40 frames) 128: 380,
         // 256: 420, 640: 436, 2048: 513; 50 KB (Swin-L 480p, D = 24) 128: 240, 256: 227, 512: 255; 115 KB (640p, one block per CU)

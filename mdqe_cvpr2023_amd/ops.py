@@ -488,7 +488,8 @@ def msda_fused(value, offs, logits, ref, levels, B, Q, M, D, L, P, mode=0, grid=
                v_brows=None, out=None, vidx=None):
     """Fused MSDeformAttn core.  value/offs/logits: 2-D row-strided fp32 views (last dim contiguous):
     value [B*v_brows, M*D], offs [B*Q, M*L*P*2], logits [B*Q, M*L*P].  ref: [Q,2|4] (broadcast) or [B,Q,2|4].
-    levels: (H list, W list, start-row list) of length groups*L."""
+    levels: (H list, W list, start-row list) of length groups*L; the levels may lie anywhere in the element's block (the
+    LDS-staged kernels are taken only where the staged levels lie back to back in ascending order)."""
     import ctypes
     Hs, Ws, Ss = levels
     n = groups * L
