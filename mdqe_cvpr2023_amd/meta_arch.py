@@ -13,7 +13,7 @@ COCO image sets (`DATASETS.TEST[0]` = coco*) take the single-image branch (`infe
 """
 import contextlib
 import os
-from collections import OrderedDict
+from collections import OrderedDict, deque
 
 import numpy as np
 import torch
@@ -23,7 +23,7 @@ import torch.nn.functional as F
 from .config import MDQEConfig, from_d2_cfg
 from .engine import Engine
 from .params import ALIASES, full_manifest, random_state
-from . import merge
+from . import merge, schedule
 from .merge import ClipMerger      # (merge_clips, sharding and online resolve the class through THIS namespace at call time)
 
 
@@ -62,6 +62,213 @@ def _shared_stream(name):
         if stream is not None:
             _STREAMS[key(self) + (name,)] = stream
     return property(get, put)
+
+
+class _PlannedGroup:
+    """Runtime state of a planned group of clips (schedule.Group): the rows it reads and the events around it."""
+    __slots__ = ("cache", "ready", "dec_ready", "outs", "done")
+
+    def __init__(self, cache, ready, dec_ready):
+        self.cache = cache                        # name -> the buffer's rows [0, rows)
+        self.ready, self.dec_ready = ready, dec_ready   # behind its last frame pass / behind what the DECODER reads of that pass
+        self.outs = None                          # decoder outputs, where the group was decoded ahead
+        self.done = None                          # behind its inference_clips: the group no longer reads its buffer
+
+
+class _ClipIssuer:
+    """The issuing half of `MDQE.iter_clip_results`: the streams, the two cache buffers and the planned groups of one call, and one
+    method per step of the plan (schedule.plan_steps) that issues the work the step stands for.  It decides nothing about the schedule;
+    what it checks at run time is what the plan cannot know (a GPU or not, the A/B knobs, a trace)."""
+
+    def __init__(self, model, frames_dev, geo, chunk, trace, on_frames_queued, h2d, halo, carry, side_streams):
+        self.model, self.eng, self.frames_dev, self.geo, self.chunk = model, model.engine, frames_dev, geo, chunk
+        self.trace, self.on_frames_queued, self.h2d, self.halo, self.carry = trace, on_frames_queued, h2d, halo, carry
+        self.side_streams = side_streams
+        self.cuda = cuda = frames_dev.is_cuda
+        self.clip_stream = torch.cuda.current_stream(frames_dev.device) if cuda else None
+        if cuda and model._frame_stream is None:
+            model._frame_stream = torch.cuda.Stream(frames_dev.device)
+        self.fstream = (model._frame_stream if model.overlap_streams else self.clip_stream) if cuda else None
+        self.bufs = [model.alloc_cache(chunk.capf, geo, keep_enc=halo is not None), None]
+        self.readers = [[], []]                   # buffer -> the groups that read it since it was last switched to
+        self.groups = deque()                     # planned (their frames queued on the frame stream) and not yet decoded, in clip order
+        self.started = False
+        self.pass_ready = self.pass_dec_ready = None      # the events of the pass queued last
+        self.tail_views = self.tail_ev = None     # (halo) the chunk's last T-1 frames and the event they are complete behind
+        self.consuming = False                    # False while the generator is being primed
+        self.carry_ev = None                      # (online carry) the event behind the hand-over of the chunk's tail rows
+        if carry is not None and chunk.lead:
+            with self.fctx():
+                if cuda and self.fstream is not self.clip_stream:
+                    self.fstream.wait_stream(self.clip_stream)
+                carry.head(self.bufs[0], 0)       # in front of every pass and every `ready` event of this chunk
+
+    def fctx(self):
+        return torch.cuda.stream(self.fstream) if self.cuda else contextlib.nullcontext()
+
+    def switch_segment(self, step):
+        """Frames [first, first + keep) are copied over once; the groups that read that buffer two segments ago have finished (events)."""
+        bufs, nb = self.bufs, step.buffer
+        if bufs[nb] is None:
+            bufs[nb] = self.model.alloc_cache(self.chunk.capf, self.geo)
+        with self.fctx():
+            for g in self.readers[nb]:
+                if self.cuda and g.done is not None:
+                    self.fstream.wait_event(g.done)
+            self.readers[nb] = []
+            if step.keep > 0:
+                o = step.src_row
+                for k, v in bufs[nb].items():
+                    v[:step.keep].copy_(bufs[1 - nb][k][o:o + step.keep])
+
+    def queue_pass(self, step):
+        """A frame pass, asynchronous on the frame stream, stored in place at the rows of its frames."""
+        cuda, fstream = self.cuda, self.fstream
+        with self.fctx():
+            if cuda:
+                if not self.started and fstream is not self.clip_stream:
+                    fstream.wait_stream(self.clip_stream)              # the frames (and weights) were produced on the caller's stream
+                if self.h2d:                                           # the upload chunks this pass reads (upload_frames)
+                    for end, ev in self.h2d:
+                        if end > step.n0:
+                            fstream.wait_event(ev)
+                        if end >= step.n1:
+                            break
+            self.started = True
+            # what the DECODER reads of this pass is complete (the mask features may still be on their way).  (Also with the halo
+            # exchange since round 5: the neighbour's rows are written on the clip stream itself, in front of the group that reads them.)
+            dr = torch.cuda.Event() if cuda and self.model.early_decode and (self.halo is None or HALO_EARLY_DECODE) else None
+            self.model._frame_cache(self.frames_dev[step.n0:step.n1], self.geo, ring=self.bufs[step.buffer], at=step.row, dec_ready=dr)
+            ready = None
+            if cuda:
+                ready = torch.cuda.Event()
+                ready.record(fstream)
+        self.pass_ready, self.pass_dec_ready = ready, dr
+
+    def halo_tail(self, step):
+        buf = self.bufs[step.buffer]
+        self.tail_views = (buf["enc"][step.row0:step.row1], buf["mf"][step.row0:step.row1])
+        self.tail_ev = self.pass_ready if step.new_pass else None
+        if self.cuda and self.tail_ev is None:
+            self.tail_ev = torch.cuda.Event()
+            self.tail_ev.record(self.fstream)
+
+    def plan_group(self, step):
+        ready, dec_ready = (self.pass_ready, self.pass_dec_ready) if step.new_frames else (None, None)
+        if self.cuda and ready is None:           # no new pass (rows of earlier passes, maybe copied by a segment switch): all that is queued so far
+            ready = torch.cuda.Event()
+            with self.fctx():
+                ready.record(self.fstream)
+        g = _PlannedGroup({k: v[:step.rows] for k, v in self.bufs[step.buffer].items()}, ready, dec_ready)
+        self.readers[step.buffer].append(g)
+        self.groups.append(g)
+        if step.frames_queued and self.on_frames_queued is not None:
+            # once, when the LAST frame of this video has been queued on the frame stream: a caller that streams videos
+            # queues the next video's first pass now, under this video's remaining clip / tracker work
+            cb, self.on_frames_queued = self.on_frames_queued, None
+            cb()
+
+    def carry_tail(self, step):
+        """(online carry) Once every clip is planned and the frames from `carry.tail_from` on are through the per-frame stages: their
+        cache rows -- carried rows in front of the chunk included -- to `carry.on_tail` on the frame stream."""
+        with self.fctx():
+            self.carry.on_tail({k: v[step.row0:step.row1] for k, v in self.bufs[0].items()})
+            if self.cuda:
+                self.carry_ev = torch.cuda.Event()
+                self.carry_ev.record(self.fstream)
+
+    def send_tail(self):
+        """The grouped send/recv of the halo exchange, behind the chunk's last pass.  Never while the
+        generator is being primed: every rank must issue it at the same point of its program -- between the gathers of two
+        rounds -- or a rank whose chunk is a single pass would queue it BEFORE the previous round's gather and RCCL, which runs
+        a rank's operations in issue order, would deadlock against a rank that queued it after."""
+        halo, model = self.halo, self.model
+        # What keeps the exchange out of the priming phase is the PLAN: it puts `send_tail` on Consume steps only, and the generator's
+        # loop sets `consuming` right in front of each.  The check below cannot fire as the code stands; it only catches a future edit
+        # that calls this from a planning step (which hangs ranks) -- do not rely on it.
+        if not self.consuming:
+            raise RuntimeError("halo exchange: send_tail() while the generator is being primed -- the grouped send/recv must be "
+                               "issued between the gathers of two rounds on every rank")
+        if not self.cuda or not HALO_OWN_STREAM:
+            with self.fctx():
+                if self.cuda:
+                    self.fstream.wait_event(self.tail_ev)
+                halo.on_tail(*self.tail_views)
+            return
+        # On the model's COPY stream, behind the event of the chunk's last pass only.  (Rounds 3-4 issued it on the frame stream --
+        # which by now holds the NEXT round's primed passes: the message, and with it the last decoder group of every rank of this
+        # round, waited for 1-3 passes of the next round.)
+        if model._copy_stream is None:
+            model._copy_stream = torch.cuda.Stream(self.frames_dev.device)
+        hs = model._copy_stream
+        hs.wait_event(self.tail_ev)
+        with torch.cuda.stream(hs):
+            halo.on_tail(*self.tail_views)
+        for v in self.tail_views:
+            v.record_stream(hs)
+
+    def consume(self, step):
+        """Decoder + inference_clips of the oldest planned group; yields its clips' (start, end, last, res)."""
+        model, eng, cuda, clip_stream = self.model, self.eng, self.cuda, self.clip_stream
+        if step.send_tail:
+            self.send_tail()
+        cur = self.groups.popleft()
+        cache, T, starts = cur.cache, step.group.T, list(step.starts)
+        dr = cur.dec_ready if cuda else None
+        if cuda:
+            clip_stream.wait_event(dr if dr is not None else cur.ready)
+        if step.straddlers:
+            enc_h, mf_h = self.halo.head()                     # (waits for the neighbour's message on this stream)
+            model._cache_from_tokens(enc_h, mf_h, self.geo, self.bufs[step.group.buffer], 0)
+        outs = cur.outs
+        if outs is None:
+            # side_streams=False (the sharded schedule): HIP multiplexes its streams onto 4 hardware queues, and with RCCL's stream
+            # and the replay thread's tracker stream in play the decoder's instance-chain stream lands on a queue behind the frame
+            # stream's long GEMMs -- 616 against 708 frames/s per rank (tools/hwq_ab2.sh; GPU_MAX_HW_QUEUES=8 recovers most of it,
+            # 697, but costs the single-GPU path 1.6 %)
+            outs = eng.decode_clips(cache, starts, T, self.geo, two_streams=self.side_streams)
+        elif cuda:
+            clip_stream.wait_stream(model._ahead_stream)       # decoded ahead (below) on the auxiliary stream
+            for v in outs.values():
+                v.record_stream(clip_stream)
+        # Decode-ahead: a following group that needs NO new frame pass -- the short clips at the end of a video, whose frames the
+        # last pass has already produced -- is decoded now, on an auxiliary stream beside this group's decoder, instead of after
+        # this group's inference_clip syncs and tracker run.  Both decoders are chains of small dependent launches (latency-bound
+        # at these sizes), so the second one is nearly free: the tail of a 120-frame video drops by the 2.6 ms the lone 3-frame
+        # clip took (tools/tail_time.py).  Same kernels, same inputs, same bits.
+        if step.ahead is not None and cuda and model.decode_ahead and self.side_streams and self.trace is None and self.groups[0].outs is None:
+            nx, nxg = self.groups[0], step.ahead
+            if model._ahead_stream is None:
+                model._ahead_stream = torch.cuda.Stream(self.frames_dev.device, priority=-1)
+            aux = model._ahead_stream
+            aux.wait_event(nx.ready)                           # its frames (the pass this group waits for too)
+            with torch.cuda.stream(aux):
+                nx.outs = eng.decode_clips(nx.cache, list(nxg.starts), nxg.T, self.geo)
+        if dr is not None:
+            clip_stream.wait_event(cur.ready)                  # the mask features of the group's last pass (inference_clip reads them)
+        ress = eng.inference_clips(outs, cache["mf"], starts, T)
+        ready = None
+        if cuda:
+            ready = torch.cuda.Event()
+            ready.record(clip_stream)             # the clip results are complete once this event fires
+        cur.done = ready                          # ... and the group no longer reads its buffer
+        group = self.chunk.clips[step.group.i:step.group.j] + step.straddlers
+        for gi, ((start, end, last), res) in enumerate(zip(group, ress)):
+            if self.trace is not None:
+                self.trace.append({k_: v.clone() for k_, v in res.items() if torch.is_tensor(v)})
+            res["ready"] = ready
+            res["batch_end"] = gi == len(group) - 1
+            yield start, end, last, res
+
+    def finish(self):
+        if self.carry_ev is not None:
+            # the tail passes no group waited for: the chunk's frames and cache are released on the caller's stream after them
+            self.clip_stream.wait_event(self.carry_ev)
+
+    # step type -> the method that issues it (plain functions: an issuer that held its own bound methods would be a reference cycle, and
+    # its cache buffers would wait for the garbage collector instead of being released with the generator)
+    ISSUE = {schedule.Switch: switch_segment, schedule.Pass: queue_pass, schedule.HaloTail: halo_tail, schedule.Group: plan_group,
+             schedule.CarryTail: carry_tail}
 
 
 class MDQE(nn.Module):
@@ -478,30 +685,7 @@ class MDQE(nn.Module):
         if "enc" in ring:
             ring["enc"][at:at + n].copy_(enc)
 
-    @staticmethod
-    def pass_bounds(n_frames, fbatch, taper=True, tail=0, split_small=False):
-        """End frames of the passes of the per-frame stages over a chunk of `n_frames`: uniform passes of `fbatch` frames, or
-        (taper) a half-size first pass -- the clip stream starts after half a pass instead of a whole one -- and a last pass of
-        at most `tail` frames (0: half a pass) -- the tail that runs with an idle frame stream (last decoder batch, tracker,
-        mask read-back) is shorter.  Measured: 20/40/40/20 at 360p +0.2-1.1 %; shorter tails lose to the extra pass."""
-        bounds = list(range(fbatch, n_frames, fbatch)) + [n_frames]
-        if split_small and taper and 16 <= n_frames <= fbatch:
-            # a chunk of a sharded video that fits ONE pass goes in two: a round's clip work trails its frames by about the pass queued
-            # behind them (the next round's first), and the round is gathered -- and its tracker replay can start on rank 0 -- only then
-            return [n_frames // 2, n_frames]
-        if taper and n_frames > fbatch:
-            h = max(fbatch // 2, 1)
-            t = max(min(tail, h), 1) if tail > 0 else h
-            bounds = [h] + list(range(h + fbatch, n_frames, fbatch)) + [n_frames]
-            if len(bounds) >= 2 and bounds[-1] - bounds[-2] > t and n_frames - t - bounds[-2] >= 4:
-                bounds.insert(-1, n_frames - t)
-            if len(bounds) >= 3 and bounds[-1] - bounds[-2] < max(min(t, h) // 2, 1):
-                # a last pass of a handful of frames (a 60-frame chunk + its 3-frame halo: 20 / 40 / 3) runs every GEMM of the
-                # per-frame stages on a sliver: split what lies behind the first pass evenly instead (20 / 22 / 21)
-                r = n_frames - h
-                k = -(-r // fbatch)
-                bounds = [h] + [h + (r * (i + 1)) // k for i in range(k)]
-        return bounds
+    pass_bounds = staticmethod(schedule.pass_bounds)
 
     @staticmethod
     def stacked_view(imgs):
@@ -519,18 +703,7 @@ class MDQE(nn.Module):
         except RuntimeError:
             return None
 
-    @staticmethod
-    def clip_schedule(L, T, stride):
-        """Clip list of mdqe/mdqe.py:308-312: (start, end, is_last); the loop ends at the first clip that
-        reaches past the video (it is clamped and may be shorter than T)."""
-        clips = []
-        for start in range(0, L, stride):
-            end = start + T
-            last = end > L
-            clips.append((start, min(end, L), last))
-            if last:
-                break
-        return clips
+    clip_schedule = staticmethod(schedule.clip_schedule)
 
     CACHE_GB = float(os.environ.get("MDQE_CACHE_GB", "24"))       # HBM budget of ONE frame-cache buffer (a long video uses two)
 
@@ -543,6 +716,8 @@ class MDQE(nn.Module):
         calls, go into the rows in front of its first frame (`carry.head`), so a clip may start anywhere in them -- a 1-frame push
         owns only such straddling clips.  The chunk's frames from global frame `carry.tail_from` on (what later calls' clips read)
         go through the per-frame stages even if no clip here reads them, and their rows are handed to `carry.on_tail`.
+        `carry.rows` / `tail_from` / `tail_sent` and `halo.tail_sent` are sampled ONCE, when the generator starts (they go into the
+        plan); afterwards only the generator's own `on_tail` call is taken to change them.
 
         Two HIP streams: the per-frame stages (backbone .. decoder value cache: large GEMMs) of the next passes run on a frame
         stream while the decoder + inference_clip of group k (small kernels and two host syncs) run on the caller's
@@ -552,307 +727,43 @@ class MDQE(nn.Module):
         frames (`_frame_cache`) and a group of clips reads them through index tables (`starts`), so nothing is copied from buffer to
         buffer -- no carried T-1 frames, no first fill -- and the decoder batch is free of the pass size (`dec_batch`).  A video
         longer than the cache budget (MDQE_CACHE_GB per buffer, 24 GB = 360 frames at 360p) continues in a second buffer, to which the
-        frames still to be read are copied once per segment; the buffers then alternate, events order their reuse."""
-        eng, cfg = self.engine, self.cfg
-        h, w = int(frames_dev.shape[-2]), int(frames_dev.shape[-1])
-        geo = eng.geometry(h, w)
-        n_local = frames_dev.shape[0]
-        Tmax = max((c[1] - c[0] for c in clips), default=1)
-        Tn = cfg.n_frames_test
+        frames still to be read are copied once per segment; the buffers then alternate, events order their reuse.
+
+        WHAT is issued and in which order is decided in schedule.py, over integers alone (`schedule.plan_steps`); this generator
+        resolves the parameters, pulls the plan one step at a time and has a `_ClipIssuer` issue it."""
+        eng = self.engine
+        geo = eng.geometry(int(frames_dev.shape[-2]), int(frames_dev.shape[-1]))
         fbatch = self.frame_batch if self.frame_batch > 0 else max(8, min(40, 306000 // max(geo.N, 1)))
-        # halo exchange (sharded videos, sharding._Halo): `clips` may START up to T-1 frames before this chunk; those clips read
-        # the LEFT neighbour's last T-1 frames, which arrive as encoder tokens + mask features and get their cache entries in the
-        # `lead` rows IN FRONT of this chunk's first frame (so a straddling clip's frames are consecutive rows); in return the tokens
-        # of this chunk's last T-1 frames are handed to `halo.on_tail` as soon as the last pass is queued.
-        strad, lead = [], 0
-        if halo is not None:
-            strad = [c for c in clips if c[0] < frame_offset]
-            clips = [c for c in clips if c[0] >= frame_offset]
-            if any(c[1] - c[0] != Tn or c[0] < frame_offset - (Tn - 1) for c in strad) or not clips:
-                raise RuntimeError("halo exchange: a chunk must hold at least one whole clip and its straddling clips T frames")
-            lead = Tn - 1 if strad else 0
-        elif carry is not None:
-            lead = carry.rows
-            if any(c[0] < frame_offset - lead or c[1] > frame_offset + n_local for c in clips):
-                raise RuntimeError("online carry: a clip reads frames outside the carried rows and the chunk")
-        bounds = self.pass_bounds(n_local, fbatch, self.taper_passes, self.taper_tail, split_small=split_small)
-        cuda = frames_dev.is_cuda
-        clip_stream = torch.cuda.current_stream(frames_dev.device) if cuda else None
-        if cuda and self._frame_stream is None:
-            self._frame_stream = torch.cuda.Stream(frames_dev.device)
-        fstream = (self._frame_stream if self.overlap_streams else clip_stream) if cuda else None
-        fctx = (lambda: torch.cuda.stream(fstream)) if cuda else contextlib.nullcontext
-        dec_batch = max(0, int(self.dec_batch))   # clips per decoder batch the planner waits for (0: whatever one frame pass completes)
-        NR = max(2, self.lookahead + 1)           # groups prepared (their frame passes queued) ahead of the one being decoded + 1
-        # ---- cache capacity (frames): the whole chunk if the budget allows, else segments in two alternating buffers
-        shapes = eng.cache_shapes(geo, keep_enc=halo is not None)
-        per_frame = 4 * sum(int(np.prod(sh)) for sh in shapes.values())
-        forced = int(os.environ.get("MDQE_CACHE_FRAMES", "0"))                 # (tests / A-B: force short segments)
-        gframes = max(fbatch, dec_batch) + Tmax - 1 + fbatch                    # frames one group can span, passes rounded up
-        floor = lead + (NR + 1) * gframes                                       # what the groups in flight need at the very least
-        budget = forced if forced > 0 else int(self.CACHE_GB * 2 ** 30 // max(per_frame, 1))
-        want = n_local + lead
-        capf = min(want, max(budget, floor))
-        single = capf >= want
-        if single:
-            capf = -(-capf // 8) * 8              # (rounded: videos of similar length reuse the allocator's blocks)
-        elif halo is not None:
-            raise RuntimeError("halo exchange: a chunk (%d frames) must fit one frame-cache buffer (%d frames; MDQE_CACHE_GB)" % (n_local, capf))
-        elif carry is not None:
-            raise RuntimeError("online carry: a chunk (%d frames) must fit one frame-cache buffer (%d frames; MDQE_CACHE_GB)" % (n_local, capf))
-        bufs = [self.alloc_cache(capf, geo, keep_enc=halo is not None), None]
-        carry_ev = []                             # (online carry) the event behind the hand-over of the chunk's tail rows
-        if carry is not None and lead:
-            with fctx():
-                if cuda and fstream is not clip_stream:
-                    fstream.wait_stream(clip_stream)
-                carry.head(bufs[0], 0)            # in front of every pass and every `ready` event of this chunk
-        readers = [[], []]                        # buffer -> group states that read it
-        seg = {"b": 0, "base": 0, "lead": lead}   # row of local frame f in buffer b: f - base + lead
-        nxt = 0                                   # local frames [0, nxt) have been through the per-frame stages
-        started = False
-
-        def switch_segment(ls):
-            """Continue in the other buffer, whose row 0 becomes local frame `ls` (the first frame a clip not yet planned reads):
-            frames [ls, nxt) are copied over once; the groups that read that buffer two segments ago have finished (events)."""
-            nb = 1 - seg["b"]
-            if bufs[nb] is None:
-                bufs[nb] = self.alloc_cache(capf, geo)
-            keep = nxt - ls
-            with fctx():
-                for st in readers[nb]:
-                    if "done" not in st:
-                        raise RuntimeError("frame cache: a buffer is needed again while a group still reads it (capacity %d frames)" % capf)
-                    if cuda and st["done"] is not None:
-                        fstream.wait_event(st["done"])
-                readers[nb] = []
-                if keep > 0:
-                    o = ls - seg["base"] + seg["lead"]
-                    for k, v in bufs[nb].items():
-                        v[:keep].copy_(bufs[seg["b"]][k][o:o + keep])
-            seg.update(b=nb, base=ls, lead=0)
-
-        def queue_pass():
-            """The next frame pass, asynchronous on the frame stream, stored in place at the rows of its frames."""
-            nonlocal nxt, started
-            c1 = next(b for b in bounds if b > nxt)
-            row = nxt - seg["base"] + seg["lead"]
-            with fctx():
-                if cuda:
-                    if not started and fstream is not clip_stream:
-                        fstream.wait_stream(clip_stream)               # the frames (and weights) were produced on the caller's stream
-                    if h2d:                                            # the upload chunks this pass reads (upload_frames)
-                        for end, ev in h2d:
-                            if end > nxt:
-                                fstream.wait_event(ev)
-                            if end >= c1:
-                                break
-                started = True
-                # what the DECODER reads of this pass is complete (the mask features may still be on their way).  (Also with the halo
-                # exchange since round 5: the neighbour's rows are written on the clip stream itself, in front of the group that reads them.)
-                dr = torch.cuda.Event() if cuda and self.early_decode and (halo is None or HALO_EARLY_DECODE) else None
-                self._frame_cache(frames_dev[nxt:c1], geo, ring=bufs[seg["b"]], at=row, dec_ready=dr)
-                ready = None
-                if cuda:
-                    ready = torch.cuda.Event()
-                    ready.record(fstream)
-            nxt = c1
-            return {"end": c1, "ready": ready, "dec_ready": dr}
-
-        def frames_queued():
-            """Once, when the LAST frame of this video has been queued on the frame stream: a caller that streams videos
-            queues the next video's first pass now, under this video's remaining clip / tracker work."""
-            nonlocal on_frames_queued
-            if on_frames_queued is not None and nxt >= n_local:
-                cb, on_frames_queued = on_frames_queued, None
-                cb()
-
-        tail_state = {"views": None, "ev": None, "consuming": False}
-
-        def send_tail():
-            """The grouped send/recv of the halo exchange, behind the chunk's last pass.  Never while the
-            generator is being primed: every rank must issue it at the same point of its program -- between the gathers of two
-            rounds -- or a rank whose chunk is a single pass would queue it BEFORE the previous round's gather and RCCL, which runs
-            a rank's operations in issue order, would deadlock against a rank that queued it after."""
-            if halo is None or halo.tail_sent or tail_state["views"] is None:
-                return
-            if not tail_state["consuming"]:       # (guard for future edits: calling this from plan_next / the priming loop hangs ranks)
-                raise RuntimeError("halo exchange: send_tail() while the generator is being primed -- the grouped send/recv must be "
-                                   "issued between the gathers of two rounds on every rank")
-            if not cuda or not HALO_OWN_STREAM:
-                with fctx():
-                    if cuda:
-                        fstream.wait_event(tail_state["ev"])
-                    halo.on_tail(*tail_state["views"])
-                return
-            # On the model's COPY stream, behind the event of the chunk's last pass only.  (Rounds 3-4 issued it on the frame stream --
-            # which by now holds the NEXT round's primed passes: the message, and with it the last decoder group of every rank of this
-            # round, waited for 1-3 passes of the next round.)
-            if self._copy_stream is None:
-                self._copy_stream = torch.cuda.Stream(frames_dev.device)
-            hs = self._copy_stream
-            hs.wait_event(tail_state["ev"])
-            with torch.cuda.stream(hs):
-                halo.on_tail(*tail_state["views"])
-            for v in tail_state["views"]:
-                v.record_stream(hs)
-
-        def carry_tail():
-            """(online carry) Once every clip is planned: the frames from `carry.tail_from` on through the per-frame stages, their cache
-            rows -- carried rows in front of the chunk included -- to `carry.on_tail` on the frame stream."""
-            nonlocal nxt
-            if carry is None or carry.tail_sent:
-                return
-            t0 = min(max(carry.tail_from - frame_offset, -lead), n_local)
-            if nxt < t0:
-                nxt = t0                          # frames no clip reads (CLIP_STRIDE > clip length)
-            while nxt < n_local:
-                queue_pass()
-            with fctx():
-                carry.on_tail({k_: v[t0 + lead:nxt + lead] for k_, v in bufs[0].items()})
-                if cuda:
-                    carry_ev.append(torch.cuda.Event())
-                    carry_ev[-1].record(fstream)
-
-        from collections import deque
-        states = deque()                          # prepared (their frames queued on the frame stream) and not yet decoded, in clip order
-        plan = {"ci": 0}
-
-        def plan_next():
-            """Fix the next group of clips and queue the frame passes it still needs: the group starts at the first clip not yet
-            planned, the planner queues passes until `dec_batch` clips (at least one) are complete, and every further clip of the same
-            length whose frames are then cached joins the batch -- clips are independent through the decoder, so they run as ONE pass
-            (M = clips*T*Q rows)."""
-            nonlocal nxt
-            ci = plan["ci"]
-            if ci >= len(clips):
-                carry_tail()
-                return False
-            off = frame_offset
-            T = clips[ci][1] - clips[ci][0]
-            ls = clips[ci][0] - off
-            if ls > nxt:
-                nxt = ls                          # CLIP_STRIDE > clip length: the frames between two clips are never read
-            k = ci
-            while k + 1 < len(clips) and k + 1 - ci < max(dec_batch, 1) and clips[k + 1][1] - clips[k + 1][0] == T:
-                k += 1
-            target = clips[k][1] - off
-            end = nxt
-            while end < target:
-                end = next(b for b in bounds if b > end)
-            if end - seg["base"] + seg["lead"] > capf:
-                switch_segment(ls)
-            nxt_before = nxt
-            passes = []
-            while nxt < end:
-                passes.append(queue_pass())
-            rows = nxt - seg["base"] + seg["lead"]
-            b = seg["b"]
-            if halo is not None and nxt >= n_local and tail_state["views"] is None and not halo.tail_sent:
-                k_t = min(Tn - 1, n_local)
-                tail_state["views"] = (bufs[b]["enc"][rows - k_t:rows], bufs[b]["mf"][rows - k_t:rows])
-                tail_state["ev"] = passes[-1]["ready"] if passes else None
-                if cuda and tail_state["ev"] is None:
-                    tail_state["ev"] = torch.cuda.Event()
-                    tail_state["ev"].record(fstream)
-            j = ci
-            while j < len(clips) and clips[j][1] - off <= nxt and clips[j][1] - clips[j][0] == T:
-                j += 1
-            ready = passes[-1]["ready"] if passes else None
-            if cuda and ready is None:            # no new pass (rows of earlier passes, maybe copied by a segment switch): all that is queued so far
-                ready = torch.cuda.Event()
-                with fctx():
-                    ready.record(fstream)
-            st = {"b": b, "base": seg["base"], "lead": seg["lead"], "i": ci, "j": j, "T": T, "ready": ready,
-                  "dec_ready": passes[-1]["dec_ready"] if passes else None, "new_frames": nxt - nxt_before, "rows": rows,
-                  "cache": {k_: v[:rows] for k_, v in bufs[b].items()}}
-            readers[b].append(st)
-            plan["ci"] = j
-            states.append(st)
-            frames_queued()
-            return True
-
-        def rows_of(st, group):
-            return [c[0] - frame_offset - st["base"] + st["lead"] for c in group]
-
-        plan_next()
+        # cache capacity (frames): the whole chunk if the budget allows, else segments in two alternating buffers (schedule.cache_capacity)
+        per_frame = 4 * sum(int(np.prod(sh)) for sh in eng.cache_shapes(geo, keep_enc=halo is not None).values())
+        chunk = schedule.resolve(clips, frame_offset, frames_dev.shape[0], self.cfg.n_frames_test, fbatch, self.dec_batch, self.lookahead,
+                                 self.taper_passes, self.taper_tail, split_small, per_frame, self.CACHE_GB,
+                                 halo=halo is not None, halo_tail_sent=halo is not None and halo.tail_sent, carry=carry is not None,
+                                 carry_rows=carry.rows if carry is not None else 0,
+                                 carry_tail_from=carry.tail_from if carry is not None else 0,
+                                 carry_tail_sent=carry is not None and carry.tail_sent)
+        issuer = _ClipIssuer(self, frames_dev, geo, chunk, trace, on_frames_queued, h2d, halo, carry, side_streams)
+        # `lookahead` groups' passes are queued BEFORE a group's clip work (the plan's order): with one, the frame stream ran dry at
+        # every group boundary -- the clip kernels share the chip with the pass queued behind them and finish together with it, and
+        # the next pass was only queued after the host had consumed the group (2-3 ms of whole-GPU idle per boundary in
+        # the HIP trace, tools/trace_gaps.py)
+        for step in schedule.plan_steps(chunk):
+            consume = type(step) is schedule.Consume
+            if not consume:
+                issuer.ISSUE[type(step)](issuer, step)
+            if primed and (consume or (not prime_all and type(step) is schedule.Group)):
+                # a primed generator (sharded videos) is resumed only after the caller has gathered the previous round -- host syncs,
+                # collectives: the frame stream gets its whole look-ahead now so that it does not run dry meanwhile.  prime_all=False
+                # (forward_stream): only the first pass -- the host has the previous video's last decoder batch to launch right now, and
+                # three passes of launches (13 ms of host time) in front of it cost more than they hide
+                primed = False
+                yield None                        # per-frame work of the first passes is queued; the caller resumes later
+            if consume:
+                issuer.consuming = True          # from here on the caller has gathered the previous round: the exchange may be issued
+                yield from issuer.consume(step)
         if primed:
-            # a primed generator (sharded videos) is resumed only after the caller has gathered the previous round -- host syncs,
-            # collectives: the frame stream gets its whole look-ahead now so that it does not run dry meanwhile.  prime_all=False
-            # (forward_stream): only the first pass -- the host has the previous video's last decoder batch to launch right now, and
-            # three passes of launches (13 ms of host time) in front of it cost more than they hide
-            while prime_all and len(states) < NR and plan_next():
-                pass
-            yield None                            # per-frame work of the first passes is queued; the caller resumes later
-        tail_state["consuming"] = True            # from here on the caller has gathered the previous round: the exchange may be issued
-        while states:
-            # `lookahead` groups' passes are queued BEFORE this group's clip work: with one, the frame stream ran dry at every group
-            # boundary -- the clip kernels share the chip with the pass queued behind them and finish together with it, and
-            # the next pass was only queued after the host had consumed the group (2-3 ms of whole-GPU idle per boundary in
-            # the HIP trace, tools/trace_gaps.py)
-            while len(states) < NR and plan_next():
-                pass
-            send_tail()
-            cur = states.popleft()
-            cache, T = cur["cache"], cur["T"]
-            group = clips[cur["i"]:cur["j"]]
-            dr = cur.get("dec_ready") if cuda else None
-            if cuda:
-                clip_stream.wait_event(dr if dr is not None else cur["ready"])
-            starts = rows_of(cur, group)
-            if strad and T == Tn and (cur["j"] >= len(clips) or clips[cur["j"]][1] - clips[cur["j"]][0] != Tn):
-                # the last full-length group of the chunk: the straddling clips join it.  Cache rows [0, T-1) = the left neighbour's
-                # last T-1 frames, directly in front of this chunk's first frame
-                enc_h, mf_h = halo.head()                      # (waits for the neighbour's message on this stream)
-                self._cache_from_tokens(enc_h, mf_h, geo, bufs[cur["b"]], 0)
-                starts = starts + rows_of(cur, strad)
-                group = group + strad
-                strad = []
-            outs = cur.pop("outs", None)
-            if outs is None:
-                # side_streams=False (the sharded schedule): HIP multiplexes its streams onto 4 hardware queues, and with RCCL's stream
-                # and the replay thread's tracker stream in play the decoder's instance-chain stream lands on a queue behind the frame
-                # stream's long GEMMs -- 616 against 708 frames/s per rank (tools/hwq_ab2.sh; GPU_MAX_HW_QUEUES=8 recovers most of it,
-                # 697, but costs the single-GPU path 1.6 %)
-                outs = eng.decode_clips(cache, starts, T, geo, two_streams=side_streams)
-            elif cuda:
-                clip_stream.wait_stream(self._ahead_stream)        # decoded ahead (below) on the auxiliary stream
-                for v in outs.values():
-                    v.record_stream(clip_stream)
-            # Decode-ahead: a following group that needs NO new frame pass -- the short clips at the end of a video, whose frames the
-            # last pass has already produced -- is decoded now, on an auxiliary stream beside this group's decoder, instead of after
-            # this group's inference_clip syncs and tracker run.  Both decoders are chains of small dependent launches (latency-bound
-            # at these sizes), so the second one is nearly free: the tail of a 120-frame video drops by the 2.6 ms the lone 3-frame
-            # clip took (tools/tail_time.py).  Same kernels, same inputs, same bits.
-            nx = states[0] if states else None
-            if (cuda and self.decode_ahead and side_streams and nx is not None and nx["new_frames"] == 0 and not strad and trace is None
-                    and "outs" not in nx):
-                if self._ahead_stream is None:
-                    self._ahead_stream = torch.cuda.Stream(frames_dev.device, priority=-1)
-                aux = self._ahead_stream
-                aux.wait_event(nx["ready"])                        # its frames (the pass this group waits for too)
-                with torch.cuda.stream(aux):
-                    nx["outs"] = eng.decode_clips(nx["cache"], rows_of(nx, clips[nx["i"]:nx["j"]]), nx["T"], geo)
-            if dr is not None:
-                clip_stream.wait_event(cur["ready"])               # the mask features of the group's last pass (inference_clip reads them)
-            ress = eng.inference_clips(outs, cache["mf"], starts, T)
-            ready = None
-            if cuda:
-                ready = torch.cuda.Event()
-                ready.record(clip_stream)         # the clip results are complete once this event fires
-            cur["done"] = ready                   # ... and the group no longer reads its buffer
-            for gi, ((start, end, last), res) in enumerate(zip(group, ress)):
-                if trace is not None:
-                    trace.append({k_: v.clone() for k_, v in res.items() if torch.is_tensor(v)})
-                res["ready"] = ready
-                res["batch_end"] = gi == len(group) - 1
-                yield start, end, last, res
-        if carry_ev:
-            # the tail passes no group waited for: the chunk's frames and cache are released on the caller's stream after them
-            clip_stream.wait_event(carry_ev[-1])
-        if strad:
-            raise RuntimeError("halo exchange: the chunk has no full-length group for its straddling clips (chunk_plan(..., halo_exchange=True) "
-                               "merges a short last chunk into its neighbour)")
+            yield None                            # (no clip to plan: nothing, or only the carry's tail, is queued)
+        issuer.finish()
 
     def merge_clips(self, results, frame_hw, out_size, mask_hw, n_frames=None, frame_source=None, ground_truth=None):
         """Tracker + window flushes + video merge (mdqe/mdqe.py:337-366) over clip results in global order.  frame_source: the video's

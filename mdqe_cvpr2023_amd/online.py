@@ -71,10 +71,11 @@ Style(trail=...) are drawn from the same points and need no `paths`; their histo
 """
 import contextlib
 import dataclasses
-import os
 
 import numpy as np
 import torch
+
+from .schedule import cache_budget_frames
 
 
 # ---- the schedule, as pure functions (tests/test_online_cpu.py drives them without a GPU) --------------------------------------------
@@ -289,8 +290,7 @@ class OnlineVideo:
                                  matte=self.matte)
         shapes = model.engine.cache_shapes(self.geo)
         per_frame = 4 * sum(int(np.prod(sh)) for sh in shapes.values())
-        forced = int(os.environ.get("MDQE_CACHE_FRAMES", "0"))
-        budget = forced if forced > 0 else int(model.CACHE_GB * 2 ** 30 // max(per_frame, 1))
+        budget = cache_budget_frames(per_frame, model.CACHE_GB)
         self.chunk = max(1, budget - (self.T - 1))   # frames of one iter_clip_results call: chunk + carry fit one cache buffer
 
     def _run(self, frames_dev, h2d, clips, offset):
