@@ -881,6 +881,48 @@ int mdqe_render_trails_yuv420sp(void* y, long y_pitch, long y_stride, void* uv, 
                                 const int* pts, long pts_row_stride, int p_off, int n, int trail, int width,
                                 const unsigned short* palette_yuv, void* stream);
 
+/* Track outlines (csrc/polygons.hip): the label map's visible regions as polygons, traced on the device.  A fourth consumer of the
+ * label map.  labels: uint8 [F, Ho, Wo] as mdqe_final_label_map_u8 writes it, 0 = background, row k's label is k + 1; rows k = 0..n-1
+ * are traced and a label above n is "not this region", as in mdqe_label_centroids_u8.  Integers only, ONE definition:
+ *   lattice   vertices (X, Y), 0 <= X <= Wo, 0 <= Y <= Ho; pixel (x, y) covers the square (x, y)..(x + 1, y + 1); X goes right, Y down.
+ *   edges     for label v in frame f let R be the pixels that hold v.  Every unit crack between a pixel of R and a pixel outside R (or
+ *             outside the picture) is a directed edge with R on its RIGHT.  For pixel (x, y) of R:
+ *               top,    if (x, y-1) is not in R: (x, y)     -> (x+1, y),   heading E;
+ *               right,  if (x+1, y) is not in R: (x+1, y)   -> (x+1, y+1), heading S;
+ *               bottom, if (x, y+1) is not in R: (x+1, y+1) -> (x, y+1),   heading W;
+ *               left,   if (x-1, y) is not in R: (x, y+1)   -> (x, y),     heading N.
+ *   successor among the edges of the same label and frame that leave the head vertex: the right turn before straight on before the left
+ *             turn.  A bijection on the edges, so they fall into closed rings; regions are 4-connected; a ring may touch itself at a
+ *             vertex (a pinch), visits a vertex at most twice and never crosses itself.
+ *   vertices  a ring's vertices are the tails of those of its edges whose predecessor has another heading: the corners only, collinear
+ *             points dropped.  Every ring has an even number of them, at least 4.
+ *   order     a corner's key is (f, Y, X, heading out) with E < S < W < N.  A ring starts at its smallest corner and is listed along the
+ *             successors; the rings of a call are listed by ascending start key, whatever their label, and each names its row.
+ *   holes     a ring is a hole exactly when its start corner's heading out is S; an outer ring's is E.  With A2 = sum(x_i * y_{i+1} -
+ *             x_{i+1} * y_i) over a ring, outer rings have A2 > 0, holes A2 < 0, and the A2 of the rings of (k, f) sum to twice the
+ *             region's pixel count; an even-odd fill of them is the region.
+ *   min_area  the rings of a region (k, f) of fewer than max(1, min_area) pixels are left out entirely (counted by a pass of this entry's
+ *             own, made only for min_area > 1).
+ * xy: int32 [cap_vertices, 2], (X, Y), ring after ring in ring order; rings: int32 [cap_rings, 5], (row k, frame f, first vertex, vertex
+ * count, hole 0|1); totals: int32 [2], the TRUE vertex and ring counts whatever the caps.  Both outputs are fully overwritten up to the
+ * counts, identical from run to run (every index comes from a scan; the only atomics count).  Where either count exceeds its cap, xy and
+ * rings hold unspecified data inside their caps and nothing is written outside them: call again with the true counts.
+ * The launches are in csrc/polygons.hip's head: mark and count corners per lattice vertex from an LDS tile of labels, scan, link each
+ * corner to its successor along its straight run, rank by ceil(log2(cap_vertices)) rounds of pointer jumping (a number the host fixes
+ * from the cap), scan the ring starts and sizes, emit.  No workgroup waits for another inside a launch.  workspace: at least
+ * mdqe_label_polygons_workspace(F, Ho, Wo, cap_vertices) bytes (-1 for sizes the entry refuses), 16-byte aligned, device memory, one per
+ * stream; it holds 2 bytes per lattice vertex and 45 per vertex of the cap.  Never allocates, never synchronises.
+ * MDQE_EINVAL, before any pointer is looked at, for n outside 0..255, min_area < 0, F < 0, Ho or Wo <= 0 or > 16384, F*Ho*Wo >= 2^31 - 1,
+ * cap_vertices outside 1..2^26, cap_rings outside 1..2^24, and a workspace that is too small.  n == 0 or F == 0 write totals = (0, 0),
+ * which is all they launch; NULL totals, and then NULL labels, xy, rings or workspace, give MDQE_ENULL. */
+int mdqe_label_polygons_u8(const unsigned char* labels, int F, int Ho, int Wo, int n, int min_area,
+                           int cap_vertices, int cap_rings,
+                           int* xy,        /* [cap_vertices, 2]: (X, Y), ring after ring in ring order */
+                           int* rings,     /* [cap_rings, 5]: (row k, frame f, first vertex, vertex count, hole 0|1) */
+                           int* totals,    /* [2]: the TRUE vertex and ring counts, whatever the caps */
+                           void* workspace, long workspace_bytes, void* stream);
+long mdqe_label_polygons_workspace(int F, int Ho, int Wo, int cap_vertices);
+
 /* ---- COCO single-image branch, after the decoder (MDQE.inference_image, mdqe/mdqe.py:486-556), on the centre frame's
  * low-resolution logits [n,Hm,Wm]; aligned_bilinear x`factor` in closed form, crop [:h,:w].
  * stats[k] = {sum(sigmoid*[sigmoid>0.5]), count(sigmoid>0.5), xmin, ymin, xmax, ymax of (logit > 0)} (:512-516, :526;

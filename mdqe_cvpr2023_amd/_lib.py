@@ -66,6 +66,7 @@ SIGNATURES = {
     "mdqe_track_crops_u8": [p, i, l, i, i, p, i, i, i, p, i, i, i, i, i, i, i, i, i, p, l, i, p, l, p],
     "mdqe_track_crops_yuv420sp": [p, l, l, p, l, l, i, i, i, i, i, i, p, i, i, i, p, i, i, i, i, i, i, i, i, i, p, l, i, p, l, p],
     "mdqe_label_centroids_u8": [p, i, i, i, i, i, p, p, l, i, p],
+    "mdqe_label_polygons_u8": [p, i, i, i, i, i, i, i, p, p, p, p, l, p],
     "mdqe_render_trails_u8": [p, i, i, i, i, p, l, i, i, i, i, p, p],
     "mdqe_render_trails_yuv420sp": [p, l, l, p, l, l, i, i, i, i, i, p, l, i, i, i, i, p, p],
     "mdqe_final_masks_overlap": [p, i, p, i, i, i, i, i, i, i, i, p, i, i, p, l, p, p],
@@ -175,6 +176,8 @@ def load_library(path=None):
     h.mdqe_groupnorm_workspace_bytes.argtypes = [c_int, c_int]
     h.mdqe_winograd_workspace_bytes.restype = c_long
     h.mdqe_winograd_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    h.mdqe_label_polygons_workspace.restype = c_long
+    h.mdqe_label_polygons_workspace.argtypes = [c_int, c_int, c_int, c_int]
     for name, args in SIGNATURES.items():
         fn = getattr(h, name)          # AttributeError if the symbol is missing: loud by design
         fn.argtypes = args

@@ -5,7 +5,8 @@ planes (dense or run boundaries), the label map (one uint8 plane per frame that 
 disjoint between windows, so it needs no `stitch`), its overlay (that map painted over the frames the caller handed in, `FrameStore`,
 uint8 [F, Ho, Wo, 3]), per-track crops cut from those frames along the map's visible regions (`crop_frames`, render.Crops; offline they
 gather in one device table per video, `CropTable`), the tracks' paths (the centroid of each visible region per frame, kept over the
-windows in a `PathTable`: an output, and what an overlay's trails are drawn from) and whose geometry.  A flushed window becomes those forms in ONE function,
+windows in a `PathTable`: an output, and what an overlay's trails are drawn from), the tracks' outline polygons (the rings around each
+visible region, traced on the device and brought to the host per window: `polygon_rings`, polygons.TrackPolygons) and whose geometry.  A flushed window becomes those forms in ONE function,
 `build_window`; the three paths differ in the destination only: per window into per-video pinned memory (`_early_masks`), per window
 as a record (`_online_window`), or all windows into whole-video device buffers with one copy at the end (`video_result`).  Shared
 beside it: `to_host` (the hop on the copy stream), `rle.positions_to_rles`, `stitch`, `result_head` / `track_geometry` (a result's keys).
@@ -33,14 +34,16 @@ class Forms:
     surface: bool = False                 # the overlay is painted onto the decoder surfaces handed in: a YuvFrames, not RGB pixels
     crops: bool = False                   # per-track chips cut from the frames (render.Crops; the map and its table: a device scratch if not returned)
     paths: bool = False                   # per-track centroids and moments of the map's visible regions (PathTable; the map: a device scratch if not returned)
+    polygons: bool = False                # per-track outline polygons of the map's visible regions (polygons.Polygons; the map: a device scratch if not returned)
     matte: bool = False                   # the soft matte of the window's tracks, one uint8 plane per frame (render.Matte), beside any other form
 
     @classmethod
-    def _of(cls, model, geometry, planes, labels, overlay, early_always=False, surface=False, crops=False, paths=False, matte=False):
+    def _of(cls, model, geometry, planes, labels, overlay, early_always=False, surface=False, crops=False, paths=False, matte=False,
+            polygons=False):
         """geometry None: the model's flag.  It describes the planes where there are planes, and the labels' regions where the map is returned."""
         g = bool(getattr(model, "geometry_output", False) if geometry is None else geometry)
         return cls(planes, labels, overlay, g and planes is not None, g and labels, early_always, bool(overlay and surface), bool(crops),
-                   bool(paths), bool(matte))
+                   bool(paths), matte=bool(matte), polygons=bool(polygons))
 
     @classmethod
     def of_model(cls, model, emit_masks=True, geometry=None):
@@ -51,15 +54,15 @@ class Forms:
         pic = getattr(model, "overlay_output", False)
         return cls._of(model, geometry, None if lab == "only" else "rle" if rle else "dense", bool(lab), bool(pic), rle, pic == "surface",
                        getattr(model, "crop_output", None) is not None, bool(getattr(model, "path_output", False)),
-                       getattr(model, "matte_output", None) is not None)
+                       getattr(model, "matte_output", None) is not None, getattr(model, "polygon_output", None) is not None)
 
     @classmethod
-    def of_emit(cls, emit, geometry=False, model=None, surface=False, crops=False, paths=False, matte=False):
+    def of_emit(cls, emit, geometry=False, model=None, surface=False, crops=False, paths=False, matte=False, polygons=False):
         """Online ("masks" | "rle" | "labels" | "overlay"; surface: the overlay onto the surfaces pushed; crops: chips beside it; paths:
-        centroids and moments beside it)."""
+        centroids and moments beside it; polygons: outline polygons beside it)."""
         lab = emit in ("labels", "overlay")
         return cls._of(model, geometry, None if lab else {"masks": "dense", "rle": "rle"}[emit], lab, emit == "overlay", surface=surface,
-                       crops=crops, paths=paths, matte=matte)
+                       crops=crops, paths=paths, matte=matte, polygons=polygons)
 
 
 def dense_masks(m, idx, stride, frame_hw, out_size, geometry, out, f_off):
@@ -512,6 +515,45 @@ def rle_positions(m, idx, stride, frame_hw, out_size, geometry):
     return pos[:, :max(mx, 1)].cpu().numpy(), n_pos.cpu().numpy(), geom.view(int(idx.numel()), int(m.shape[1]), 5).cpu() if geometry else None
 
 
+def polygon_rings(labels, l_off, n, nf, out_size, spec, cls, f0):
+    """The outline polygons of a window's n rows from its label map labels[l_off:l_off + nf], on the host -> polygons.TrackPolygons with
+    f in video frames (the window starts at f0) and k the window's row; the only caller of ops.label_polygons.  `spec`
+    (polygons.Polygons): its min_area goes to the kernel; `every` and `classes` (by the window's class rows `cls`, on the host)
+    filter the ring records here and xy is compacted.  Like `rle_positions` the size depends on the data: the default caps, one host
+    sync on the true totals, one more call with them as caps where they overflow, then exactly `totals` rows to pinned host memory
+    behind a second sync."""
+    from . import ops
+    from .polygons import TrackPolygons, select_rings
+    size = (int(out_size[0]), int(out_size[1]))
+    if not n or not nf:
+        return TrackPolygons(torch.zeros((0, 2), dtype=torch.int32).numpy(), torch.zeros((0, 5), dtype=torch.int32).numpy(), size)
+    lab = labels[l_off:l_off + nf]
+    xy, rings, totals = ops.label_polygons(lab, n, spec.min_area)
+    V, R = (int(v) for v in totals.tolist())                       # the one sync the data's size takes
+    if V > xy.shape[0] or R > rings.shape[0]:
+        xy, rings, totals = ops.label_polygons(lab, n, spec.min_area, max(V, 1), max(R, 1))
+    host = (torch.empty((V, 2), dtype=torch.int32, pin_memory=bool(V)), torch.empty((R, 5), dtype=torch.int32, pin_memory=bool(R)))
+    if V:
+        host[0].copy_(xy[:V], non_blocking=True)
+        host[1].copy_(rings[:R], non_blocking=True)
+        torch.cuda.current_stream(lab.device).synchronize()
+    hx, hr = host[0].numpy(), host[1].numpy().copy()
+    hx, hr = select_rings(hx, hr, spec.keep(hr, f0, cls, n))
+    hr[:, 1] += int(f0)
+    return TrackPolygons(hx, hr, size)
+
+
+def polygon_result(rows, out_size, parts):
+    """{"pred_polygons": polygons.TrackPolygons} of a whole video from its windows' (`parts`, in video order; k = tracker row): k becomes
+    the output j with rows[j] == k -- the FIRST such j where a track stands behind several outputs -- and the rings of a track that
+    misses the selection are dropped, as rle.labels_keep drops its label."""
+    from .polygons import TrackPolygons
+    table = {}
+    for j, r in enumerate(rows):
+        table.setdefault(int(r), j)
+    return {"pred_polygons": TrackPolygons.concat([p.renumbered(table) for p in parts], size=out_size)}
+
+
 def matte_planes(m, stride, frame_hw, out_size, spec, cls, out, f_off):
     """The matte output of window logits m [n, F, Hm, Wm] into out[f_off:f_off + F] (uint8 [>= f_off + F, Ho, Wo], device): the union
     matte of ALL n rows, or with spec.classes (render.Matte) of the rows those classes select by the window's class rows `cls`; n = 0:
@@ -524,7 +566,7 @@ def matte_planes(m, stride, frame_hw, out_size, spec, cls, out, f_off):
 
 
 def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels=None, picture=None, paint=None,
-                 hop=lambda stage, geom: geom, crops=None, paths=None, matte=None):
+                 hop=lambda stage, geom: geom, crops=None, paths=None, matte=None, polygons=None):
     """What `forms` asks for of ONE flushed window (logits m [n, F, Hm, Wm]), on the current stream, for every path; the only caller
     of `overlay_frames`, `label_maps`, `dense_masks` and `rle_positions`.  First the label map of ALL n rows into labels = (device
     buffer, frame offset) and, with picture = (buffer, offset), its overlay, painted from paint = (FrameStore, first video frame,
@@ -536,8 +578,12 @@ def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels
     paths (a PathTable, `begin` called for this window): behind the label map the window's centroids (`PathTable.run`), which the
     overlay's trail pass draws and, with forms.paths, the stage "paths" sends on; the map is then made whether or not it is returned.
     matte = (render.Matte, the window's class rows on the host, buffer, offset): the window's matte (`matte_planes`), stage "matte".
-    -> (labels' geometry table [n, F, 5] or None, planes' table [len(rows), F, 5] or None, (pos, n_pos) of `rle_positions` or None)."""
-    lgeom = pgeom = runs = None
+    polygons = (polygons.Polygons, the window's class rows on the host, first video frame): behind the labels stage the outlines of
+    the map's visible regions (`polygon_rings`: they come to the host there), stage "polygons"; the map is then made whether or not it is
+    returned.
+    -> (labels' geometry table [n, F, 5] or None, planes' table [len(rows), F, 5] or None, (pos, n_pos) of `rle_positions` or None,
+    the window's TrackPolygons or None)."""
+    lgeom = pgeom = runs = poly = None
     if labels is not None:
         table = forms.label_geometry or crops is not None
         if picture is not None:
@@ -553,6 +599,9 @@ def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels
             spec, source, f0, chips, rects, c_off = crops
             crop_frames(int(m.shape[0]), int(m.shape[1]), *labels, dgeom, source, f0, spec, chips, rects, c_off)
             hop("crops", None)
+        if polygons is not None:
+            poly = polygon_rings(*labels, int(m.shape[0]), int(m.shape[1]), out_size, *polygons)
+            hop("polygons", None)
     if matte is not None:
         matte_planes(m, stride, frame_hw, out_size, *matte)
         hop("matte", None)
@@ -561,7 +610,7 @@ def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels
             pgeom = hop("planes", dense_masks(m, rows, stride, frame_hw, out_size, forms.plane_geometry, *planes))
         elif forms.planes == "rle":
             *runs, pgeom = rle_positions(m, rows, stride, frame_hw, out_size, forms.plane_geometry)
-    return lgeom, pgeom, runs
+    return lgeom, pgeom, runs, poly
 
 
 def copy_stream(model):
@@ -648,6 +697,7 @@ class EarlyMasks:
     label_geom: list = dataclasses.field(default_factory=list)        # per window, as `geom`, of the labels' visible regions
     overlay: object = None                                            # overlay: ONE pinned uint8 [L, Ho, Wo, 3] per video (model.overlay_output)
     matte: object = None                                              # matte: ONE pinned uint8 [L, Ho, Wo] per video (model.matte_output)
+    polygons: list = dataclasses.field(default_factory=list)          # per window, its TrackPolygons (k = tracker row; model.polygon_output)
 
 
 def result_head(model, cls_clips, out_size, n_frames, score=None, track_ids=True):
@@ -694,12 +744,13 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
         elif forms.planes:
             planes_res = {"pred_masks": [early.hosts[i].view(torch.bool)[:n_frames] for i in inst]}
         host = {"labels": early.labels, "overlay": early.overlay, "matte": early.matte}
+        polys = early.polygons
     else:
         sel = sorted(set(inst))
         rows = [sel.index(i) for i in inst]                        # rows of the planes' buffer = positions in sel
-        plane_geoms, label_geoms, u8 = [], [], dict(dtype=torch.uint8, device=model.device)
+        plane_geoms, label_geoms, polys, u8 = [], [], [], dict(dtype=torch.uint8, device=model.device)
         # (the windows tile [0, n_frames): every row of the map and the picture is written; a track's planes start at its first window)
-        d_lab = torch.empty(n_frames, Ho, Wo, **u8) if forms.labels or forms.overlay or forms.crops or forms.paths else None
+        d_lab = torch.empty(n_frames, Ho, Wo, **u8) if forms.labels or forms.overlay or forms.crops or forms.paths or forms.polygons else None
         if forms.crops:
             crops = CropTable(model.crop_output, n_frames, model.device)
         paths = path_table(forms, model.overlay_style if forms.overlay else None, model.device, keep=forms.paths)
@@ -715,10 +766,13 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
             at = [None if t is None else (t, f_off) for t in (d_planes, d_lab, d_pic)]
             if paths is not None:
                 paths.begin(n, nf)
-            lg, pg, _ = build_window(m, forms, sel_dev[:cnt] if forms.planes else None, model.cfg.match_stride, frame_hw, out_size, *at,
+            lg, pg, _, poly = build_window(m, forms, sel_dev[:cnt] if forms.planes else None, model.cfg.match_stride, frame_hw, out_size, *at,
                                      paint=(frame_source, f_off, model.overlay_style, cls_clips[i]) if forms.overlay else None,
                                      crops=(crops.spec, frame_source, f_off, *crops.rows(n), crops.spec.count(f_off)) if forms.crops else None,
-                                     paths=paths, matte=(model.matte_output, cls_clips[i], d_mat, f_off) if forms.matte else None)
+                                     paths=paths, matte=(model.matte_output, cls_clips[i], d_mat, f_off) if forms.matte else None,
+                                     **({"polygons": (model.polygon_output, cls_clips[i], f_off)} if forms.polygons else {}))
+            if forms.polygons:
+                polys.append(poly)
             if paths is not None:
                 paths.keep(f_off)
             label_geoms.append((f_off, nf, n, lg))
@@ -744,7 +798,7 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
                 planes_res = {"pred_rles": [enc[p] for p in rows]}
             else:
                 planes_res = {"pred_masks": [planes[p] for p in rows]}
-    if forms.labels or forms.overlay or forms.crops or forms.paths or forms.matte:
+    if forms.labels or forms.overlay or forms.crops or forms.paths or forms.matte or forms.polygons:
         res.setdefault("pred_track_ids", list(inst))
     if forms.matte:
         res["pred_matte"] = host["matte"][:n_frames]
@@ -752,6 +806,8 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
         res.update(crops.result(inst))
     if forms.paths:
         res.update(paths.result(inst, n_frames))
+    if forms.polygons:
+        res.update(polygon_result(inst, out_size, polys))
     if forms.labels:
         res["pred_label_map"] = host["labels"][:n_frames]
     if forms.overlay:
@@ -773,7 +829,7 @@ class ClipMerger:
     EARLY_TRACKS = 48                       # tracks per video the early-mask path budgets pinned memory for
 
     def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True, online=None, geometry=None, frame_source=None,
-                 style=None, ground_truth=None, surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None):
+                 style=None, ground_truth=None, surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None, polygons=None):
         self.model, self.frame_hw, self.out_size, self.mask_hw = model, frame_hw, out_size, mask_hw
         self.emit_masks = emit_masks                # False: scores / labels only (ranks > 0 of a sharded video)
         # online ("masks" | "rle" | "labels" | "overlay"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their
@@ -787,7 +843,10 @@ class ClipMerger:
         # paths: an online session's; offline the model's path_output
         # matte (render.Matte): an online session's; offline the model's matte_output
         self.matte_spec = matte if online else (getattr(model, "matte_output", None) if emit_masks else None)
-        self.forms = forms = (Forms.of_emit(online, geometry, model, surface, self.crop_spec is not None, bool(paths), matte is not None) if online
+        # polygons (polygons.Polygons): an online session's; offline the model's polygon_output
+        self.polygon_spec = polygons if online else (getattr(model, "polygon_output", None) if emit_masks else None)
+        self.forms = forms = (Forms.of_emit(online, geometry, model, surface, self.crop_spec is not None, bool(paths), matte is not None,
+                                            self.polygon_spec is not None) if online
                               else Forms.of_model(model, emit_masks, geometry))
         self.crop_table = None                      # the early path's CropTable, from its first window
         self.path_table = None                      # the early and the online path's PathTable, from their first window
@@ -916,7 +975,7 @@ class ClipMerger:
         -> build_window's."""
         forms, u8 = self.forms, dict(dtype=torch.uint8, device=self.dev)
         n, nf, Ho, Wo = int(m.shape[0]), int(m.shape[1]), int(self.out_size[0]), int(self.out_size[1])
-        lab = torch.empty(nf, Ho, Wo, **u8) if forms.labels or forms.overlay or forms.crops or forms.paths else None    # (an overlay, crops or paths alone: a scratch, not copied)
+        lab = torch.empty(nf, Ho, Wo, **u8) if forms.labels or forms.overlay or forms.crops or forms.paths or forms.polygons else None    # (an overlay, crops, paths or polygons alone: a scratch, not copied)
         pic = torch.empty(nf, Ho, Wo, 3, **u8) if forms.overlay and not forms.surface else None
         if forms.surface:                           # (the host's pitch: the window copy is then two plain copies, padding and all)
             pic = surface_picture(self.frame_source, nf, self.out_size, self.dev, self.surface_pitch_align)
@@ -924,7 +983,7 @@ class ClipMerger:
         planes = torch.empty(n, nf, Ho, Wo, **u8) if rows is not None and forms.planes == "dense" else None
         mat = torch.empty(nf, Ho, Wo, **u8) if forms.matte else None
         copies = {"labels": (pairs("labels", lab) if forms.labels else []) + (pairs("overlay", pic) if forms.overlay else []),
-                  "planes": pairs("planes", planes) if planes is not None else [], "crops": [], "paths": [],
+                  "planes": pairs("planes", planes) if planes is not None else [], "crops": [], "paths": [], "polygons": [],
                   "matte": pairs("matte", mat) if mat is not None else []}
         crop = None
         if forms.crops:
@@ -953,6 +1012,7 @@ class ClipMerger:
         out = build_window(m, forms, rows, self.model.cfg.match_stride, self.frame_hw, self.out_size, *at,
                            paint=(self.frame_source, self.f_off, self.style, c), crops=crop, paths=self.path_table,
                            matte=(self.matte_spec, c, mat, 0) if mat is not None else None,
+                           **({"polygons": (self.polygon_spec, c, self.f_off)} if forms.polygons else {}),
                            hop=lambda stage, geom: (to_host(cs, self.side, copies[stage], geom, event())
                                                     if copies[stage] or geom is not None else None))   # (a scratch stage: nothing to send)
         if self.path_table is not None:
@@ -986,7 +1046,9 @@ class ClipMerger:
             if getattr(early, kind) is None:
                 setattr(early, kind, model.pinned_mask_buffer(shape + (3,) * (kind == "overlay")))
             return [(getattr(early, kind)[f0:f0 + nf], buf)]
-        lgeom, pgeom, runs = self._window_to_host(m, pairs, lambda: early.done, c)
+        lgeom, pgeom, runs, poly = self._window_to_host(m, pairs, lambda: early.done, c)
+        if forms.polygons:
+            early.polygons.append(poly)
         if forms.label_geometry:
             early.label_geom.append((f0, nf, n, lgeom))
         if runs is not None:
@@ -1018,7 +1080,9 @@ class ClipMerger:
         def event():                                # (None stays where nothing is copied: RLE, or a window without tracks)
             rec["ready"] = rec["ready"] or torch.cuda.Event()
             return rec["ready"]
-        lgeom, pgeom, runs = self._window_to_host(m, pairs, event, c)
+        lgeom, pgeom, runs, poly = self._window_to_host(m, pairs, event, c)
+        if forms.polygons:
+            rec["polygons"] = poly
         if forms.crops:
             rec["crop_frames"] = self.crop_spec.taken(self.f_off, self.f_off + nf)
         if forms.planes == "rle":

@@ -331,7 +331,10 @@ class MDQE(nn.Module):
         # True: forward() on a video adds "pred_centroids" / "pred_moments", where each output's track is in every frame, summed on the
         # device from the label map (ops.label_centroids).  False: nothing changes.  (A property: see below.)
         self.path_output = False
-        self.merge_on_cpu = None                  # None: cfg.merge_on_cpu (MODEL.MDQE.MERGE_ON_CPU); True / False override it
+        # A polygons.Polygons: forward() on a video adds "pred_polygons", the outlines of each output's visible regions as rings of
+        # lattice corners, traced on the device from the label map (ops.label_polygons).  None: nothing changes.  (A property: see below.)
+        self.polygon_output = None
+        self.merge_on_cpu = None                 # None: cfg.merge_on_cpu (MODEL.MDQE.MERGE_ON_CPU); True / False override it
         # Final masks of a tracker window leave the device when the window is flushed (pinned host buffers, copied under the later
         # windows' compute) instead of in one pass + one 100-MB copy after the last window.  Independent of MERGE_ON_CPU, which in the
         # reference only picks the device the window results wait on (mdqe/mdqe.py:185-186,337,354-355) and never changes an output.
@@ -556,6 +559,25 @@ class MDQE(nn.Module):
         if value:
             self.check_label_capacity()
         self.__dict__["_path_output"] = value
+
+    @property
+    def polygon_output(self):
+        """None, or a polygons.Polygons: forward() on a video adds "pred_polygons" (a polygons.TrackPolygons on the host: per output
+        and taken frame the closed rings of lattice corners around the track's visible region of the label map, holes flagged --
+        include/mdqe_hip.h's rule, traced on the device by ops.label_polygons window by window, a few KB each; row k of a ring is
+        output k of "pred_track_ids", and a track behind several outputs has its rings under the first) and "pred_track_ids".  Beside
+        every other output form, on either mask path; the label map is then made whether or not it is returned, and the bits of the
+        other outputs are left alone.  Videos only, one device (sharding.py refuses it).  None: nothing changes."""
+        return self.__dict__.get("_polygon_output", None)
+
+    @polygon_output.setter
+    def polygon_output(self, value):
+        from .polygons import Polygons
+        if value is not None and not isinstance(value, Polygons):
+            raise ValueError("polygon_output must be None or a polygons.Polygons, got %r" % (value,))
+        if value is not None:
+            self.check_label_capacity()
+        self.__dict__["_polygon_output"] = value
 
     @property
     def overlay_style(self):
@@ -1003,7 +1025,7 @@ class MDQE(nn.Module):
             yield guarded(step)
 
     def online_video(self, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None,
-                     surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None):
+                     surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None, polygons=None):
         """An online session over ONE video whose frames arrive in pushes (a camera, a stream, a video too long to hold): push()
         returns each tracker window as soon as it is final, close() the rest, result() the video-level scores / labels / tracks.
         height / width: output mask size (default: the frame size); emit: "masks" (bool [n, F, H, W] per window), "rle" or "labels" (one
@@ -1018,10 +1040,13 @@ class MDQE(nn.Module):
         `crop_frames`, one fixed-size picture per track and taken frame (`crop_output`'s); paths (a bool, beside any emit): every
         window carries `centroids` / `moments` of its tracks' visible regions and, with keep, result() "pred_centroids" /
         "pred_moments" (`path_output`'s); matte (render.Matte, beside any emit): every window carries `matte`, uint8 [F, H, W], the soft
-        matte of its tracks, and with keep result() "pred_matte" (`matte_output`'s).  See online.py."""
+        matte of its tracks, and with keep result() "pred_matte" (`matte_output`'s); polygons (polygons.Polygons, beside any emit): every
+        window carries `polygons`, a polygons.TrackPolygons of its tracks' outlines, and with keep result() "pred_polygons"
+        (`polygon_output`'s).  See online.py."""
         from .online import OnlineVideo
         return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep, geometry=geometry, style=style, ground_truth=ground_truth,
-                           surface=surface, surface_pitch_align=surface_pitch_align, crops=crops, paths=paths, matte=matte)
+                           surface=surface, surface_pitch_align=surface_pitch_align, crops=crops, paths=paths, matte=matte,
+                           polygons=polygons)
 
     def inference_image(self, batched_inputs):
         """COCO single-image branch: MDQE.forward :213-236 -> mdqe.forward (models/mdqe.py:62-70) -> decoder
@@ -1047,6 +1072,9 @@ class MDQE(nn.Module):
         if getattr(self, "path_output", False):
             raise ValueError("path_output: the COCO image branch has no paths (track centroids are a video output: use a video config, or "
                              "set path_output = False)")
+        if getattr(self, "polygon_output", None) is not None:
+            raise ValueError("polygon_output: the COCO image branch has no polygons (track outlines are a video output: use a video config, "
+                             "or set polygon_output = None)")
         from .preprocess import YuvFrames
         if isinstance(item["image"], YuvFrames):
             raise ValueError("YuvFrames: the COCO image branch takes RGB tensors (decoder surfaces are a video input; convert one with "

@@ -68,6 +68,10 @@ the track's visible region of the label map, ((SX + m/2) / m, (SY + m/2) / m) in
 every emit).  keep=True adds "pred_centroids" / "pred_moments" to result(), equal to forward()'s with model.path_output.  The trails of
 Style(trail=...) are drawn from the same points and need no `paths`; their history is a device table of `trail` columns
 (merge.PathTable), so lines continue across windows and pushes and nothing grows with the video.
+polygons=Polygons(...) (polygons.py), beside ANY emit: every window also carries `win.polygons`, a polygons.TrackPolygons of the outlines
+of its tracks' visible regions of the label map -- rings of lattice corners, traced on the device (ops.label_polygons; the map is then
+made for every emit), a few KB per window; f counts video frames, k is the window's row.  keep=True adds "pred_polygons" to result(),
+equal to forward()'s with model.polygon_output.
 """
 import contextlib
 import dataclasses
@@ -160,7 +164,9 @@ class Window:
     and `crop_frames`, the Fc video frames taken (pseudo-fields of the same kind).  In a session with paths=True: `centroids` int32 [n,
     f1-f0, 2], (x, y) of each track's visible region of the label map per frame, (-1, -1) where it has none, and `moments` int64 [n,
     f1-f0, 3], its (pixels, sum of X, sum of Y) (pseudo-fields of the same kind).  In a session with matte=: `matte` uint8 [f1-f0, H, W]
-    on pinned host, the soft matte of the window's tracks (render.Matte; a pseudo-field of the same kind)."""
+    on pinned host, the soft matte of the window's tracks (render.Matte; a pseudo-field of the same kind).  In a session with
+    polygons=: `polygons`, a polygons.TrackPolygons of the outlines of the window's tracks, f in video frames, k the window's row (a
+    pseudo-field of the same kind)."""
     frames: tuple
     track_ids: list
     cls_probs: torch.Tensor
@@ -176,9 +182,11 @@ class Window:
     centroids: dataclasses.InitVar[torch.Tensor] = None
     moments: dataclasses.InitVar[torch.Tensor] = None
     matte: dataclasses.InitVar[torch.Tensor] = None
+    polygons: dataclasses.InitVar[object] = None
 
-    def __post_init__(self, labels, overlay, crops, crop_rects, crop_frames, centroids, moments, matte):
+    def __post_init__(self, labels, overlay, crops, crop_rects, crop_frames, centroids, moments, matte, polygons=None):
         self.matte = matte
+        self.polygons = polygons
         self.labels = labels
         self.overlay = overlay
         self.crops, self.crop_rects, self.crop_frames = crops, crop_rects, crop_frames
@@ -187,7 +195,7 @@ class Window:
 
 class OnlineVideo:
     def __init__(self, model, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None,
-                 surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None):
+                 surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None, polygons=None):
         if emit not in ("masks", "rle", "labels", "overlay"):
             raise ValueError("online_video: emit must be 'masks', 'rle', 'labels' or 'overlay'")
         if not isinstance(surface, bool):
@@ -219,7 +227,14 @@ class OnlineVideo:
             if model.cfg.is_coco:
                 raise ValueError("online_video: matte with a COCO image config: the soft matte is a video output (use a video config)")
         self.matte = matte
-        if emit in ("labels", "overlay") or crops is not None or paths or matte is not None:
+        if polygons is not None:
+            from .polygons import Polygons
+            if not isinstance(polygons, Polygons):
+                raise ValueError("online_video: polygons must be a polygons.Polygons, got %s" % type(polygons).__name__)
+            if model.cfg.is_coco:
+                raise ValueError("online_video: polygons with a COCO image config: track outlines are a video output (use a video config)")
+        self.polygons = polygons
+        if emit in ("labels", "overlay") or crops is not None or paths or matte is not None or polygons is not None:
             model.check_label_capacity()
         from .render import Style
         if style is not None and (emit != "overlay" or not isinstance(style, Style)):
@@ -287,7 +302,7 @@ class OnlineVideo:
         self.merger = ClipMerger(model, self.hw, self.out_size, self.mask_hw, n_frames=None, online=self.emit,
                                  geometry=self.geometry, frame_source=self.store, style=self.style, ground_truth=self.ground_truth,
                                  surface=self.surface, surface_pitch_align=self.surface_pitch_align, crops=self.crops, paths=self.paths,
-                                 matte=self.matte)
+                                 matte=self.matte, polygons=self.polygons)
         shapes = model.engine.cache_shapes(self.geo)
         per_frame = 4 * sum(int(np.prod(sh)) for sh in shapes.values())
         budget = cache_budget_frames(per_frame, model.CACHE_GB)
@@ -320,7 +335,7 @@ class OnlineVideo:
                               masks=r.get("masks"), rles=r.get("rles"), boxes=boxes, areas=areas, labels=r.get("labels"),
                               overlay=r.get("overlay"), crops=r.get("crops"), crop_rects=r.get("crop_rects"),
                               crop_frames=r.get("crop_frames"), centroids=r.get("centroids"), moments=r.get("moments"),
-                              matte=r.get("matte")))
+                              matte=r.get("matte"), polygons=r.get("polygons")))
         del self.merger.emitted[:]
         if self.store is not None:
             # the chunks that lie wholly before the first frame no window has emitted are done with; what stays and may be the caller's
@@ -438,5 +453,7 @@ class OnlineVideo:
         if self.keep and forms.paths:             # (per output the track's path; absent before its first window)
             res.update(merge.path_result(inst, self.received, [(w.frames[0], w.frames[1] - w.frames[0], len(w.track_ids), w.centroids, w.moments)
                                                                for w in self.kept]))
+        if self.keep and forms.polygons:          # (the windows' rings in a row, their rows renumbered to the outputs)
+            res.update(merge.polygon_result(inst, self.out_size, [w.polygons for w in self.kept]))
         self._result = res
         return res

@@ -1308,6 +1308,48 @@ def label_centroids(labels, n, min_area=0, mom=None, pts=None, p_off=0):
     return mom, (None if pts is False else pts)
 
 
+def label_polygons(labels, n, min_area=0, cap_vertices=None, cap_rings=None):
+    """The outlines of each track's visible region: for rows k = 0..n-1 (label k + 1) and the frames f of labels (uint8 [F, Ho, Wo],
+    CUDA, contiguous: ops.final_label_map's output) the closed rings of lattice corners around the pixels that hold the label -- the
+    rule of include/mdqe_hip.h, mdqe_label_polygons_u8: the region on the right of every edge, corners only, a ring from its smallest
+    corner (f, Y, X, heading), the rings by ascending start, holes flagged.  -> (xy int32 [cap_vertices, 2]: (X, Y), ring after ring;
+    rings int32 [cap_rings, 5]: (row k, frame f, first vertex, vertex count, hole); totals int32 [2]: the TRUE vertex and ring counts),
+    all on the device.  Where a count exceeds its cap, xy and rings hold nothing of use: call again with the counts as caps
+    (merge.polygon_rings does).  Regions of fewer than max(1, min_area) pixels have no rings.  Default caps: F * 16 * (Ho + Wo) + 1024
+    vertices and a quarter of that for rings, generous for anything mask-like.  Integers only, identical from run to run; the
+    workspace is ops._workspace's; n == 0 or F == 0 write the totals and launch nothing else."""
+    # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
+    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        raise RuntimeError("label_polygons: labels must be contiguous uint8 [F, Ho, Wo]")
+    F, Ho, Wo = (int(v) for v in labels.shape)
+    if Ho < 1 or Wo < 1 or Ho > 16384 or Wo > 16384 or F * Ho * Wo >= 2 ** 31 - 1:
+        raise RuntimeError("label_polygons: Ho, Wo must be in 1..16384 with F*Ho*Wo < 2^31 - 1, got %s" % (tuple(labels.shape),))
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= 255:
+        raise RuntimeError("label_polygons: n must be an int in 0..255, got %r" % (n,))
+    if isinstance(min_area, bool) or not isinstance(min_area, int) or not 0 <= min_area <= 2 ** 31 - 1:
+        raise RuntimeError("label_polygons: min_area must be an int in 0..%d, got %r" % (2 ** 31 - 1, min_area))
+    if cap_vertices is None:
+        cap_vertices = min(F * 16 * (Ho + Wo) + 1024, 2 ** 26)
+    if cap_rings is None:
+        cap_rings = min(max(cap_vertices // 4, 1), 2 ** 24)
+    for what, v, hi in (("cap_vertices", cap_vertices, 2 ** 26), ("cap_rings", cap_rings, 2 ** 24)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= hi:
+            raise RuntimeError("label_polygons: %s must be an int in 1..%d, got %r" % (what, hi, v))
+    if not labels.is_cuda:
+        raise RuntimeError("label_polygons: labels must be a CUDA tensor, got %s" % (labels.device,))
+    xy = torch.empty((cap_vertices, 2), dtype=torch.int32, device=labels.device)
+    rings = torch.empty((cap_rings, 5), dtype=torch.int32, device=labels.device)
+    totals = torch.empty(2, dtype=torch.int32, device=labels.device)
+    with torch.cuda.device(labels.device):
+        need = int(lib.mdqe_label_polygons_workspace(F, Ho, Wo, cap_vertices))
+        if need < 0:
+            raise RuntimeError("label_polygons: no workspace for labels %s with cap_vertices = %d" % (tuple(labels.shape), cap_vertices))
+        ws = _workspace(need, labels.device)
+        check(lib.mdqe_label_polygons_u8(ptr(labels), F, Ho, Wo, n, min_area, cap_vertices, cap_rings, ptr(xy), ptr(rings), ptr(totals),
+                                         ptr(ws), ws.numel(), cur_stream(labels.device)), "label_polygons")
+    return xy, rings, totals
+
+
 def _trail_args(name, pts, n, palette, F, f_off, p_off, trail, width, table_dtypes):
     """The checks render_trails and render_trails_yuv share.  -> the point table's row stride."""
     # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)

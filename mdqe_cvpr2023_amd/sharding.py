@@ -572,6 +572,10 @@ class _Job:
         if getattr(model, "path_output", False):
             raise ValueError("path_output is not offered by the sharded driver: the centroids are summed from the label map where it is made, "
                              "window by window on one device (sum them from pred_label_map on the host, or run the video on one device)")
+        if getattr(model, "polygon_output", None) is not None:
+            raise ValueError("polygon_output is not offered by the sharded driver: the outlines are traced from the label map where it is "
+                             "made, window by window on one device (trace them from pred_label_map on the host with "
+                             "polygons.polygons_from_labels, or run the video on one device)")
         if ground_truth is not None:
             raise ValueError("ground_truth is not offered by the sharded driver: the overlap counts would have to follow the tracker replay on "
                              "rank 0 with the whole video's ground truth there (score the video on one device: model([{..., 'ground_truth': gt}]))")
