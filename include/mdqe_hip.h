@@ -923,6 +923,30 @@ int mdqe_label_polygons_u8(const unsigned char* labels, int F, int Ho, int Wo, i
                            void* workspace, long workspace_bytes, void* stream);
 long mdqe_label_polygons_workspace(int F, int Ho, int Wo, int cap_vertices);
 
+/* The redaction margin (csrc/grow.hip): a copy of the label map in which chosen labels have GROWN by up to `radius` pixels, for the
+ * overlay painters to take in place of the map (a mask under-covers hair, fingers and blurred borders).  labels: uint8 [F, Ho, Wo] as
+ * mdqe_final_label_map_u8 writes it; out: uint8 [F, Ho, Wo];
+ *   grow     uint8 [256], device: label g GROWS when g >= 1 and grow[g] != 0.  grow[0] is ignored: the background never grows;
+ *   radius   0..32, in pixels.
+ * Integers only, ONE definition, for frame f and pixel (Y, X) with l = labels[f, Y, X]:
+ *   kept       if l grows, out = l: a growing region is never overwritten;
+ *   candidates otherwise, the pixels (Y', X') of the SAME frame, inside the picture, whose label grows and for which
+ *              d2 = (Y - Y')^2 + (X - X')^2 <= radius^2 (a Euclidean disc);
+ *   pixel      without a candidate out = l; else out is the label of the candidate with the smallest pair (d2, label) in
+ *              lexicographic order: the nearest, and of equally near ones the smallest label.
+ * Growing labels spread over the background and over tracks that do not grow.  Nothing is read beyond the picture's border (no
+ * replication).  radius = 0, or a table without a growing label, gives out == labels.  A single pixel grows to 1, 5, 13, 29, 81 pixels
+ * at radius 0, 1, 2, 3, 5.  The minimum separates: a column pass keeps, per (Y, X'), the smallest (dy^2, label) over |dy| <= radius; a
+ * row pass takes the smallest (dx^2 + that dy^2, label) over |dx| <= radius and accepts d2 <= radius^2 -- exactly the definition.
+ * MDQE_EINVAL for a radius outside 0..32, a negative F, Ho or Wo, F*Ho*Wo >= 2^31 - 1 -- all before any pointer is looked at -- and,
+ * when F*Ho*Wo > 0, for a null labels, grow or out and for an out that meets labels or grow in any byte: the entry does NOT work in
+ * place, a pixel reads its neighbours' labels.  F == 0 or an empty picture returns OK and launches nothing.  Nothing needs to be
+ * aligned.  Only tiles (16 x 64 pixels) whose neighbourhood of `radius` holds a growing label are searched; the others are copied.  One
+ * launch, no global scratch, no atomics: identical from run to run.  Never allocates, never synchronises. */
+int mdqe_grow_labels_u8(const unsigned char* labels, int F, int Ho, int Wo,
+                        const unsigned char* grow /* [256], device */, int radius,
+                        unsigned char* out /* [F, Ho, Wo] */, void* stream);
+
 /* ---- COCO single-image branch, after the decoder (MDQE.inference_image, mdqe/mdqe.py:486-556), on the centre frame's
  * low-resolution logits [n,Hm,Wm]; aligned_bilinear x`factor` in closed form, crop [:h,:w].
  * stats[k] = {sum(sigmoid*[sigmoid>0.5]), count(sigmoid>0.5), xmin, ymin, xmax, ymax of (logit > 0)} (:512-516, :526;

@@ -241,7 +241,11 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
     one ops.annotate / ops.annotate_yuv launch per piece in place on the painted frames, on the same stream, with the captions made
     from `cls`; nothing is read back.  `paths` (a PathTable whose `begin` has been called for this window): the window's centroids are
     made behind the label map (`PathTable.run`), and a style with a trail (style.trails) has one ops.render_trails /
-    ops.render_trails_yuv launch per piece draw them between the painter and the annotations, so plates stay legible.
+    ops.render_trails_yuv launch per piece draw them between the painter and the annotations, so plates stay legible.  A style with a
+    margin (style.grow > 0, and a window with tracks): behind the label map (and `paths.run`) one ops.grow_labels launch dilates the
+    labels of the style's `grows` table into a fresh device scratch [F, Ho, Wo], and the painter launches take that scratch's frames
+    in place of the label map's: contours and tints are those of the grown map.  Everything else -- `labels` itself, the geometry
+    table, the centroids, trails, boxes and captions -- stays that of the map as made; with grow == 0 nothing is allocated or launched.
     -> `label_maps`' geometry table where `geometry` asks for it, else None."""
     from . import ops
     notes = style.annotates and int(m.shape[0]) > 0
@@ -258,10 +262,14 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
         back = style.backdrop_yuv_on(m.device, *out.meta()[2:]) if surface else style.backdrop_on(m.device)
     taps = style.taps_on(m.device) if style.blur is not None else None
     taps_c = style.taps_c_on(m.device) if taps is not None and surface else None
+    grown = None
+    if style.grow > 0 and n:
+        grown = ops.grow_labels(labels[l_off:l_off + nf], style.grows_on(m.device, cls), style.grow,
+                                torch.empty((nf,) + tuple(labels.shape[1:]), dtype=torch.uint8, device=m.device))
     pieces = source.pieces(int(f0), int(f0) + nf, stream=torch.cuda.current_stream(m.device))
     for t, first in pieces:
         k, d = len(t), first - int(f0)
-        lab = labels[l_off + d:l_off + d + k]
+        lab = labels[l_off + d:l_off + d + k] if grown is None else grown[d:d + k]
         if matte is not None and surface:
             ops.render_replace_yuv(lab, t, pal, act, matte[d:d + k], back, out, o_off + d, style.a256, style.contour, style.replace)
         elif matte is not None:

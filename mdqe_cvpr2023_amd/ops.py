@@ -1350,6 +1350,40 @@ def label_polygons(labels, n, min_area=0, cap_vertices=None, cap_rings=None):
     return xy, rings, totals
 
 
+def grow_labels(labels, grow, radius, out=None):
+    """The redaction margin: a copy of labels (uint8 [F, Ho, Wo], CUDA, contiguous: ops.final_label_map's output) in which the labels
+    that `grow` (uint8 [256] on the same device; entry 0 is ignored) marks have grown by up to `radius` pixels (an int in 0..32) over
+    the background and over the tracks that do not grow -- the rule of include/mdqe_hip.h, mdqe_grow_labels_u8: a pixel whose label
+    grows keeps it, any other takes the label of the nearest growing pixel of its frame within the Euclidean radius, of equally near
+    ones the smallest label.  `out`: a buffer of labels' shape that shares no byte with labels or grow (None: allocated), fully
+    overwritten.  The painters (ops.render_overlay and the others) take the result in place of the label map.  Integers only, identical
+    from run to run; one launch on the current stream, none for an empty map.  -> out."""
+    # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
+    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        raise RuntimeError("grow_labels: labels must be contiguous uint8 [F, Ho, Wo]")
+    F, Ho, Wo = (int(v) for v in labels.shape)
+    if F * Ho * Wo >= 2 ** 31 - 1:
+        raise RuntimeError("grow_labels: F*Ho*Wo must be < 2^31 - 1, got %s" % (tuple(labels.shape),))
+    if not torch.is_tensor(grow) or grow.dtype != torch.uint8 or tuple(grow.shape) != (256,) or not grow.is_contiguous():
+        raise RuntimeError("grow_labels: grow must be contiguous uint8 [256] (entry l: whether label l grows)")
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= 32:
+        raise RuntimeError("grow_labels: radius must be an int in 0..32, got %r" % (radius,))
+    if out is None:
+        out = torch.empty_like(labels)
+    if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (F, Ho, Wo) or not out.is_contiguous():
+        raise RuntimeError("grow_labels: out must be contiguous uint8 %s, the labels' shape" % ((F, Ho, Wo),))
+    for t, what in ((labels, "labels"), (grow, "grow"), (out, "out")):
+        if not t.is_cuda or t.device != labels.device:
+            raise RuntimeError("grow_labels: %s must be a CUDA tensor on the labels' device, got %s" % (what, t.device))
+    n = F * Ho * Wo
+    if n and (max(out.data_ptr(), labels.data_ptr()) < min(out.data_ptr(), labels.data_ptr()) + n
+              or (out.data_ptr() < grow.data_ptr() + 256 and grow.data_ptr() < out.data_ptr() + n)):
+        raise RuntimeError("grow_labels: out must not share memory with labels or grow (a pixel reads its neighbours' labels)")
+    with torch.cuda.device(labels.device):
+        check(lib.mdqe_grow_labels_u8(ptr(labels), F, Ho, Wo, ptr(grow), radius, ptr(out), cur_stream(labels.device)), "grow_labels")
+    return out
+
+
 def _trail_args(name, pts, n, palette, F, f_off, p_off, trail, width, table_dtypes):
     """The checks render_trails and render_trails_yuv share.  -> the point table's row stride."""
     # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)

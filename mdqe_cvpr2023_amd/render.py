@@ -1,7 +1,8 @@
 """How an overlay is painted (model.overlay_output, online_video(emit="overlay")): the palette and the style.  The painting itself is
 ops.render_overlay (csrc/render.hip) behind the label map; merge.overlay_frames puts the two together for a tracker window.  A style
 with a mosaic (redaction) is painted by ops.render_mosaic (csrc/render_mosaic.hip) from the style's per-label action table, one with a
-blur by ops.render_blur (csrc/render_blur.hip) from the same table and the tap tables of `blur_taps`.  A style
+blur by ops.render_blur (csrc/render_blur.hip) from the same table and the tap tables of `blur_taps`.  A style with a margin
+(`grow`) has ops.grow_labels (csrc/grow.hip) dilate the labels of its `grows` table first, and the painter takes that map.  A style
 with a box or a caption has ops.annotate (csrc/annotate.hip) draw them onto the painted picture, from the label map's geometry table,
 the font, the ink colours and the window's caption table made here.  `Crops` is the request for the other picture made from the same
 trio of frames, label map and geometry table: one fixed-size chip per track and frame (ops.track_crops, csrc/crops.hip).
@@ -281,7 +282,15 @@ class Style:
     frames' channel order, or a uint8 tensor [Ho, Wo, 3], one picture of the output's size for every frame, or, in a surface=True
     session, a preprocess.YuvFrames of one surface of the session's kind.  matte_gain: in (0, 64],
     the factor on the logit under the matte's sigmoid: above 1 a sharper edge, below 1 a softer one; the matte's 128 level, the hard
-    mask's edge, does not move."""
+    mask's edge, does not move.
+    grow: the safety margin of a redaction in output pixels, an int in 0..32 (0: none, and exactly the former launches are made).  Behind
+    the label map one ops.grow_labels launch (csrc/grow.hip) makes a grown copy of it and the painter takes that copy: with
+    mosaic="tracks" or blur="tracks" the tracks that are pixelated or blurred grow by up to `grow` pixels (a Euclidean disc; where two
+    meet, the nearer wins) over the background and over the tinted tracks, so hair, fingers and motion-blurred borders that the mask
+    under-covers are redacted too; with mosaic="background", blur="background" or the plain overlay every track grows, so the objects
+    keep a sharp margin, or the tint becomes wider (`grows`).  Contours and tints are those of the grown map.  Every other output --
+    the label maps, boxes, captions, trails, crops, polygons, mattes, masks -- stays that of the map as the model made it.  Not with
+    `replace`: there the matte owns the edge."""
     alpha: float = 0.5
     contour: int = 1
     palette: torch.Tensor = None
@@ -300,8 +309,11 @@ class Style:
     replace: str = None
     backdrop: object = (0, 255, 0)
     matte_gain: float = 1.0
+    grow: int = 0
 
     def __post_init__(self):
+        if isinstance(self.grow, bool) or not isinstance(self.grow, int) or not 0 <= self.grow <= 32:
+            raise ValueError("overlay style: grow must be an int in 0..32, got %r" % (self.grow,))
         if isinstance(self.trail, bool) or not isinstance(self.trail, int) or not 0 <= self.trail <= 64:
             raise ValueError("overlay style: trail must be an int in 0..64, got %r" % (self.trail,))
         if isinstance(self.trail_width, bool) or not isinstance(self.trail_width, int) or not 1 <= self.trail_width <= 5:
@@ -347,6 +359,9 @@ class Style:
         if (isinstance(self.matte_gain, bool) or not isinstance(self.matte_gain, (int, float))
                 or not 0.0 < float(self.matte_gain) <= 64.0):
             raise ValueError("overlay style: matte_gain must be a number in (0, 64] (1.0: the model's own sigmoid), got %r" % (self.matte_gain,))
+        if self.grow > 0 and self.replace is not None:
+            raise ValueError("overlay style: grow is the margin of a mosaic, a blur or the tint; with replace=%r the matte owns the edge "
+                             "-- lower matte_gain for a softer, wider edge, or use blur= or mosaic= with grow=%d" % (self.replace, self.grow))
         self.backdrop = _backdrop(self.backdrop, "overlay style")
         if self.classes is not None:
             try:
@@ -429,6 +444,23 @@ class Style:
                 hit = torch.isin(first, torch.tensor(self.classes, dtype=first.dtype))
                 act[1:n + 1] = torch.where(hit, hit_as, miss_as).to(torch.uint8)
         return act
+
+    def grows(self, cls_probs=None):
+        """The table of ops.grow_labels, uint8 [256] on the host, a pure function of `actions(cls_probs)`: entry l says whether label l
+        grows by the style's margin.  With mosaic="tracks" or blur="tracks": exactly the labels whose action is the redaction (2 or 3)
+        -- with `classes` only those tracks, and they grow over the tinted ones; with mosaic="background", blur="background" or the
+        plain overlay: every label >= 1.  Entry 0 is 0: the background never grows."""
+        act = self.actions(cls_probs)
+        what = self.blur if self.blur is not None else self.mosaic
+        g = ((act == 2) | (act == 3)) if what == "tracks" else torch.ones(256, dtype=torch.bool)
+        g[0] = False
+        return g.to(torch.uint8)
+
+    def grows_on(self, device, cls_probs=None):
+        """`grows` on `device`: cached per device where the table does not depend on the window (no `classes`), as `actions_on` is."""
+        if self.classes is not None:
+            return self.grows(cls_probs).to(device)
+        return self._cached_on("_grow_on", (str(device),), self.grows)
 
     def takes(self, cls_probs=None):
         """The matte's row table of ops.final_matte for a replace style, uint8 [256] on the host, from `actions(cls_probs)`: entry l says
