@@ -669,7 +669,7 @@ int mdqe_render_mosaic_yuv420sp(const void* y, long y_pitch, long y_stride, cons
  *              blur_c(Y, X) = (sum_{d = -R..R} taps[|d|] * h_c(Y', X) + 32768) >> 16      (the sum stays below 2^26)
  *            A constant picture is therefore unchanged.  The taps take in ALL pixels under the kernel whatever their labels: a sharp
  *            (kept or tinted) object next to a blurred background bleeds into it, and a blurred object takes in its surroundings --
- *            the behaviour of a plain Gaussian blur; the blur does not stop at region borders;
+ *            the behaviour of a plain Gaussian blur.  The blur that stops at region borders is mdqe_render_blur_within_u8 below;
  *   RGB      with l the pixel's label:  action 1: out_c = palette[l][c] if edge, else (s_c*(256 - a256) + palette[l][c]*a256 + 128) >> 8;
  *                                       action 3: out_c = blur_c(Y, X);
  *                                       else:     out_c = s_c;
@@ -696,6 +696,52 @@ int mdqe_render_blur_yuv420sp(const void* y, long y_pitch, long y_stride, const 
                               const unsigned short* taps, int radius, const unsigned short* taps_c, int radius_c,
                               void* out_y, long out_y_pitch, long out_y_stride,
                               void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream);
+
+/* The edge-stopping blur overlay (csrc/render_blur_within.hip): the two blur painters above with a blur that stays INSIDE the blurred
+ * region -- a normalised, membership-weighted Gaussian, the usual cure for the halo a sharp object smears into a blurred background.
+ * The argument lists are those of mdqe_render_blur_u8 and mdqe_render_blur_yuv420sp, argument by argument.  Everything that is not the
+ * blurred value is the plain entries' rule above: edge, source, the actions (0 keep, 1 tint, 3 blur, any other value as 0), the tints,
+ * the chroma block mean, P010's kept words, every check and refusal (in place included), F == 0, nothing needs to be aligned, and only
+ * tiles (16 x 64 pixels) that hold a pixel of action 3 are filtered.  The blurred value, integers only, ONE definition:
+ *   member   m(Y, X) = 1 where action[labels[f, Y, X]] == 3, else 0;
+ *   clamp    coordinates are clamped as in the plain rule, X' = min(max(X + d, 0), Wo - 1), Y' likewise: a border pixel is replicated
+ *            TOGETHER WITH its membership;
+ *   per channel c, with NO rounding between the passes:
+ *              Hn_c(Y, X) = sum_{d = -R..R} taps[|d|] * m(Y, X') * s_c(Y, X')        Hw(Y, X) = sum_{d = -R..R} taps[|d|] * m(Y, X')
+ *              N_c(Y, X)  = sum_{d = -R..R} taps[|d|] * Hn_c(Y', X)                   D(Y, X)  = sum_{d = -R..R} taps[|d|] * Hw(Y', X)
+ *              within_c(Y, X) = (N_c + D // 2) // D                                   (// is the floor division; everything is >= 0)
+ *            The value is defined only for pixels of action 3; there D >= taps[0]^2 > 0, because the pixel itself counts.  Elsewhere D
+ *            may be 0 and nothing is computed;
+ *   bounds   Hw <= 4096; Hn <= 4096 * 255 < 2^20 for 8-bit values and <= 4096 * 1023 < 2^22 for P010 values; D <= 2^24; for 8-bit values
+ *            N + D // 2 <= 2^24 * 255 + 2^23 = 4 286 578 688 < 2^32, so 32 bits hold it; N of 10-bit values needs more than 32 bits (the
+ *            kernel sums P010 in 64);
+ *   RGB      action 3: out_c = within_c(Y, X); every other action as mdqe_render_blur_u8;
+ *   YUV      (values: word >> 6 for P010.)  Luma follows the rule above on the luma plane with `taps`.  Chroma is filtered on its own
+ *            ceil(H/2) x ceil(W/2) grid of pairs, U and V separately, with taps_c and coordinates clamped to that plane.  A pair is a
+ *            member when ANY in-picture pixel of its 2 x 2 block has action 3: the pair of every blurred pixel is a member, so D > 0
+ *            wherever the value is used.  The blurred pixel then enters its pair's block mean with the pair's within value, as it does
+ *            with the pair's blurred C in the plain rule.
+ * What follows from it:
+ *   - a region whose members under the kernel all have the value v keeps v exactly (N = v * D), whatever lies outside it;
+ *   - the value at a pixel of action 3 does not depend on the source value of ANY pixel whose action is not 3 (a kept or tinted object
+ *     does not bleed into a blurred background, a blurred track takes in nothing of its surroundings);
+ *   - where every pixel is a member D = 2^24, and the value differs from the plain rule's blur_c by at most 1: the plain rule's row
+ *     rounding moves the exact mean by at most 1/32 before the final rounding;
+ *   - with action = {0, 1, 1, ..., 1} both entries are bit-identical to the plain painters, and with radius = 0, taps = {4096} a pixel of
+ *     action 3 keeps its source value.
+ * The division is exact.  One launch, no global scratch, no atomics: identical from run to run.  Never allocates, never synchronises.
+ * An RGB launch with a radius above 24 takes 68 KB of LDS, more than the 64 KB a kernel gets unasked; MDQE_ELAUNCH where the device does
+ * not grant it. */
+int mdqe_render_blur_within_u8(const void* frames, int is_u8, long frame_stride, int h0, int w0,
+                               const unsigned char* labels, int F, int Ho, int Wo,
+                               const unsigned char* palette, const unsigned char* action, int a256, int contour,
+                               const unsigned short* taps, int radius, unsigned char* out, int f_off, void* stream);
+int mdqe_render_blur_within_yuv420sp(const void* y, long y_pitch, long y_stride, const void* uv, long uv_pitch, long uv_stride,
+                                     int F, int H, int W, int fmt /*0 nv12, 1 p010*/, const unsigned char* labels,
+                                     const unsigned short* palette_yuv, const unsigned char* action, int a256, int contour,
+                                     const unsigned short* taps, int radius, const unsigned short* taps_c, int radius_c,
+                                     void* out_y, long out_y_pitch, long out_y_stride,
+                                     void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream);
 
 /* The compositing painter (csrc/render_replace.hip): the overlay's picture mixed with a backdrop by a soft matte, so that tracks or the
  * background are REPLACED with an anti-aliased edge.  Every argument the entry shares with mdqe_render_mosaic_u8 means what it means

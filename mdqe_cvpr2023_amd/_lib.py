@@ -61,6 +61,8 @@ SIGNATURES = {
     "mdqe_render_mosaic_yuv420sp": [p, l, l, p, l, l, i, i, i, i, p, p, p, i, i, i, p, l, l, p, l, l, i, p],
     "mdqe_render_blur_u8": [p, i, l, i, i, p, i, i, i, p, p, i, i, p, i, p, i, p],
     "mdqe_render_blur_yuv420sp": [p, l, l, p, l, l, i, i, i, i, p, p, p, i, i, p, i, p, i, p, l, l, p, l, l, i, p],
+    "mdqe_render_blur_within_u8": [p, i, l, i, i, p, i, i, i, p, p, i, i, p, i, p, i, p],
+    "mdqe_render_blur_within_yuv420sp": [p, l, l, p, l, l, i, i, i, i, p, p, p, i, i, p, i, p, i, p, l, l, p, l, l, i, p],
     "mdqe_annotate_u8": [p, i, i, i, i, p, i, p, p, p, i, p, i, i, i, p],
     "mdqe_annotate_yuv420sp": [p, l, l, p, l, l, i, i, i, i, i, p, i, p, p, p, i, p, i, i, i, p],
     "mdqe_track_crops_u8": [p, i, l, i, i, p, i, i, i, p, i, i, i, i, i, i, i, i, i, p, l, i, p, l, p],

@@ -233,7 +233,8 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
     ops.render_overlay_yuv launch per piece, with the palette in the surfaces' samples.  A style with a mosaic (style.mosaic): the
     same launches of ops.render_mosaic / ops.render_mosaic_yuv with the style's action table; `cls`, the window's class rows [n, K]
     on the host, is what a style with `classes` builds that table from.  A style with a blur (style.blur): the same launches of
-    ops.render_blur / ops.render_blur_yuv with that table and the style's tap tables (style.taps_on, style.taps_c_on).  A style that
+    ops.render_blur / ops.render_blur_yuv with that table, the style's tap tables (style.taps_on, style.taps_c_on) and its
+    blur_edge ("stop": the blur that stays inside what it blurs; with a margin, inside the grown map's regions).  A style that
     replaces (style.replace): behind the label map one ops.final_matte launch sweeps the same logits into a device scratch [F, Ho, Wo]
     -- the matte of the rows the style's `takes` table selects, with the style's matte_gain -- and the painter launches are
     ops.render_replace / ops.render_replace_yuv with that matte and the style's backdrop (a backdrop picture must have the output's size).  A style that annotates (style.annotates: track boxes,
@@ -262,6 +263,7 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
         back = style.backdrop_yuv_on(m.device, *out.meta()[2:]) if surface else style.backdrop_on(m.device)
     taps = style.taps_on(m.device) if style.blur is not None else None
     taps_c = style.taps_c_on(m.device) if taps is not None and surface else None
+    edge = {"edge": style.blur_edge} if style.blur_edge != "bleed" else {}     # ("bleed": the blur's calls exactly as they were)
     grown = None
     if style.grow > 0 and n:
         grown = ops.grow_labels(labels[l_off:l_off + nf], style.grows_on(m.device, cls), style.grow,
@@ -275,9 +277,9 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
         elif matte is not None:
             ops.render_replace(lab, t, pal, act, matte[d:d + k], back, out, o_off + d, style.a256, style.contour, style.replace)
         elif taps is not None and surface:
-            ops.render_blur_yuv(lab, t, pal, act, taps, taps_c, out, o_off + d, style.a256, style.contour)
+            ops.render_blur_yuv(lab, t, pal, act, taps, taps_c, out, o_off + d, style.a256, style.contour, **edge)
         elif taps is not None:
-            ops.render_blur(lab, t, pal, act, taps, out, o_off + d, style.a256, style.contour)
+            ops.render_blur(lab, t, pal, act, taps, out, o_off + d, style.a256, style.contour, **edge)
         elif act is not None and surface:
             ops.render_mosaic_yuv(lab, t, pal, act, out, o_off + d, style.a256, style.contour, style.cell)
         elif act is not None:

@@ -1022,38 +1022,53 @@ def _host_planes_apart(name, what, yuv, out, f_off, F):
                 raise RuntimeError("%s: out must not share memory with yuv (the %s is not painted in place)" % (name, what))
 
 
-def render_blur(labels, frames, palette, action, taps, out, f_off=0, a256=128, contour=1):
+def _blur_edge(name, edge):
+    """The `edge` of render_blur / render_blur_yuv: "bleed", the plain Gaussian, or "stop", the blur that stays inside the blurred region."""
+    if edge not in ("bleed", "stop"):
+        raise RuntimeError("%s: edge must be 'bleed' or 'stop', got %r" % (name, edge))
+    return edge == "stop"
+
+
+def render_blur(labels, frames, palette, action, taps, out, f_off=0, a256=128, contour=1, edge="bleed"):
     """`render_overlay` with a per-label action (uint8 [256], action[l]: 0 keep the source, 1 tint as render_overlay does, 3 blur, any
     other value as 0; action[0] is the background's): a blur pixel becomes the separable Gaussian of the OUTPUT grid's source values
     with the integer taps `taps` (uint16 [radius + 1], radius 0..32, taps[0] + 2 * sum(taps[1:]) == 4096: render.blur_taps), the
     picture's border replicated, over all pixels under the kernel whatever their labels.  Every other argument is render_overlay's;
     with action = [0, 1, 1, ...] the picture is render_overlay's bit for bit: the integer rule of include/mdqe_hip.h,
-    mdqe_render_blur_u8.  -> out."""
+    mdqe_render_blur_u8.  edge="stop": the blur stays inside the blurred region -- the taps weigh only pixels of action 3 and the
+    sums are normalised by the weight they met (one exact division per sample), so nothing that is kept or tinted bleeds into a
+    blurred pixel: mdqe_render_blur_within_u8 (csrc/render_blur_within.hip), same arguments, same checks.  -> out."""
+    stop = _blur_edge("render_blur", edge)
     F, Ho, Wo, h0, w0, stride = _rgb_paint_args("render_blur", labels, frames, palette, out, f_off, a256, contour, blur=(action, taps))
-    check(lib.mdqe_render_blur_u8(ptr(frames) if frames is not None else None, int(frames is not None and frames.dtype == torch.uint8),
-                                  stride, h0, w0, ptr(labels), F, Ho, Wo, ptr(palette), ptr(action), a256, contour, ptr(taps),
-                                  int(taps.numel()) - 1, ptr(out), f_off, cur_stream()), "render_blur")
+    entry = lib.mdqe_render_blur_within_u8 if stop else lib.mdqe_render_blur_u8
+    check(entry(ptr(frames) if frames is not None else None, int(frames is not None and frames.dtype == torch.uint8),
+                stride, h0, w0, ptr(labels), F, Ho, Wo, ptr(palette), ptr(action), a256, contour, ptr(taps),
+                int(taps.numel()) - 1, ptr(out), f_off, cur_stream()), "render_blur")
     return out
 
 
-def render_blur_yuv(labels, yuv, palette_yuv, action, taps, taps_c, out=None, f_off=0, a256=128, contour=1):
+def render_blur_yuv(labels, yuv, palette_yuv, action, taps, taps_c, out=None, f_off=0, a256=128, contour=1, edge="bleed"):
     """`render_overlay_yuv` with a per-label action (as `render_blur`): a blur pixel's luma is the Gaussian of the luma plane with
     `taps`, and it enters its chroma pair's block mean with the pair's U / V blurred on the chroma plane's own ceil(H/2) x ceil(W/2)
     grid with `taps_c` (uint16 [radius_c + 1], radius_c 0..16); a pixel that is kept keeps the decoder's bits (P010: all 16 of a word;
     a chroma pair when its whole block is kept): the integer rule of include/mdqe_hip.h, mdqe_render_blur_yuv420sp.  Not in place:
     `out` must not share memory with `yuv` (the taps read samples other threads write).  On a HIP device one launch on the current
-    stream; on host planes the same rule in torch integers.  -> out."""
+    stream; on host planes the same rule in torch integers.  edge="stop": the blur stays inside the blurred region, as
+    render_blur's -- luma among the pixels of action 3, U and V among the pairs whose block holds such a pixel:
+    mdqe_render_blur_within_yuv420sp, on the device and on host planes alike.  -> out."""
+    stop = _blur_edge("render_blur_yuv", edge)
     F, H, W, out = _yuv_paint_args("render_blur_yuv", labels, yuv, palette_yuv, out, f_off, a256, contour, blur=(action, taps, taps_c))
     if yuv.is_cuda:
         src, dst = _surface_call_args(labels, yuv, palette_yuv, out, F, H, W)
         with torch.cuda.device(yuv.device):
-            check(lib.mdqe_render_blur_yuv420sp(*src, ptr(action), a256, contour, ptr(taps), int(taps.numel()) - 1, ptr(taps_c),
-                                                int(taps_c.numel()) - 1, *dst, f_off, cur_stream(yuv.device)), "render_blur_yuv")
+            entry = lib.mdqe_render_blur_within_yuv420sp if stop else lib.mdqe_render_blur_yuv420sp
+            check(entry(*src, ptr(action), a256, contour, ptr(taps), int(taps.numel()) - 1, ptr(taps_c),
+                        int(taps_c.numel()) - 1, *dst, f_off, cur_stream(yuv.device)), "render_blur_yuv")
         return out
     if F == 0:
         return out
     _host_planes_apart("render_blur_yuv", "blur", yuv, out, f_off, F)
-    return _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action, taps=(taps, taps_c))
+    return _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action, taps=(taps, taps_c), within=stop)
 
 
 def _blur_plane(v, taps):
@@ -1070,6 +1085,25 @@ def _blur_plane(v, taps):
             acc += w[abs(d)] * t.index_select(dim, (idx + d).clamp(0, n - 1))
         return (acc + add) >> shift
     return one(one(v, 2, 128, 8), 1, 32768, 16)
+
+
+def _blur_plane_within(v, member, taps):
+    """v int64 [F, h, w], member bool [F, h, w] -> the edge-stopping blur of include/mdqe_hip.h (mdqe_render_blur_within_u8): the taps
+    weigh member * v and member, rows then columns with no rounding between, the border replicated with its membership, then
+    (N + D // 2) // D where `member`, 0 elsewhere (there the value is not defined and D may be 0).  N stays below 2^34."""
+    w = (taps.view(torch.int16).to(torch.int64) & 0xFFFF).tolist()
+    R = len(w) - 1
+    m = member.to(torch.int64)
+
+    def one(t, dim):
+        n = t.shape[dim]
+        idx = torch.arange(n)
+        acc = torch.zeros_like(t)
+        for d in range(-R, R + 1):
+            acc += w[abs(d)] * t.index_select(dim, (idx + d).clamp(0, n - 1))
+        return acc
+    N, D = one(one(m * v, 2), 1), one(one(m, 2), 1)
+    return torch.where(member, (N + D // 2) // D.clamp(min=1), torch.zeros_like(N))
 
 
 def _annotate_args(name, geom, n, palette, ink, captions, font, f_off, box, scale, min_area, table_dtypes):
@@ -1448,10 +1482,12 @@ def render_trails_yuv(yuv, pts, n, palette_yuv, F, f_off=0, p_off=0, trail=16, w
     return yuv
 
 
-def _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action=None, cell=None, taps=None):
+def _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action=None, cell=None, taps=None, within=False):
     """The surface painters' rule of include/mdqe_hip.h on host planes, in torch integers.  action None: the plain painter, which is the
     table [0, 1, 1, ...] (no label has action 2, so no cell mean is taken) and may paint in place.  taps = (taps, taps_c): the blur
-    painter, whose special action is 3 and whose special value is the blurred plane's; every action but 1 and 3 then keeps.  -> out."""
+    painter, whose special action is 3 and whose special value is the blurred plane's; every action but 1 and 3 then keeps.  within:
+    the blur painter's edge-stopping rule (mdqe_render_blur_within_yuv420sp): luma is blurred among the pixels of action 3, U and V
+    among the pairs whose block holds one.  -> out."""
     F, H, W = len(yuv), yuv.height, yuv.width
     p010 = yuv.fmt == "p010"
     ch, cw = (H + 1) // 2, (W + 1) // 2
@@ -1468,6 +1504,8 @@ def _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action=
 
     def means(v, sub):                              # cell means of a plane sub-sampled by `sub`; never looked at without an action 2
         if taps is not None:                        # (the blur: the plane's own taps; what px calls action 2 is action 3 here)
+            if within:
+                return _blur_plane_within(v, act == 2 if sub == 1 else blocks((act == 2).to(torch.int64)) > 0, taps[sub - 1])
             return _blur_plane(v, taps[sub - 1])
         return v if action is None else _cell_means(v, cell // sub)
 

@@ -264,8 +264,12 @@ class Style:
     every track, or with `classes` the tracks of those classes, the others tinted; the background stays as decoded -- or "background"
     -- everything but the tracks, which are tinted as alpha / contour say.  Not together with a mosaic.  blur_radius: the reach of the
     Gaussian in output pixels, an int in 1..32 (sigma = blur_radius / 2, `blur_taps`; a surface's chroma planes, half as wide, are
-    blurred with radius (blur_radius + 1) // 2).  The blur takes in ALL pixels under the kernel whatever their labels: a sharp object
-    next to a blurred background bleeds into it, as with any plain Gaussian blur.
+    blurred with radius (blur_radius + 1) // 2).  blur_edge: what the blur does at the border of what it blurs.  "bleed": the taps take
+    in ALL pixels under the kernel whatever their labels, so a sharp object next to a blurred background smears a halo of blur_radius
+    pixels into it and a blurred track takes in its surroundings, as with any plain Gaussian blur.  "stop": the taps weigh only the
+    pixels that are blurred themselves and the sum is normalised by the weight it met (ops.render_blur(edge="stop"),
+    csrc/render_blur_within.hip), so nothing kept or tinted reaches a blurred pixel; a thin blurred track is then blurred with
+    itself only -- a weaker redaction, best used with `grow`.  Only with a blur.
     Annotations (ops.annotate, csrc/annotate.hip: a pass behind whichever painter the fields above choose): box: the thickness in
     pixels, 0..4, of a frame around each track's visible region per frame (0: none); caption: None or which fields are written on a
     plate at the box's top left corner -- "id", "class", "id+class", "id+class+score", "class+score" (`captions`); class_names: None or
@@ -310,6 +314,7 @@ class Style:
     backdrop: object = (0, 255, 0)
     matte_gain: float = 1.0
     grow: int = 0
+    blur_edge: str = "bleed"
 
     def __post_init__(self):
         if isinstance(self.grow, bool) or not isinstance(self.grow, int) or not 0 <= self.grow <= 32:
@@ -349,6 +354,11 @@ class Style:
             raise ValueError("overlay style: blur must be None, 'tracks' or 'background', got %r" % (self.blur,))
         if isinstance(self.blur_radius, bool) or not isinstance(self.blur_radius, int) or not 1 <= self.blur_radius <= 32:
             raise ValueError("overlay style: blur_radius must be an int in 1..32, got %r" % (self.blur_radius,))
+        if self.blur_edge not in ("bleed", "stop"):
+            raise ValueError("overlay style: blur_edge must be 'bleed' or 'stop', got %r" % (self.blur_edge,))
+        if self.blur_edge == "stop" and self.blur is None:
+            raise ValueError("overlay style: blur_edge='stop' is the edge of a blur -- add blur='tracks' or blur='background', or leave "
+                             "blur_edge at 'bleed'; got blur_edge='stop' with blur=None")
         if self.mosaic is not None and self.blur is not None:
             raise ValueError("overlay style: a style has a mosaic or a blur, not both; got mosaic=%r with blur=%r" % (self.mosaic, self.blur))
         if self.replace not in (None, "tracks", "background"):
