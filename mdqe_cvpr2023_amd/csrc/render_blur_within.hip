@@ -17,7 +17,8 @@
 //             computed): 32-bit values by the compiler's exact unsigned division, P010 by a float quotient with an integer fix-up
 //             (`rdiv`).  RGB: the result plane (one packed dword per pixel) takes the place of the dead source plane -- the centres'
 //             membership bits are read into a register and a barrier passes before the first result is written;
-//   5 paint   the plain kernel's painters: RGB in groups of 4 pixels laid out from the OUTPUT address, surfaces one 2 x 2 block per thread.
+//   5 paint   the plain kernel's painters, the same functions: RGB in groups of 4 pixels laid out from the OUTPUT address (paint_rgb_tile
+//             of render_tile_paint.h), surfaces one 2 x 2 block per thread (paint_blur_blocks of render_blur_tile.h).
 // Which direction is first is the kernel's to choose: the plain rule rounds after its row pass, which fixes its order; this rule rounds
 // nowhere between the passes, so N and D are the same double sum either way, bit for bit.  Rows first (render_blur.hip's order) sums
 // at (16 + 2R) x 64 positions and keeps as many in LDS; columns first at 16 x (64 + 2R): 2048 positions against 5120 at R = 32, and
@@ -37,7 +38,9 @@
 // Only RGB at R = 32 is above 64 KB: that launch asks for it with mdqe_allow_lds, and two blocks still share a CU's 160 KB.  A narrower
 // tile at the large radii or Hn packed into 24 bits would save LDS that no longer limits the blocks per CU; neither was built.
 // Both passes run over the whole tile of a flagged tile, whatever the labels: no data-dependent order, no atomics, no global scratch,
-// identical from run to run.  The entries' checks are the plain entries' (render_rule.h).
+// identical from run to run.  The argument structs, the entries' checks and the kernels' first phase are the plain blur's too
+// (render_blur_tile.h: BlurArgs, BlurYuvArgs, blur_rgb_call, blur_yuv_call, tile_begin); this file holds the passes, the LDS plans, the
+// load phases and the launches.
 #include "render_blur_tile.h"
 
 namespace {
@@ -80,51 +83,61 @@ __device__ __forceinline__ uint32_t rdiv(uint64_t n, uint32_t D) {
   return q;
 }
 
-// ROWS FIRST (R <= 8).  Phase 3, RGB: for `rows` rows of TW columns, hn[k][i] = sum_d taps[|d|] * (m * c_k)(r, c + R + d) and hw[i] = sum_d taps[|d|] * m; s
-// rows are `pitch` dwords apart.  A lane of a pair's sum is at most 510, a sum at most 4096 * 255.
+// The tap sums of phase 3, each said once for a centre and its R neighbours either way, S words apart: S is 1 along a row, the row
+// length of the plane along a column -- a compile-time constant in every pass, and the loops are fully unrolled per padded radius.  The
+// results go to hn[.. + i] and hw[i], indexed here as the passes index everything else.  (Phase 4's two passes carry their own tap
+// loops: DESIGN.md §4, "Where the painters' rule lives", has the registers that decide it.)
+// RGB: hn[k * hplane + i] = sum_d taps[|d|] * (m * c_k)(q + d * S) and hw[i] = sum_d taps[|d|] * m over packed dwords.  The two dwords
+// of a distance go apart into two 16-bit lanes each: a lane of a pair's sum is at most 510, a sum at most 4096 * 255.
+template <int R, int S>
+__device__ __forceinline__ void first_sums_rgb(const uint32_t* q, const uint32_t* taps, uint32_t* hn, int hplane, unsigned short* hw, int i) {
+  const uint32_t x = q[0], w0 = taps[0];
+  uint32_t a0 = w0 * (x & 0xFFu), a1 = w0 * ((x >> 8) & 0xFFu), a2 = w0 * ((x >> 16) & 0xFFu), aw = w0 * (x >> 24);
+#pragma unroll
+  for (int d = 1; d <= R; ++d) {
+    const uint32_t w = taps[d], xa = q[-d * S], xb = q[d * S];
+    const uint32_t e = (xa & 0x00FF00FFu) + (xb & 0x00FF00FFu);                       // c0 | c2 << 16
+    const uint32_t o = ((xa >> 8) & 0x00FF00FFu) + ((xb >> 8) & 0x00FF00FFu);         // c1 | m << 16
+    a0 += w * (e & 0xFFFFu); a2 += w * (e >> 16);
+    a1 += w * (o & 0xFFFFu); aw += w * (o >> 16);
+  }
+  hn[i] = a0; hn[hplane + i] = a1; hn[2 * hplane + i] = a2;
+  hw[i] = (unsigned short)aw;
+}
+
+// Surfaces: the same for NP planes (`splane` words apart) of 16-bit words m * value | m << 15 (every plane carries the bit;
+// plane 0's is summed).  A sum is at most 4096 * 1023.
+template <int NP, int R, int S>
+__device__ __forceinline__ void first_sums_yuv(const unsigned short* q, int splane, const uint32_t* taps, uint32_t* hn, int hplane, unsigned short* hw,
+                                               int i) {
+  uint32_t acc[NP], aw = taps[0] * ((uint32_t)q[0] >> 15);
+#pragma unroll
+  for (int p = 0; p < NP; ++p) acc[p] = taps[0] * ((uint32_t)q[p * splane] & 0x7FFFu);
+#pragma unroll
+  for (int d = 1; d <= R; ++d) {
+    const uint32_t w = taps[d];
+    aw += w * (((uint32_t)q[-d * S] >> 15) + ((uint32_t)q[d * S] >> 15));
+#pragma unroll
+    for (int p = 0; p < NP; ++p) acc[p] += w * (((uint32_t)q[p * splane - d * S] & 0x7FFFu) + ((uint32_t)q[p * splane + d * S] & 0x7FFFu));
+  }
+#pragma unroll
+  for (int p = 0; p < NP; ++p) hn[p * hplane + i] = acc[p];
+  hw[i] = (unsigned short)aw;
+}
+
+// ROWS FIRST (R <= 8).  Phase 3, RGB: the horizontal sums at `rows` rows of TW columns, i = r * TW + c; s rows are `pitch` dwords apart.
 template <int R>
 __device__ __forceinline__ void row_pass_rgb(const uint32_t* s, int pitch, uint32_t* hn, int hplane, unsigned short* hw, const uint32_t* taps,
                                              int rows, int tid) {
-  for (int i = tid; i < rows * TW; i += 256) {
-    const int r = i / TW, c = i % TW;
-    const uint32_t* q = s + r * pitch + c + R;
-    const uint32_t x = q[0], w0 = taps[0];
-    uint32_t a0 = w0 * (x & 0xFFu), a1 = w0 * ((x >> 8) & 0xFFu), a2 = w0 * ((x >> 16) & 0xFFu), aw = w0 * (x >> 24);
-#pragma unroll
-    for (int d = 1; d <= R; ++d) {
-      const uint32_t w = taps[d], xa = q[-d], xb = q[d];
-      const uint32_t e = (xa & 0x00FF00FFu) + (xb & 0x00FF00FFu);                       // c0 | c2 << 16
-      const uint32_t o = ((xa >> 8) & 0x00FF00FFu) + ((xb >> 8) & 0x00FF00FFu);         // c1 | m << 16
-      a0 += w * (e & 0xFFFFu); a2 += w * (e >> 16);
-      a1 += w * (o & 0xFFFFu); aw += w * (o >> 16);
-    }
-    hn[i] = a0; hn[hplane + i] = a1; hn[2 * hplane + i] = a2;
-    hw[i] = (unsigned short)aw;
-  }
+  for (int i = tid; i < rows * TW; i += 256) first_sums_rgb<R, 1>(s + (i / TW) * pitch + i % TW + R, taps, hn, hplane, hw, i);
 }
 
-// Phase 3, surfaces, rows first: the same for NP planes of 16-bit words m * value | m << 15 (every plane carries the bit; plane 0's is summed).
-// A sum is at most 4096 * 1023.
+// Phase 3, surfaces, rows first: the same at `rows` rows of COLS columns of NP planes.
 template <int COLS, int NP, int R>
 __device__ __forceinline__ void row_pass_yuv(const unsigned short* s, int pitch, int splane, uint32_t* hn, int hplane, unsigned short* hw,
                                              const uint32_t* taps, int rows, int tid) {
-  for (int i = tid; i < rows * COLS; i += 256) {
-    const int r = i / COLS, c = i % COLS;
-    const unsigned short* q = s + r * pitch + c + R;
-    uint32_t acc[NP], aw = taps[0] * ((uint32_t)q[0] >> 15);
-#pragma unroll
-    for (int p = 0; p < NP; ++p) acc[p] = taps[0] * ((uint32_t)q[p * splane] & 0x7FFFu);
-#pragma unroll
-    for (int d = 1; d <= R; ++d) {
-      const uint32_t w = taps[d];
-      aw += w * (((uint32_t)q[-d] >> 15) + ((uint32_t)q[d] >> 15));
-#pragma unroll
-      for (int p = 0; p < NP; ++p) acc[p] += w * (((uint32_t)q[p * splane - d] & 0x7FFFu) + ((uint32_t)q[p * splane + d] & 0x7FFFu));
-    }
-#pragma unroll
-    for (int p = 0; p < NP; ++p) hn[p * hplane + i] = acc[p];
-    hw[i] = (unsigned short)aw;
-  }
+  for (int i = tid; i < rows * COLS; i += 256)
+    first_sums_yuv<NP, R, 1>(s + (i / COLS) * pitch + i % COLS + R, splane, taps, hn, hplane, hw, i);
 }
 
 // Phase 4, rows first: fin(i, N[NP], D) for i = r * COLS + c over `rows` rows, N_p = sum_d taps[|d|] * hn[p][r + R + d][c] in the type ACC and
@@ -151,50 +164,19 @@ __device__ __forceinline__ void column_pass_within(const uint32_t* hn, int hplan
   }
 }
 
-// COLUMNS FIRST (R >= 16).  Phase 3, RGB: the VERTICAL sums of the TH tile rows over all SW = TW + 2R halo columns: hn[k][i] = sum_d taps[|d|] * (m * c_k)(r + R + d, c)
-// and hw[i] = sum_d taps[|d|] * m for i = r * SW + c.  A lane of a pair's sum is at most 510, a sum at most 4096 * 255.
+// COLUMNS FIRST (R >= 16).  Phase 3, RGB: the VERTICAL sums of the TH tile rows over all SW = TW + 2R halo columns, i = r * SW + c.
 template <int R>
 __device__ __forceinline__ void column_pass_rgb(const uint32_t* s, uint32_t* hn, unsigned short* hw, const uint32_t* taps, int tid) {
-  constexpr int SW = TW + 2 * R, hplane = TH * SW;
-  for (int i = tid; i < TH * SW; i += 256) {
-    const uint32_t* q = s + i + R * SW;
-    const uint32_t x = q[0], w0 = taps[0];
-    uint32_t a0 = w0 * (x & 0xFFu), a1 = w0 * ((x >> 8) & 0xFFu), a2 = w0 * ((x >> 16) & 0xFFu), aw = w0 * (x >> 24);
-#pragma unroll
-    for (int d = 1; d <= R; ++d) {
-      const uint32_t w = taps[d], xa = q[-d * SW], xb = q[d * SW];
-      const uint32_t e = (xa & 0x00FF00FFu) + (xb & 0x00FF00FFu);                       // c0 | c2 << 16
-      const uint32_t o = ((xa >> 8) & 0x00FF00FFu) + ((xb >> 8) & 0x00FF00FFu);         // c1 | m << 16
-      a0 += w * (e & 0xFFFFu); a2 += w * (e >> 16);
-      a1 += w * (o & 0xFFFFu); aw += w * (o >> 16);
-    }
-    hn[i] = a0; hn[hplane + i] = a1; hn[2 * hplane + i] = a2;
-    hw[i] = (unsigned short)aw;
-  }
+  constexpr int SW = TW + 2 * R;
+  for (int i = tid; i < TH * SW; i += 256) first_sums_rgb<R, SW>(s + i + R * SW, taps, hn, TH * SW, hw, i);
 }
 
-// Phase 3, surfaces, columns first: the same for NP planes (`splane` words apart) of ROWS tile rows and SW = COLS + 2R columns of 16-bit words
-// m * value | m << 15 (every plane carries the bit; plane 0's is summed).  A sum is at most 4096 * 1023.
+// Phase 3, surfaces, columns first: the same for NP planes of ROWS tile rows and SW = COLS + 2R columns.
 template <int ROWS, int COLS, int NP, int R>
 __device__ __forceinline__ void column_pass_yuv(const unsigned short* s, int splane, uint32_t* hn, unsigned short* hw, const uint32_t* taps,
                                                 int tid) {
-  constexpr int SW = COLS + 2 * R, hplane = ROWS * SW;
-  for (int i = tid; i < ROWS * SW; i += 256) {
-    const unsigned short* q = s + i + R * SW;
-    uint32_t acc[NP], aw = taps[0] * ((uint32_t)q[0] >> 15);
-#pragma unroll
-    for (int p = 0; p < NP; ++p) acc[p] = taps[0] * ((uint32_t)q[p * splane] & 0x7FFFu);
-#pragma unroll
-    for (int d = 1; d <= R; ++d) {
-      const uint32_t w = taps[d];
-      aw += w * (((uint32_t)q[-d * SW] >> 15) + ((uint32_t)q[d * SW] >> 15));
-#pragma unroll
-      for (int p = 0; p < NP; ++p) acc[p] += w * (((uint32_t)q[p * splane - d * SW] & 0x7FFFu) + ((uint32_t)q[p * splane + d * SW] & 0x7FFFu));
-    }
-#pragma unroll
-    for (int p = 0; p < NP; ++p) hn[p * hplane + i] = acc[p];
-    hw[i] = (unsigned short)aw;
-  }
+  constexpr int SW = COLS + 2 * R;
+  for (int i = tid; i < ROWS * SW; i += 256) first_sums_yuv<NP, R, SW>(s + i + R * SW, splane, taps, hn, ROWS * SW, hw, i);
 }
 
 // Phase 4, columns first: fin(i, N[NP], D) for i = r * COLS + c over ROWS rows: the HORIZONTAL sums over the planes of phase 3 (ROWS rows of COLS +
@@ -223,25 +205,8 @@ __device__ __forceinline__ void row_pass_within(const uint32_t* hn, const unsign
 }
 
 // ---- RGB ----------------------------------------------------------------------------------------------------------------------------
-struct WithinArgs {
-  TileArgs t;
-  RgbSource src;
-  const unsigned char* palette;  // [256, 3]
-  unsigned char* out;            // at frame f_off already: [F, Ho, Wo, 3]
-  unsigned head;                 // out address mod 4: groups of 4 pixels start at flat pixels = head (mod 4)
-  int ident;
-  int items;                     // paint items (groups of 4 pixels) per tile row
-  uint32_t m_items;
-  int src_bytes;                 // the source plane's share of the dynamic LDS (>= 4 * TH * TW: the result plane takes its place)
-};
-
-template <int KIND>
-__device__ __forceinline__ uint32_t source_of(const WithinArgs& a, int f, int Y, int X) {
-  return source_px<KIND>(a.src, a.ident, (long)f * a.src.frame_stride, Y, X, a.t.H, a.t.W);
-}
-
 template <int KIND, int CR, bool CF>              // CF: the kernel of the padded radii 16, 24, 32 (columns first); else of 0, 4, 8
-__global__ __launch_bounds__(256) void render_blur_within_kernel(const WithinArgs a) {
+__global__ __launch_bounds__(256) void render_blur_within_kernel(const BlurArgs a) {
   extern __shared__ __align__(16) unsigned char dyn[];
   __shared__ uint32_t pal[256];
   __shared__ unsigned char act[256];
@@ -249,14 +214,7 @@ __global__ __launch_bounds__(256) void render_blur_within_kernel(const WithinArg
   __shared__ int flag;
   const TileArgs& t = a.t;
   const int tid = (int)threadIdx.x;
-  pal[tid] = pack_rgb(a.palette + 3 * tid);
-  act[tid] = t.action[tid];
-  if (tid <= MAX_R) taps[tid] = tid < t.n_taps ? (uint32_t)t.taps[tid] : 0u;
-  if (tid == 0) flag = 0;
-  __syncthreads();
-  const TilePos p = tile_pos(t);
-  flag_tile(t, p, act, &flag, tid);
-  __syncthreads();
+  const TilePos p = tile_begin(t, pack_rgb(a.palette + 3 * tid), pal, act, taps, &flag, tid);
   uint32_t* res = (uint32_t*)dyn;                                     // [TH][TW]: the blurred pixel, c0 | c1 << 8 | c2 << 16
   if (flag != 0) {                                                    // (uniform over the block)
     const int R = t.radius, SH = TH + 2 * R, SW = TW + 2 * R;
@@ -269,7 +227,7 @@ __global__ __launch_bounds__(256) void render_blur_within_kernel(const WithinArg
       if (c >= SW) continue;
       const int Y = clampi(p.Y0 - R + r, t.H - 1), X = clampi(p.X0 - R + c, t.W - 1);
       const bool m = act[t.labels[((long)p.f * t.H + Y) * t.W + X]] == 3;
-      s[r * SW + c] = m ? source_of<KIND>(a, p.f, Y, X) | 1u << 24 : 0u;
+      s[r * SW + c] = m ? source_of<KIND>(a.src, a.ident, p.f, Y, X, t.H, t.W) | 1u << 24 : 0u;
     }
     __syncthreads();
     with_radius_of<CF>(R, [&](auto RR) {
@@ -294,58 +252,12 @@ __global__ __launch_bounds__(256) void render_blur_within_kernel(const WithinArg
     });
     __syncthreads();
   }
-  // paint: item j of tile row r is the j-th group of 4 flat pixels that meets the row's segment (render_blur.hip's painter)
-  for (int it = tid; it < p.th * a.items; it += 256) {
-    const int r = mdiv(it, a.m_items), j = it - r * a.items;
-    const int Y = p.Y0 + r;
-    const long row = ((long)p.f * t.H + Y) * t.W;                    // flat pixel of (f, Y, 0), < 2^31
-    const long seg = row + p.X0;                                      // the segment: flat pixels [seg, seg + tw)
-    const long ps = 4 * ((seg + 4 - a.head) / 4 + j) + a.head - 4;    // the group's first flat pixel (may lie before seg)
-    const long lo = ps > seg ? ps : seg, hi = ps + 4 < seg + p.tw ? ps + 4 : seg + p.tw;
-    if (lo >= hi) continue;
-    const bool whole = hi - lo == 4;
-    uint32_t l4 = 0u, c0 = 0u, c1 = 0u, c2 = 0u;
-    const bool wide_src = KIND == 1 && whole && a.ident;
-    if (whole) l4 = ld4(t.labels + ps);
-    if (wide_src) {
-      const unsigned char* q = (const unsigned char*)a.src.frames + (long)p.f * a.src.frame_stride + (long)Y * a.src.w0 + (int)(ps - row);
-      c0 = ld4(q); c1 = ld4(q + a.src.plane); c2 = ld4(q + 2 * a.src.plane);
-    }
-    uint32_t px[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const long q = ps + k;
-      if (q < lo || q >= hi) continue;
-      const int X = (int)(q - row);
-      const uint32_t l = whole ? (l4 >> 8 * k) & 0xFFu : (uint32_t)t.labels[q];
-      const uint32_t ac = act[l];
-      if (ac == 3u) {
-        px[k] = res[r * TW + (X - p.X0)] & 0x00FFFFFFu;
-        continue;
-      }
-      const uint32_t s = wide_src ? ((c0 >> 8 * k) & 0xFFu) | ((c1 >> 8 * k) & 0xFFu) << 8 | ((c2 >> 8 * k) & 0xFFu) << 16
-                                  : source_of<KIND>(a, p.f, Y, X);
-      px[k] = ac != 1u ? s : tint(s, pal[l], edge_at<CR>(t.labels + q, l, Y, X, t.H, t.W), t.a256);
-    }
-    unsigned char* o = a.out + 3L * ps;
-    if (whole) {
-      uint32_t* o4 = (uint32_t*)o;                                    // 4-byte aligned by the groups' layout
-      o4[0] = px[0] | px[1] << 24;
-      o4[1] = px[1] >> 8 | px[2] << 16;
-      o4[2] = px[2] >> 16 | px[3] << 8;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (ps + k >= lo && ps + k < hi) {
-          o[3 * k] = (unsigned char)px[k]; o[3 * k + 1] = (unsigned char)(px[k] >> 8); o[3 * k + 2] = (unsigned char)(px[k] >> 16);
-        }
-    }
-  }
+  paint_blur_rgb<KIND, CR>(a, p, pal, act, res, tid);
 }
 
 // -> MDQE_OK where the kernel was launched, MDQE_ELAUNCH where the LDS it needs was not granted (nothing is launched then)
 template <int KIND>
-int launch_within(int contour, dim3 grid, size_t lds, hipStream_t stream, const WithinArgs& a) {
+int launch_within(int contour, dim3 grid, size_t lds, hipStream_t stream, const BlurArgs& a) {
   int st = MDQE_OK;
   with_contour(contour, [&](auto R) {
     if (a.t.radius <= ROWS_FIRST_TO) {                                 // (never above 64 KB)
@@ -360,21 +272,6 @@ int launch_within(int contour, dim3 grid, size_t lds, hipStream_t stream, const 
 }
 
 // ---- surfaces -----------------------------------------------------------------------------------------------------------------------
-constexpr int CTH = TH / 2, CTW = TW / 2;        // the chroma tile: the pairs under the luma tile
-
-struct WithinYuvArgs {
-  TileArgs t;
-  const unsigned short* taps_c;                  // [n_taps_c]
-  int n_taps_c, radius_c;                        // (as TileArgs' n_taps and radius)
-  const unsigned char* y;
-  const unsigned char* uv;
-  const unsigned short* palette;                 // [256, 3]: Y, U, V in sample units
-  unsigned char* oy;                             // at frame f_off already
-  unsigned char* ouv;
-  long y_pitch, y_stride, uv_pitch, uv_stride;   // bytes
-  long oy_pitch, oy_stride, ouv_pitch, ouv_stride;
-};
-
 // The dynamic LDS of a surface launch, in bytes: the 32-bit planes first (luma Hn, then U and V Hn), then the 16-bit planes: luma source
 // and Hw, U and V source and the pairs' Hw, then the results.
 struct WithinYuvLds {
@@ -395,7 +292,7 @@ struct WithinYuvLds {
 };
 
 template <int FMT, int CR, bool CF>               // CF: as the RGB kernel's, for the LUMA radius; the chroma passes go by their own
-__global__ __launch_bounds__(256) void render_blur_within_yuv_kernel(const WithinYuvArgs a) {
+__global__ __launch_bounds__(256) void render_blur_within_yuv_kernel(const BlurYuvArgs a) {
   extern __shared__ __align__(16) unsigned char dyn[];
   __shared__ uint32_t pal[256];
   __shared__ unsigned char act[256];
@@ -405,24 +302,11 @@ __global__ __launch_bounds__(256) void render_blur_within_yuv_kernel(const Withi
   using ACC = typename std::conditional<FMT == 0, uint32_t, uint64_t>::type;   // N of 10-bit values needs more than 32 bits
   const TileArgs& t = a.t;
   const int tid = (int)threadIdx.x;
-  pal[tid] = pack_yuv(a.palette + 3 * tid);
-  act[tid] = t.action[tid];
-  if (tid <= MAX_R) taps[tid] = tid < t.n_taps ? (uint32_t)t.taps[tid] : 0u;
-  if (tid <= MAX_RC) taps_c[tid] = tid < a.n_taps_c ? (uint32_t)a.taps_c[tid] : 0u;
-  if (tid == 0) flag = 0;
-  __syncthreads();
-  const TilePos p = tile_pos(t);
-  constexpr int BPS = FMT ? 2 : 1;                                   // bytes per sample
+  load_taps(taps_c, a.taps_c, a.n_taps_c, MAX_RC, tid);
+  const TilePos p = tile_begin(t, pack_yuv(a.palette + 3 * tid), pal, act, taps, &flag, tid);
   const unsigned char* yf = a.y + p.f * a.y_stride;                  // the frame's planes
   const unsigned char* cf = a.uv + p.f * a.uv_stride;
-  const unsigned char* y0 = yf + (long)p.Y0 * a.y_pitch + (long)p.X0 * BPS;               // sample (Y0, X0)
-  const unsigned char* c0p = cf + (long)(p.Y0 / 2) * a.uv_pitch + (long)p.X0 * BPS;       // pair (Y0 / 2, X0 / 2)
-  unsigned char* oy0 = a.oy + p.f * a.oy_stride + (long)p.Y0 * a.oy_pitch + (long)p.X0 * BPS;
-  unsigned char* oc0 = a.ouv + p.f * a.ouv_stride + (long)(p.Y0 / 2) * a.ouv_pitch + (long)p.X0 * BPS;
   const unsigned char* labf = t.labels + (long)p.f * t.H * t.W;      // the frame's labels
-  const unsigned char* lab0 = labf + (long)p.Y0 * t.W + p.X0;
-  flag_tile(t, p, act, &flag, tid);
-  __syncthreads();
   const WithinYuvLds at(t.radius, a.radius_c);
   const unsigned short* ry = (const unsigned short*)(dyn + at.ry);     // [TH][TW]: blurred luma values
   const unsigned short* rc = (const unsigned short*)(dyn + at.rc);     // [2][CTH][CTW]: blurred U, V of the pairs
@@ -492,57 +376,11 @@ __global__ __launch_bounds__(256) void render_blur_within_yuv_kernel(const Withi
     });
     __syncthreads();
   }
-  // paint: item j of row pair rp is the 2 x 2 block at column 2 * j of the tile (render_blur.hip's painter)
-  const int chr = (p.th + 1) / 2;
-  for (int it = tid; it < chr * CTW; it += 256) {
-    const int rp = it / CTW, j = it % CTW;
-    const int cb = 2 * j;                                             // column inside the tile
-    if (cb >= p.tw) continue;
-    const int r0 = p.Y0 + 2 * rp, c0 = p.X0 + cb;
-    const int nr = r0 + 1 < t.H ? 2 : 1, nc = c0 + 1 < t.W ? 2 : 1;
-    const unsigned char* yrow = y0 + (long)(2 * rp) * a.y_pitch;
-    const unsigned char* crow = c0p + (long)rp * a.uv_pitch;
-    unsigned char* oyrow = oy0 + (long)(2 * rp) * a.oy_pitch;
-    unsigned char* ocrow = oc0 + (long)rp * a.ouv_pitch;
-    const unsigned char* lab = lab0 + (long)(2 * rp) * t.W + cb;
-    const uint32_t ru = row_raw<FMT>(crow, cb), rv = row_raw<FMT>(crow, cb + 1);
-    const uint32_t U = value_of<FMT>(ru), V = value_of<FMT>(rv);
-    uint32_t su = 0u, sv = 0u;
-    bool kept = true;
-#pragma unroll
-    for (int row = 0; row < 2; ++row) {
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        if (row >= nr || k >= nc) continue;
-        const unsigned char* q = lab + (long)row * t.W + k;
-        const uint32_t l = q[0], ac = act[l];
-        const uint32_t raw = row_raw<FMT>(yrow + (long)row * a.y_pitch, cb + k);
-        uint32_t o = raw;
-        if (ac == 3u) {                                               // (only in a flagged tile; the pixel's pair is a member)
-          o = stored<FMT>((uint32_t)ry[(2 * rp + row) * TW + cb + k]);
-          su += rc[rp * CTW + j]; sv += rc[CTH * CTW + rp * CTW + j];
-          kept = false;
-        } else if (ac == 1u) {
-          const bool edge = edge_at<CR>(q, l, r0 + row, c0 + k, t.H, t.W);
-          const uint32_t col = pal[l];
-          o = stored<FMT>(tint1(value_of<FMT>(raw), comp<FMT>(col, 0), edge, t.a256));
-          su += tint1(U, comp<FMT>(col, 1), edge, t.a256);
-          sv += tint1(V, comp<FMT>(col, 2), edge, t.a256);
-          kept = false;
-        } else {
-          su += U; sv += V;
-        }
-        row_put<FMT>(oyrow + (long)row * a.oy_pitch, cb + k, o);
-      }
-    }
-    const uint32_t sh = (uint32_t)(nr * nc) >> 1;                       // n = 1, 2, 4: n / 2 = log2(n) = 0, 1, 2
-    row_put<FMT>(ocrow, cb, kept ? ru : stored<FMT>((su + sh) >> sh));
-    row_put<FMT>(ocrow, cb + 1, kept ? rv : stored<FMT>((sv + sh) >> sh));
-  }
+  paint_blur_blocks<FMT, CR>(a, p, pal, act, ry, rc, tid);
 }
 
 template <int FMT>
-int launch_within_yuv(int contour, dim3 grid, size_t lds, hipStream_t stream, const WithinYuvArgs& a) {
+int launch_within_yuv(int contour, dim3 grid, size_t lds, hipStream_t stream, const BlurYuvArgs& a) {
   int st = MDQE_OK;
   with_contour(contour, [&](auto R) {
     if (a.t.radius <= ROWS_FIRST_TO) {                                 // (never above 64 KB)
@@ -562,21 +400,11 @@ extern "C" int mdqe_render_blur_within_u8(const void* frames, int is_u8, long fr
                                           const unsigned char* labels, int F, int Ho, int Wo,
                                           const unsigned char* palette, const unsigned char* action, int a256, int contour,
                                           const unsigned short* taps, int radius, unsigned char* out, int f_off, void* stream) {
-  MDQE_REQUIRE(radius >= 0 && radius <= MAX_R);
-  WithinArgs a;
-  const int st = rgb_call(frames, frame_stride, h0, w0, labels, F, Ho, Wo, palette, action, true, a256, contour, out, f_off, a.src, a.ident, a.out);
+  BlurArgs a;
+  long tiles = 0;
+  const int st = blur_rgb_call(frames, frame_stride, h0, w0, labels, F, Ho, Wo, palette, action, a256, contour, taps, radius, out, f_off, a, tiles);
   if (st != MDQE_OK || F == 0) return st;
-  MDQE_CHECK_PTR(taps);
-  MDQE_REQUIRE(((uintptr_t)taps & 1u) == 0);
-  const long tiles = tile_args(a.t, labels, action, taps, radius, F, Ho, Wo, a256);
-  a.palette = palette;
-  a.head = (unsigned)((uintptr_t)a.out & 3u);
-  // (the groups of a segment: as mdqe_render_blur_u8)
-  a.items = TW / 4 + ((Wo & 3) == 0 && a.head == 0 ? 0 : 1);
-  a.m_items = magic(a.items);
-  const int SH = TH + 2 * a.t.radius;
-  const int SW = TW + 2 * a.t.radius;
-  a.src_bytes = 4 * SH * SW;                                          // (>= 4 * TH * TW)
+  a.src_bytes = 4 * (TH + 2 * a.t.radius) * (TW + 2 * a.t.radius);    // (>= 4 * TH * TW)
   const size_t lds = (size_t)a.src_bytes + (size_t)kept_sums(TH, TW, a.t.radius) * (3 * sizeof(uint32_t) + sizeof(unsigned short));     // <= 69632
   mdqe_clear_error();
   const dim3 grid((unsigned)tiles);
@@ -594,35 +422,11 @@ extern "C" int mdqe_render_blur_within_yuv420sp(const void* y, long y_pitch, lon
                                                 const unsigned short* taps, int radius, const unsigned short* taps_c, int radius_c,
                                                 void* out_y, long out_y_pitch, long out_y_stride,
                                                 void* out_uv, long out_uv_pitch, long out_uv_stride, int f_off, void* stream) {
-  MDQE_REQUIRE(radius >= 0 && radius <= MAX_R && radius_c >= 0 && radius_c <= MAX_RC);
-  // not in place: the taps read samples that other threads write
-  SurfaceOut o;
-  const int st = surface_call(y, y_pitch, y_stride, uv, uv_pitch, uv_stride, F, H, W, fmt, labels, palette_yuv, action, true, false, a256,
-                              contour, out_y, out_y_pitch, out_y_stride, out_uv, out_uv_pitch, out_uv_stride, f_off, o);
+  BlurYuvArgs a;
+  long tiles = 0;
+  const int st = blur_yuv_call(y, y_pitch, y_stride, uv, uv_pitch, uv_stride, F, H, W, fmt, labels, palette_yuv, action, a256, contour, taps, radius,
+                               taps_c, radius_c, out_y, out_y_pitch, out_y_stride, out_uv, out_uv_pitch, out_uv_stride, f_off, a, tiles);
   if (st != MDQE_OK || F == 0) return st;
-  MDQE_CHECK_PTR(taps);
-  MDQE_CHECK_PTR(taps_c);
-  MDQE_REQUIRE((((uintptr_t)taps | (uintptr_t)taps_c) & 1u) == 0);
-  {
-    // the overlap refusals of surface_call, for the two tap tables
-    const long bps = fmt ? 2 : 1, yb = bps * W, cb = bps * 2 * ((W + 1L) / 2), CH = (H + 1L) / 2;
-    const Plane ty = plane_of(o.oy, out_y_pitch, out_y_stride, F, H, yb), tc = plane_of(o.ouv, out_uv_pitch, out_uv_stride, F, CH, cb);
-    const Plane s1 = plane_of(taps, 2L * (radius + 1), 0, 1, 1, 2L * (radius + 1));
-    const Plane s2 = plane_of(taps_c, 2L * (radius_c + 1), 0, 1, 1, 2L * (radius_c + 1));
-    MDQE_REQUIRE(apart(s1, ty) && apart(s1, tc) && apart(s2, ty) && apart(s2, tc));
-  }
-  WithinYuvArgs a;
-  const long tiles = tile_args(a.t, labels, action, taps, radius, F, H, W, a256);
-  a.taps_c = taps_c;
-  a.n_taps_c = radius_c + 1;
-  a.radius_c = padded(radius_c);
-  a.y = (const unsigned char*)y;
-  a.uv = (const unsigned char*)uv;
-  a.palette = palette_yuv;
-  a.oy = o.oy;
-  a.ouv = o.ouv;
-  a.y_pitch = y_pitch; a.y_stride = y_stride; a.uv_pitch = uv_pitch; a.uv_stride = uv_stride;
-  a.oy_pitch = out_y_pitch; a.oy_stride = out_y_stride; a.ouv_pitch = out_uv_pitch; a.ouv_stride = out_uv_stride;
   const size_t lds = (size_t)WithinYuvLds(a.t.radius, a.radius_c).end;                       // <= 51200
   mdqe_clear_error();
   const dim3 grid((unsigned)tiles);

@@ -26,8 +26,10 @@
 // pixels and d <= 124).
 // Both kernels say a phase once: the LDS block (TileLds, init_lds), tile_pos, flag_cells, the sum loop (sum_flagged over what a lane adds
 // up: RgbSum, LumaSum, ChromaSum; the fast loads are the loader each kernel passes in) and cell_means.  The rule's pieces (source pixel,
-// tints, sample helpers, contour test and dispatch) and the entries' checks are render_rule.h's, shared with the plain painters.
-#include "render_rule.h"
+// tints, sample helpers, contour test and dispatch) and the entries' checks are render_rule.h's, shared with the plain painters; the RGB
+// paint phase (paint_rgb_tile, with the groups' count and the multiplications by ceil(2^32 / d)) is render_tile_paint.h's, shared with
+// the two blurs.  The surface paint phase is this file's own: 2 rows x PX pixels per thread with chunked loads.
+#include "render_tile_paint.h"
 
 namespace {
 
@@ -44,9 +46,6 @@ Tile tile_of(int cell) {
   return {ny, nx};
 }
 
-uint32_t magic(int d) { return (uint32_t)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }   // d >= 2
-__device__ __forceinline__ int mdiv(int n, uint32_t m) { return (int)__umulhi((uint32_t)n, m); }
-
 struct TileArgs {
   const unsigned char* labels;   // [F, H, W]
   const unsigned char* action;   // [256]
@@ -59,8 +58,6 @@ struct TileArgs {
   int items;                     // paint items per tile row (RGB) or row pair (surfaces)
   uint32_t a256;
 };
-
-struct TilePos { int f, Y0, X0, th, tw; };                            // frame, origin, in-picture rows and columns of the tile
 
 __device__ __forceinline__ TilePos tile_pos(const TileArgs& a) {
   unsigned b = blockIdx.x;
@@ -195,12 +192,6 @@ struct MosaicArgs {
   int ident;
 };
 
-// the source pixel of output pixel (f, Y, X)
-template <int KIND>
-__device__ __forceinline__ uint32_t source_of(const MosaicArgs& a, int f, int Y, int X) {
-  return source_px<KIND>(a.src, a.ident, (long)f * a.src.frame_stride, Y, X, a.t.H, a.t.W);
-}
-
 template <int KIND, int R>
 __global__ __launch_bounds__(256) void render_mosaic_kernel(const MosaicArgs a) {
   TILE_LDS(lds);
@@ -223,67 +214,24 @@ __global__ __launch_bounds__(256) void render_mosaic_kernel(const MosaicArgs a) 
       } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-          if (c + k < p.tw) v.px(source_of<KIND>(a, p.f, p.Y0 + r, p.X0 + c + k));
+          if (c + k < p.tw) v.px(source_of<KIND>(a.src, a.ident, p.f, p.Y0 + r, p.X0 + c + k, t.H, t.W));
       }
       return v;
     });
   else
     sum_flagged<1, 1, RgbSum>(t, lds, tid, p.th, p.tw, t.TW, t.m_tw, t.G, [&](int r, int c) {
       RgbSum v;
-      v.px(source_of<KIND>(a, p.f, p.Y0 + r, p.X0 + c));
+      v.px(source_of<KIND>(a.src, a.ident, p.f, p.Y0 + r, p.X0 + c, t.H, t.W));
       return v;
     });
   __syncthreads();
   cell_means<8, false>(t, p, lds, tid);
   __syncthreads();
-  // paint: item j of tile row r is the j-th group of 4 flat pixels that meets the row's segment
-  for (int it = tid; it < p.th * t.items; it += 256) {
-    const int r = mdiv(it, t.m_items), j = it - r * t.items;
-    const int Y = p.Y0 + r;
-    const long row = ((long)p.f * t.H + Y) * t.W;                    // flat pixel of (f, Y, 0), < 2^31
-    const long seg = row + p.X0;                                      // the segment: flat pixels [seg, seg + tw)
-    const long ps = 4 * ((seg + 4 - a.head) / 4 + j) + a.head - 4;    // the group's first flat pixel (may lie before seg)
-    const long lo = ps > seg ? ps : seg, hi = ps + 4 < seg + p.tw ? ps + 4 : seg + p.tw;
-    if (lo >= hi) continue;
-    const int cyn = mdiv(r, t.m_cell) * t.nx;
-    const bool whole = hi - lo == 4;
-    uint32_t l4 = 0u, c0 = 0u, c1 = 0u, c2 = 0u;
-    const bool wide_src = KIND == 1 && whole && a.ident;
-    if (whole) l4 = ld4(t.labels + ps);
-    if (wide_src) {
-      const unsigned char* q = (const unsigned char*)a.src.frames + (long)p.f * a.src.frame_stride + (long)Y * a.src.w0 + (int)(ps - row);
-      c0 = ld4(q); c1 = ld4(q + a.src.plane); c2 = ld4(q + 2 * a.src.plane);
-    }
-    uint32_t px[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const long q = ps + k;
-      if (q < lo || q >= hi) continue;
-      const int X = (int)(q - row);
-      const uint32_t l = whole ? (l4 >> 8 * k) & 0xFFu : (uint32_t)t.labels[q];
-      const uint32_t ac = lds.act[l];
-      if (ac == 2u) {
-        px[k] = lds.mean[cyn + mdiv(X - p.X0, t.m_cell)];
-        continue;
-      }
-      const uint32_t s = wide_src ? ((c0 >> 8 * k) & 0xFFu) | ((c1 >> 8 * k) & 0xFFu) << 8 | ((c2 >> 8 * k) & 0xFFu) << 16
-                                  : source_of<KIND>(a, p.f, Y, X);
-      px[k] = ac == 0u ? s : tint(s, lds.pal[l], edge_at<R>(t.labels + q, l, Y, X, t.H, t.W), t.a256);
-    }
-    unsigned char* o = a.out + 3L * ps;
-    if (whole) {
-      uint32_t* o4 = (uint32_t*)o;                                    // 4-byte aligned by the groups' layout
-      o4[0] = px[0] | px[1] << 24;
-      o4[1] = px[1] >> 8 | px[2] << 16;
-      o4[2] = px[2] >> 16 | px[3] << 8;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (ps + k >= lo && ps + k < hi) {
-          o[3 * k] = (unsigned char)px[k]; o[3 * k + 1] = (unsigned char)(px[k] >> 8); o[3 * k + 2] = (unsigned char)(px[k] >> 16);
-        }
-    }
-  }
+  // paint (render_tile_paint.h): action 2 takes the cell's mean, every other action but 0 tints
+  paint_rgb_tile<KIND, R, 2u>(
+      t.labels, t.H, t.W, t.a256, a.src, a.ident, a.out, a.head, p, t.items, t.m_items, lds.pal, lds.act, tid,
+      [&](int r) { return [&lds, &t, cyn = mdiv(r, t.m_cell) * t.nx](int x) { return lds.mean[cyn + mdiv(x, t.m_cell)]; }; },
+      [](uint32_t ac) { return ac != 0u; });
 }
 
 template <int KIND>
@@ -500,9 +448,7 @@ extern "C" int mdqe_render_mosaic_u8(const void* frames, int is_u8, long frame_s
   const long tiles = tile_args(a.t, labels, action, F, Ho, Wo, cell, a256);
   a.palette = palette;
   a.head = (unsigned)((uintptr_t)a.out & 3u);
-  // a segment of TW pixels meets at most TW / 4 + 1 groups; exactly TW / 4 where every segment starts a group (Wo and the tiles'
-  // width are multiples of 4 and so is the output address)
-  a.t.items = a.t.TW / 4 + ((Wo & 3) == 0 && a.head == 0 ? 0 : 1);
+  a.t.items = paint_items(a.t.TW, Wo, a.head);
   a.t.m_items = magic(a.t.items);
   mdqe_clear_error();
   const dim3 grid((unsigned)tiles);

@@ -691,17 +691,21 @@ def final_masks_overlap(logits, inst_idx, factor, h, w, Ho, Wo, gt_bits, G, f_of
     return inter, area
 
 
-def _mosaic_args(name, action, cell):
+def _action_arg(name, action):
+    """The per-label action table of the painters that take one."""
     if not torch.is_tensor(action) or action.dtype != torch.uint8 or tuple(action.shape) != (256,) or not action.is_contiguous():
         raise RuntimeError("%s: action must be contiguous uint8 [256] (render.Style.actions)" % name)
+
+
+def _mosaic_args(name, action, cell):
+    _action_arg(name, action)
     if isinstance(cell, bool) or not isinstance(cell, int) or not 2 <= cell <= 64 or cell % 2:
         raise RuntimeError("%s: cell must be an even int in 2..64, got %r" % (name, cell))
 
 
 def _blur_args(name, action, taps, taps_c=None, surface=False):
     """The action table and the tap tables of the blur painters (render.blur_taps): luma / RGB radius 0..32, chroma 0..16."""
-    if not torch.is_tensor(action) or action.dtype != torch.uint8 or tuple(action.shape) != (256,) or not action.is_contiguous():
-        raise RuntimeError("%s: action must be contiguous uint8 [256] (render.Style.actions)" % name)
+    _action_arg(name, action)
     for t, what, top in ((taps, "taps", 32),) + (((taps_c, "taps_c", 16),) if surface else ()):
         if (not torch.is_tensor(t) or t.dtype not in (torch.uint16, torch.int16) or t.dim() != 1 or not 1 <= t.numel() <= top + 1
                 or not t.is_contiguous()):
@@ -710,8 +714,7 @@ def _blur_args(name, action, taps, taps_c=None, surface=False):
 
 def _replace_args(name, action, matte, backdrop, F, H, W):
     """The action table, the matte and an RGB backdrop of the compositing painter."""
-    if not torch.is_tensor(action) or action.dtype != torch.uint8 or tuple(action.shape) != (256,) or not action.is_contiguous():
-        raise RuntimeError("%s: action must be contiguous uint8 [256] (render.Style.actions)" % name)
+    _action_arg(name, action)
     if not torch.is_tensor(matte) or matte.dtype != torch.uint8 or tuple(matte.shape) != (F, H, W) or not matte.is_contiguous():
         raise RuntimeError("%s: matte must be contiguous uint8 [F = %d, %d, %d], the labels' shape (ops.final_matte)" % (name, F, H, W))
     if (not torch.is_tensor(backdrop) or backdrop.dtype != torch.uint8 or tuple(backdrop.shape) not in ((3,), (H, W, 3))
@@ -825,8 +828,7 @@ def render_replace_yuv(labels, yuv, palette_yuv, action, matte, backdrop, out=No
     if not isinstance(yuv, YuvFrames):
         raise RuntimeError("%s: yuv must be a preprocess.YuvFrames, got %s" % (name, type(yuv).__name__))
     F, H, W = len(yuv), yuv.height, yuv.width
-    if not torch.is_tensor(action) or action.dtype != torch.uint8 or tuple(action.shape) != (256,) or not action.is_contiguous():
-        raise RuntimeError("%s: action must be contiguous uint8 [256] (render.Style.actions)" % name)
+    _action_arg(name, action)
     if not torch.is_tensor(matte) or matte.dtype != torch.uint8 or tuple(matte.shape) != (F, H, W) or not matte.is_contiguous():
         raise RuntimeError("%s: matte must be contiguous uint8 [F = %d, %d, %d], the surfaces' own size (ops.final_matte)" % (name, F, H, W))
     surf = isinstance(backdrop, YuvFrames)
@@ -1071,38 +1073,30 @@ def render_blur_yuv(labels, yuv, palette_yuv, action, taps, taps_c, out=None, f_
     return _paint_yuv_host(labels, yuv, palette_yuv, out, f_off, a256, contour, action, taps=(taps, taps_c), within=stop)
 
 
+def _tap_sums(t, dim, taps):
+    """sum_d taps[|d|] * t[.. + d ..] along `dim` of an int64 tensor, the border replicated: one pass of the blurs, not rounded."""
+    w = (taps.view(torch.int16).to(torch.int64) & 0xFFFF).tolist()
+    R = len(w) - 1
+    n = t.shape[dim]
+    idx = torch.arange(n)
+    acc = torch.zeros_like(t)
+    for d in range(-R, R + 1):
+        acc += w[abs(d)] * t.index_select(dim, (idx + d).clamp(0, n - 1))
+    return acc
+
+
 def _blur_plane(v, taps):
     """v int64 [F, h, w] -> the blur of include/mdqe_hip.h: rows first, (sum + 128) >> 8, then columns, (sum + 32768) >> 16, the
     border replicated."""
-    w = (taps.view(torch.int16).to(torch.int64) & 0xFFFF).tolist()
-    R = len(w) - 1
-
-    def one(t, dim, add, shift):
-        n = t.shape[dim]
-        idx = torch.arange(n)
-        acc = torch.zeros_like(t)
-        for d in range(-R, R + 1):
-            acc += w[abs(d)] * t.index_select(dim, (idx + d).clamp(0, n - 1))
-        return (acc + add) >> shift
-    return one(one(v, 2, 128, 8), 1, 32768, 16)
+    return (_tap_sums((_tap_sums(v, 2, taps) + 128) >> 8, 1, taps) + 32768) >> 16
 
 
 def _blur_plane_within(v, member, taps):
     """v int64 [F, h, w], member bool [F, h, w] -> the edge-stopping blur of include/mdqe_hip.h (mdqe_render_blur_within_u8): the taps
     weigh member * v and member, rows then columns with no rounding between, the border replicated with its membership, then
     (N + D // 2) // D where `member`, 0 elsewhere (there the value is not defined and D may be 0).  N stays below 2^34."""
-    w = (taps.view(torch.int16).to(torch.int64) & 0xFFFF).tolist()
-    R = len(w) - 1
     m = member.to(torch.int64)
-
-    def one(t, dim):
-        n = t.shape[dim]
-        idx = torch.arange(n)
-        acc = torch.zeros_like(t)
-        for d in range(-R, R + 1):
-            acc += w[abs(d)] * t.index_select(dim, (idx + d).clamp(0, n - 1))
-        return acc
-    N, D = one(one(m * v, 2), 1), one(one(m, 2), 1)
+    N, D = _tap_sums(_tap_sums(m * v, 2, taps), 1, taps), _tap_sums(_tap_sums(m, 2, taps), 1, taps)
     return torch.where(member, (N + D // 2) // D.clamp(min=1), torch.zeros_like(N))
 
 

@@ -400,12 +400,13 @@ class Style:
         are made)."""
         return self.trail > 0
 
-    def _cached_on(self, slot, key, make):
-        """A small host-made table on a device, made once per `key` (as `palette_on` keeps the palette)."""
+    def _cached_on(self, slot, key, make, to=lambda t, device: t.contiguous().to(device)):
+        """What `make()` gives on the host, on the device key[0]: made and moved there once per `key` -- one tiny upload per session, not
+        per window.  `to(made, device)` moves it: a small table (a tensor) by default."""
         cache = self.__dict__.setdefault(slot, {})
         if key not in cache:
-            cache[key] = make().contiguous().to(key[0])
-            if cache[key].is_cuda:
+            cache[key] = to(make(), key[0])
+            if cache[key].is_cuda:                 # later windows read it on other streams: the one upload is complete before it is handed out
                 torch.cuda.current_stream(cache[key].device).synchronize()
         return cache[key]
 
@@ -501,25 +502,14 @@ class Style:
         key = (str(device), fmt, matrix, bool(full_range), order)
         if not isinstance(self.backdrop, YuvFrames):
             return self._cached_on("_backdrop_yuv_on", key, lambda: backdrop_yuv(self.backdrop, fmt, matrix, bool(full_range), order))
-        cache = self.__dict__.setdefault("_backdrop_yuv_on", {})
-        if key not in cache:
-            cache[key] = self.backdrop.to(device)
-            if cache[key].is_cuda:
-                torch.cuda.current_stream(cache[key].device).synchronize()
-        return cache[key]
+        return self._cached_on("_backdrop_yuv_on", key, lambda: self.backdrop, YuvFrames.to)
 
     def actions_on(self, device, cls_probs=None):
         """`actions` on `device`: cached per device as the palette is where the table does not depend on the window (no `classes`);
         with `classes` built from the window's class rows and uploaded, 256 bytes per window."""
         if self.classes is not None:
             return self.actions(cls_probs).to(device)
-        cache = self.__dict__.setdefault("_act_on", {})
-        key = str(device)
-        if key not in cache:
-            cache[key] = self.actions().to(device)
-            if cache[key].is_cuda:
-                torch.cuda.current_stream(cache[key].device).synchronize()
-        return cache[key]
+        return self._cached_on("_act_on", (str(device),), self.actions)
 
     def taps_on(self, device):
         """`blur_taps(blur_radius)` on `device` (cached per device, as `palette_on` keeps the palette)."""
@@ -530,26 +520,14 @@ class Style:
         return self._cached_on("_taps_c_on", (str(device), self.blur_radius), lambda: blur_taps((self.blur_radius + 1) // 2))
 
     def palette_on(self, device):
-        """The palette on `device`, contiguous (cached per device: one tiny upload per session, not per window)."""
-        cache = self.__dict__.setdefault("_on", {})
-        key = str(device)
-        if key not in cache:
-            pal = default_palette() if self.palette is None else self.palette
-            cache[key] = pal.contiguous().to(device)
-            if cache[key].is_cuda:                 # later windows read it on other streams: the one upload is complete before it is handed out
-                torch.cuda.current_stream(cache[key].device).synchronize()
-        return cache[key]
+        """The palette on `device`, contiguous (cached per device)."""
+        return self._cached_on("_on", (str(device),), lambda: default_palette() if self.palette is None else self.palette)
 
     def palette_yuv_on(self, device, fmt, matrix, full_range, order):
         """`palette_yuv` of the palette on `device` (cached per device and kind of surface, as `palette_on` is)."""
-        cache = self.__dict__.setdefault("_yuv_on", {})
-        key = (str(device), fmt, matrix, bool(full_range), order)
-        if key not in cache:
-            pal = default_palette() if self.palette is None else self.palette
-            cache[key] = palette_yuv(pal, fmt, matrix, bool(full_range), order).contiguous().to(device)
-            if cache[key].is_cuda:
-                torch.cuda.current_stream(cache[key].device).synchronize()
-        return cache[key]
+        return self._cached_on("_yuv_on", (str(device), fmt, matrix, bool(full_range), order),
+                               lambda: palette_yuv(default_palette() if self.palette is None else self.palette, fmt, matrix,
+                                                   bool(full_range), order))
 
 
 @dataclasses.dataclass(frozen=True)
