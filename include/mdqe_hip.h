@@ -993,6 +993,52 @@ int mdqe_grow_labels_u8(const unsigned char* labels, int F, int Ho, int Wo,
                         const unsigned char* grow /* [256], device */, int radius,
                         unsigned char* out /* [F, Ho, Wo] */, void* stream);
 
+/* Object removal (csrc/plate.hip): a BACKGROUND PLATE learned from the pixels no track covers, and the picture of it that the
+ * compositing painters (mdqe_render_replace_u8 / mdqe_render_replace_yuv420sp) take as their backdrop picture or surface, so that
+ * replaced tracks show the scene behind them.  Per video and device, STATE on the output grid, int32, 16-byte aligned, all zero when fresh:
+ *   RGB       plate   [Ho, Wo, 4]  cells (P_0, P_1, P_2, n);
+ *   surfaces  plate_y [H, W, 2]    cells (P, n), and plate_c [ch, cw, 4] cells (P_U, P_V, n, 0), ch = (H + 1) / 2, cw = (W + 1) / 2.
+ * P is the sample in 24.8 fixed point, n the number of observations, saturating at n_max (1..256).  A state started from an empty-scene
+ * picture holds P = 256 * value and n = 1 everywhere.  Integers only, ONE definition:
+ *   observed  block: uint8 [F, Ho, Wo] (surfaces: [F, H, W]), non-zero = "not background here": the label map, or that map grown by a
+ *             margin (mdqe_grow_labels_u8 with every label growing).  RGB pixel (Y, X) and a luma sample are observed in frame f iff
+ *             block[f, Y, X] == 0; a chroma pair iff every in-picture pixel of its 2 x 2 block is;
+ *   value     RGB: s_c is exactly mdqe_render_overlay_u8's source value (nearest-sampled onto the output grid, float32 by the rint /
+ *             clamp / NaN rule; frames are required); surfaces: the sample itself, word >> 6 for P010;
+ *   update    per observed value, the call's frames in order:  n' = min(n + 1, n_max);  d = 256 * s - P;
+ *             P' = P + floordiv(d + (n' >> 1), n'), floordiv rounding towards minus infinity;  n = n'.  (The channels of a cell share n.)
+ *             The first observation sets P = 256 * s, the first n_max form a rounded cumulative mean, later ones an exponential mean
+ *             of weight 1 / n_max; a background that does not change is reproduced exactly; P stays in [0, 256 * max sample].
+ *   picture   a seen cell (n > 0) shows (P + 128) >> 8 per channel.  A never-seen cell (Y, X) shows the value of the seen cell
+ *             (Y', X') of its plane with the smallest triple (d2, Y', X') in lexicographic order, d2 = (Y - Y')^2 + (X - X')^2 <= reach^2;
+ *             without one it shows `fill`.  Nothing is read beyond the plane.  The chroma plane does the same on its own grid with
+ *             reach (reach + 1) / 2 and the fill's (U, V).  P010 words are written as value << 6.
+ * The minimum separates as mdqe_grow_labels_u8's does: a column pass keeps, per (Y, X'), the smallest key dy^2 << 8 | (dy + reach) over
+ * the seen cells with |dy| <= reach; a row pass scans dx = -reach .. reach ascending and takes a strictly smaller dx^2 << 8 + key --
+ * exactly the definition's triple.
+ * mdqe_plate_update_u8: frames, is_u8, frame_stride, h0, w0 are mdqe_render_overlay_u8's (frames not NULL); mdqe_plate_update_yuv420sp:
+ * y .. fmt are mdqe_render_overlay_yuv420sp's (pitches and strides in BYTES).  One thread per state cell walks the F frames: one
+ * 16-byte (luma: 8-byte) load and store of the cell per launch.  mdqe_plate_picture_u8: out uint8 [Ho, Wo, 3], pixel-interleaved,
+ * fill uint8 [3], device; mdqe_plate_picture_yuv420sp: ONE surface (out_y, out_y_pitch, out_uv, out_uv_pitch) of H x W fmt, fill_yuv
+ * uint16 [3] (Y, U, V) in sample units, device (only the 8 / 10 bits are used).  A tile (16 x 64 cells) whose own cells are all seen
+ * skips the search.  Output padding is never written.
+ * MDQE_EINVAL, before any pointer is looked at: n_max outside 1..256, reach outside 0..32, negative F, Ho, Wo (surfaces: H or W <= 0),
+ * Ho * Wo * 4 >= 2^31, F * Ho * Wo >= 2^31 - 1, h0 or w0 < 1, h0 * Ho or w0 * Wo >= 2^31, frame_stride < 3 * h0 * w0, fmt outside {0, 1},
+ * a pitch smaller than a row, a negative stride, odd P010 pitches or strides.  F == 0 or an empty picture returns OK and launches
+ * nothing.  Then: a null pointer, a state that is not 16-byte aligned, odd P010 plane pointers, and ANY overlap of the state with
+ * an input (frames or surfaces, block, fill) or an output, or of an output with the fill, are MDQE_EINVAL.  Outputs need no alignment
+ * (single samples).  One launch each, no atomics, no global scratch: identical from run to run.  Never allocates, never synchronises. */
+int mdqe_plate_update_u8(const void* frames, int is_u8, long frame_stride, int h0, int w0,
+                         const unsigned char* block, int F, int Ho, int Wo, int n_max, int* plate /* [Ho, Wo, 4] */, void* stream);
+int mdqe_plate_update_yuv420sp(const void* y, long y_pitch, long y_stride, const void* uv, long uv_pitch, long uv_stride,
+                               int F, int H, int W, int fmt /*0 nv12, 1 p010*/, const unsigned char* block, int n_max,
+                               int* plate_y /* [H, W, 2] */, int* plate_c /* [ch, cw, 4] */, void* stream);
+int mdqe_plate_picture_u8(const int* plate, int Ho, int Wo, int reach, const unsigned char* fill /* [3], device */,
+                          unsigned char* out /* [Ho, Wo, 3] */, void* stream);
+int mdqe_plate_picture_yuv420sp(const int* plate_y, const int* plate_c, int H, int W, int fmt /*0 nv12, 1 p010*/, int reach,
+                                const unsigned short* fill_yuv /* [3], device */,
+                                void* out_y, long out_y_pitch, void* out_uv, long out_uv_pitch, void* stream);
+
 /* ---- COCO single-image branch, after the decoder (MDQE.inference_image, mdqe/mdqe.py:486-556), on the centre frame's
  * low-resolution logits [n,Hm,Wm]; aligned_bilinear x`factor` in closed form, crop [:h,:w].
  * stats[k] = {sum(sigmoid*[sigmoid>0.5]), count(sigmoid>0.5), xmin, ymin, xmax, ymax of (logit > 0)} (:512-516, :526;

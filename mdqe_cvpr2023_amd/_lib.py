@@ -70,6 +70,10 @@ SIGNATURES = {
     "mdqe_label_centroids_u8": [p, i, i, i, i, i, p, p, l, i, p],
     "mdqe_label_polygons_u8": [p, i, i, i, i, i, i, i, p, p, p, p, l, p],
     "mdqe_grow_labels_u8": [p, i, i, i, p, i, p, p],
+    "mdqe_plate_update_u8": [p, i, l, i, i, p, i, i, i, i, p, p],
+    "mdqe_plate_update_yuv420sp": [p, l, l, p, l, l, i, i, i, i, p, i, p, p, p],
+    "mdqe_plate_picture_u8": [p, i, i, i, p, p, p],
+    "mdqe_plate_picture_yuv420sp": [p, p, i, i, i, i, p, p, l, p, l, p],
     "mdqe_render_trails_u8": [p, i, i, i, i, p, l, i, i, i, i, p, p],
     "mdqe_render_trails_yuv420sp": [p, l, l, p, l, l, i, i, i, i, i, p, l, i, i, i, i, p, p],
     "mdqe_final_masks_overlap": [p, i, p, i, i, i, i, i, i, i, i, p, i, i, p, l, p, p],

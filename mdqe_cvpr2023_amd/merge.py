@@ -224,7 +224,7 @@ class FrameStore:
         return out
 
 
-def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, source, f0, style, cls, out, o_off, paths=None):
+def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, source, f0, style, cls, out, o_off, paths=None, plate=None):
     """A window's overlay: the label map of window logits m [n, F, Hm, Wm] into labels[l_off:l_off + F] (`label_maps`: all n rows
     compete, as in every label path), then that map painted over video frames [f0, f0 + F) of `source` (a FrameStore) into
     out[o_off:o_off + F] (uint8 [>= o_off + F, Ho, Wo, 3], device) in `style` (render.Style) -- one ops.render_overlay launch per
@@ -247,6 +247,11 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
     labels of the style's `grows` table into a fresh device scratch [F, Ho, Wo], and the painter launches take that scratch's frames
     in place of the label map's: contours and tints are those of the grown map.  Everything else -- `labels` itself, the geometry
     table, the centroids, trails, boxes and captions -- stays that of the map as made; with grow == 0 nothing is allocated or launched.
+    A style that removes objects (style.plate: replace="tracks" with backdrop="plate") needs `plate`, the video's Plate: between the label
+    map and the painters the window's frames teach it (`Plate.observe`: an optional ops.grow_labels launch for the plate's margin, then
+    one ops.plate_update / ops.plate_update_yuv launch per piece, a window without tracks included) and its picture of the scene
+    (`Plate.picture`: one ops.plate_picture / ops.plate_picture_yuv launch) is the backdrop the painters composite; with any other
+    backdrop nothing of this is made or launched.
     -> `label_maps`' geometry table where `geometry` asks for it, else None."""
     from . import ops
     notes = style.annotates and int(m.shape[0]) > 0
@@ -260,7 +265,10 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
     matte = back = None
     if style.replace is not None:
         matte = replace_matte(m, stride, frame_hw, out_size, style, cls)
-        back = style.backdrop_yuv_on(m.device, *out.meta()[2:]) if surface else style.backdrop_on(m.device)
+        if not style.plate:
+            back = style.backdrop_yuv_on(m.device, *out.meta()[2:]) if surface else style.backdrop_on(m.device)
+        elif plate is None:
+            raise RuntimeError("overlay: a style with backdrop='plate' needs the video's Plate (merge.plate_of)")
     taps = style.taps_on(m.device) if style.blur is not None else None
     taps_c = style.taps_c_on(m.device) if taps is not None and surface else None
     edge = {"edge": style.blur_edge} if style.blur_edge != "bleed" else {}     # ("bleed": the blur's calls exactly as they were)
@@ -269,6 +277,9 @@ def overlay_frames(m, stride, frame_hw, out_size, geometry, labels, l_off, sourc
         grown = ops.grow_labels(labels[l_off:l_off + nf], style.grows_on(m.device, cls), style.grow,
                                 torch.empty((nf,) + tuple(labels.shape[1:]), dtype=torch.uint8, device=m.device))
     pieces = source.pieces(int(f0), int(f0) + nf, stream=torch.cuda.current_stream(m.device))
+    if matte is not None and style.plate:
+        plate.observe(labels, l_off, nf, [(t, first - int(f0)) for t, first in pieces])
+        back = plate.picture()
     for t, first in pieces:
         k, d = len(t), first - int(f0)
         lab = labels[l_off + d:l_off + d + k] if grown is None else grown[d:d + k]
@@ -312,6 +323,24 @@ def check_replace(style, out_size, surface):
     from .preprocess import YuvFrames
     Ho, Wo = (int(v) for v in out_size)
     b = style.backdrop
+    if style.plate:                                 # object removal: what the plate starts from is checked as a backdrop picture is
+        b = style.plate_init
+        if isinstance(b, YuvFrames):
+            if not surface:
+                raise ValueError("overlay style: plate_init is a YuvFrames surface but the session paints RGB pictures; give a uint8 "
+                                 "tensor [Ho, Wo, 3], or run the session with surface=True")
+            if (b.height, b.width) != (Ho, Wo) or (isinstance(surface, str) and b.fmt != surface):
+                raise ValueError("overlay style: the plate_init surface is %d x %d %s but the output is %d x %d%s; resize the picture to "
+                                 "the output's size (height, width) and convert it to the session's format"
+                                 % (b.height, b.width, b.fmt, Ho, Wo, " " + surface if isinstance(surface, str) else ""))
+        elif torch.is_tensor(b):
+            if surface:
+                raise ValueError("overlay style: plate_init is an RGB picture but the session paints decoder surfaces; give a "
+                                 "preprocess.YuvFrames of one surface of the session's kind, or run the session with surface=False")
+            if tuple(b.shape[:2]) != (Ho, Wo):
+                raise ValueError("overlay style: the plate_init picture is %d x %d but the output is %d x %d; resize the picture to the "
+                                 "output's size (height, width)" % (b.shape[0], b.shape[1], Ho, Wo))
+        return
     if isinstance(b, YuvFrames):
         if not surface:
             raise ValueError("overlay style: the backdrop is a YuvFrames surface but the session paints RGB pictures; give a uint8 "
@@ -472,6 +501,79 @@ def path_table(forms, style, device, keep=False):
     return PathTable(trail, style.min_area if drawn else 0, device, keep)
 
 
+class Plate:
+    """The background plate of one video on one device: what object removal (render.Style(replace="tracks", backdrop="plate")) shows
+    in place of the tracks.  State on the output grid (the rule: include/mdqe_hip.h, above mdqe_plate_update_u8): RGB `state` int32
+    [Ho, Wo, 4], cells (P_0, P_1, P_2, n); surfaces (`kind`: the YuvFrames.meta() of the session's surfaces) `state` int32 [H, W, 2] and
+    `state_c` int32 [ceil(H/2), ceil(W/2), 4].  All zero when fresh, or P = 256 * value and n = 1 everywhere from style.plate_init.
+    `observe` teaches it a window's frames where the window's label map -- grown by style.plate_margin into `scratch` -- is free;
+    `picture` makes the backdrop the painters take, into `back`, which the video keeps and reuses.  The state, the backdrop and the
+    scratch (one window of labels) are made once: nothing grows with the video.  It belongs to the video, not to the style, which
+    sessions share."""
+
+    def __init__(self, style, out_size, device, kind=None):
+        from .preprocess import YuvFrames
+        self.style, self.device, self.kind = style, device, kind
+        H, W = int(out_size[0]), int(out_size[1])
+        i32 = dict(dtype=torch.int32, device=device)
+        init = style.plate_init_on(device) if style.plate_init is not None else None
+        self.state_c = self.scratch = None
+        if kind is None:
+            self.state = torch.zeros(H, W, 4, **i32)
+            self.back = torch.empty(H, W, 3, dtype=torch.uint8, device=device)
+            self.fill = style.plate_fill_on(device)
+            if init is not None:
+                self.state[..., :3] = init.to(torch.int32) * 256
+                self.state[..., 3] = 1
+        else:
+            ch, cw = (H + 1) // 2, (W + 1) // 2
+            self.state, self.state_c = torch.zeros(H, W, 2, **i32), torch.zeros(ch, cw, 4, **i32)
+            self.back = YuvFrames.empty(1, H, W, fmt=kind[2], device=device, matrix=kind[3], full_range=kind[4], order=kind[5])
+            self.fill = style.plate_fill_yuv_on(device, *kind[2:])
+            if init is not None:
+                def values(t):                     # samples as int32: a P010 word's value is word >> 6
+                    v = t.to(torch.int32) if t.dtype == torch.uint8 else t.view(torch.int16).to(torch.int32) & 0xFFFF
+                    return v >> 6 if kind[2] == "p010" else v
+                self.state[..., 0] = values(init.y[0, :H, :W]) * 256
+                self.state[..., 1] = 1
+                self.state_c[..., :2] = values(init.uv[0, :ch, :2 * cw]).reshape(ch, cw, 2) * 256
+                self.state_c[..., 2] = 1
+        self.every = torch.ones(256, dtype=torch.uint8, device=device) if style.plate_margin > 0 else None     # ops.grow_labels' table: every label grows
+
+    def observe(self, labels, l_off, nf, pieces):
+        """The window's frames teach the plate, on the current stream: labels[l_off:l_off + nf] is the window's label map, `pieces` its
+        frames as (frames [k, 3, h0, w0] or a YuvFrames of k surfaces, offset in the window) in video order."""
+        from . import ops
+        if not nf:
+            return
+        block = labels[l_off:l_off + nf]
+        if self.every is not None:
+            if self.scratch is None or self.scratch.shape[0] < nf:       # (one window of labels; windows have a bounded length)
+                self.scratch = torch.empty((nf,) + tuple(block.shape[1:]), dtype=torch.uint8, device=self.device)
+            block = ops.grow_labels(block, self.every, self.style.plate_margin, self.scratch[:nf])
+        for t, d in pieces:
+            if self.kind is None:
+                ops.plate_update(self.state, t, block[d:d + len(t)], self.style.plate_frames)
+            else:
+                ops.plate_update_yuv(self.state, self.state_c, t, block[d:d + len(t)], self.style.plate_frames)
+
+    def picture(self):
+        """The plate's picture in `back`, on the current stream: uint8 [Ho, Wo, 3], or a YuvFrames of one surface -- what
+        ops.render_replace / ops.render_replace_yuv take as their backdrop picture."""
+        from . import ops
+        if self.kind is None:
+            return ops.plate_picture(self.state, self.fill, self.style.plate_reach, self.back)
+        return ops.plate_picture_yuv(self.state, self.state_c, self.fill, self.back, self.style.plate_reach)
+
+
+def plate_of(forms, style, out_size, device, picture):
+    """The Plate of a video with `forms` and overlay style `style`, or None where the style does not ask for it.  picture: the buffer
+    the overlay is painted into -- a YuvFrames says the kind of the session's surfaces."""
+    if not forms.overlay or style is None or not style.plate:
+        return None
+    return Plate(style, out_size, device, None if torch.is_tensor(picture) else picture.meta())
+
+
 def path_result(rows, n_frames, windows):
     """{"pred_centroids": int32 [n_out, L, 2], "pred_moments": int64 [n_out, L, 3]}: per output j the path of tracker row rows[j] from
     the windows' tables (`windows`: (f_off, frames, rows the window holds, centroids [n, F, 2], moments [n, F, 3]) on the host); the
@@ -576,7 +678,7 @@ def matte_planes(m, stride, frame_hw, out_size, spec, cls, out, f_off):
 
 
 def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels=None, picture=None, paint=None,
-                 hop=lambda stage, geom: geom, crops=None, paths=None, matte=None, polygons=None):
+                 hop=lambda stage, geom: geom, crops=None, paths=None, matte=None, polygons=None, plate=None):
     """What `forms` asks for of ONE flushed window (logits m [n, F, Hm, Wm]), on the current stream, for every path; the only caller
     of `overlay_frames`, `label_maps`, `dense_masks` and `rle_positions`.  First the label map of ALL n rows into labels = (device
     buffer, frame offset) and, with picture = (buffer, offset), its overlay, painted from paint = (FrameStore, first video frame,
@@ -591,13 +693,15 @@ def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels
     polygons = (polygons.Polygons, the window's class rows on the host, first video frame): behind the labels stage the outlines of
     the map's visible regions (`polygon_rings`: they come to the host there), stage "polygons"; the map is then made whether or not it is
     returned.
+    plate (a Plate): the video's background plate, which an overlay in a style with backdrop="plate" teaches and composites.
     -> (labels' geometry table [n, F, 5] or None, planes' table [len(rows), F, 5] or None, (pos, n_pos) of `rle_positions` or None,
     the window's TrackPolygons or None)."""
     lgeom = pgeom = runs = poly = None
     if labels is not None:
         table = forms.label_geometry or crops is not None
         if picture is not None:
-            dgeom = overlay_frames(m, stride, frame_hw, out_size, table, *labels, *paint, *picture, paths=paths)
+            dgeom = overlay_frames(m, stride, frame_hw, out_size, table, *labels, *paint, *picture, paths=paths,
+                                   **({"plate": plate} if plate is not None else {}))
         else:
             dgeom = label_maps(m, stride, frame_hw, out_size, table, *labels)
             if paths is not None:
@@ -767,6 +871,7 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
         d_pic = torch.empty(n_frames, Ho, Wo, 3, **u8) if forms.overlay and not forms.surface else None
         if forms.surface:
             d_pic = surface_picture(frame_source, n_frames, out_size, model.device)
+        plate = plate_of(forms, model.overlay_style if forms.overlay else None, out_size, model.device, d_pic)
         d_planes = torch.zeros(len(sel), n_frames, Ho, Wo, **u8) if forms.planes else None
         d_mat = torch.empty(n_frames, Ho, Wo, **u8) if forms.matte else None
         sel_dev = torch.tensor(sel, dtype=torch.int32, device=model.device) if forms.planes else None
@@ -780,6 +885,7 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
                                      paint=(frame_source, f_off, model.overlay_style, cls_clips[i]) if forms.overlay else None,
                                      crops=(crops.spec, frame_source, f_off, *crops.rows(n), crops.spec.count(f_off)) if forms.crops else None,
                                      paths=paths, matte=(model.matte_output, cls_clips[i], d_mat, f_off) if forms.matte else None,
+                                     **({"plate": plate} if plate is not None else {}),
                                      **({"polygons": (model.polygon_output, cls_clips[i], f_off)} if forms.polygons else {}))
             if forms.polygons:
                 polys.append(poly)
@@ -860,6 +966,7 @@ class ClipMerger:
                               else Forms.of_model(model, emit_masks, geometry))
         self.crop_table = None                      # the early path's CropTable, from its first window
         self.path_table = None                      # the early and the online path's PathTable, from their first window
+        self.plate = None                           # the early and the online path's Plate (a style with backdrop="plate"), from their first window
         self.surface_pitch_align = surface_pitch_align
         self.geometry = forms.plane_geometry or forms.label_geometry
         # False | True | "only" (model.label_output): the label map next to -- or, "only", instead of -- the per-track planes
@@ -1014,6 +1121,8 @@ class ClipMerger:
         cs = copy_stream(self.model) if copies["labels"] or copies["planes"] or copies["crops"] or copies["matte"] or sends_paths else None
         if self.path_table is None:
             self.path_table = path_table(forms, self.style, self.dev, keep=forms.paths and not self.online)
+        if self.plate is None:
+            self.plate = plate_of(forms, self.style, self.out_size, self.dev, pic)
         if self.path_table is not None:
             views = self.path_table.begin(n, nf)
             if forms.paths and self.online:
@@ -1022,6 +1131,7 @@ class ClipMerger:
         out = build_window(m, forms, rows, self.model.cfg.match_stride, self.frame_hw, self.out_size, *at,
                            paint=(self.frame_source, self.f_off, self.style, c), crops=crop, paths=self.path_table,
                            matte=(self.matte_spec, c, mat, 0) if mat is not None else None,
+                           **({"plate": self.plate} if self.plate is not None else {}),
                            **({"polygons": (self.polygon_spec, c, self.f_off)} if forms.polygons else {}),
                            hop=lambda stage, geom: (to_host(cs, self.side, copies[stage], geom, event())
                                                     if copies[stage] or geom is not None else None))   # (a scratch stage: nothing to send)

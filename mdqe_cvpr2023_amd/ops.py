@@ -1412,6 +1412,134 @@ def grow_labels(labels, grow, radius, out=None):
     return out
 
 
+def _plate_state(name, what, t, shape):
+    if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+        raise RuntimeError("%s: %s must be contiguous int32 %s (merge.Plate holds it)" % (name, what, list(shape)))
+
+
+def _plate_rgb(name, plate):
+    if not torch.is_tensor(plate) or plate.dtype != torch.int32 or plate.dim() != 3 or plate.shape[2] != 4 or not plate.is_contiguous():
+        raise RuntimeError("%s: plate must be contiguous int32 [Ho, Wo, 4] (merge.Plate holds it)" % name)
+    return int(plate.shape[0]), int(plate.shape[1])
+
+
+def _plate_int(name, what, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise RuntimeError("%s: %s must be an int in %d..%d, got %r" % (name, what, lo, hi, v))
+
+
+def _plate_block(name, block, F, H, W):
+    if not torch.is_tensor(block) or block.dtype != torch.uint8 or tuple(block.shape) != (F, H, W) or not block.is_contiguous():
+        raise RuntimeError("%s: block must be contiguous uint8 [F = %d, %d, %d] (the label map, or ops.grow_labels of it)" % (name, F, H, W))
+
+
+def _plate_on(name, first, tensors):
+    dev = first.device
+    for t, what in tensors:
+        if not t.is_cuda or t.device != dev:
+            raise RuntimeError("%s: %s must be a CUDA tensor on one device (%s), got %s: the plate has no host path" % (name, what, dev, t.device))
+    return dev
+
+
+def plate_update(plate, frames, block, n_max=64):
+    """The background plate learns from frames: plate (int32 [Ho, Wo, 4], CUDA, cells (P_0, P_1, P_2, n), P in 24.8 fixed point; zeros
+    when fresh) takes, frame by frame, ops.render_overlay's source value of frames ([F, 3, h0, w0] uint8 or float32, each frame
+    contiguous, any stride >= 3*h0*w0 apart) at every pixel where block (uint8 [F, Ho, Wo]) is 0: n' = min(n + 1, n_max), P += floordiv(256 *
+    s - P + (n' >> 1), n') -- the integer rule of include/mdqe_hip.h, mdqe_plate_update_u8.  n_max: an int in 1..256.  One launch on the
+    current stream, in place.  -> plate."""
+    name = "plate_update"
+    # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
+    Ho, Wo = _plate_rgb(name, plate)
+    if (not torch.is_tensor(frames) or frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4 or int(frames.shape[1]) != 3
+            or frames.shape[2] < 1 or frames.shape[3] < 1):
+        raise RuntimeError("%s: frames must be uint8 or float32 [F, 3, h0, w0]" % name)
+    F, h0, w0 = int(frames.shape[0]), int(frames.shape[2]), int(frames.shape[3])
+    stride = int(frames.stride(0)) if F > 1 else 3 * h0 * w0
+    if tuple(frames.stride()[1:]) != (h0 * w0, w0, 1) or stride < 3 * h0 * w0 or h0 * Ho >= 2 ** 31 or w0 * Wo >= 2 ** 31:
+        raise RuntimeError("%s: every frame must be contiguous and the frames a stride >= 3*h0*w0 apart, got strides %s"
+                           % (name, tuple(frames.stride())))
+    _plate_block(name, block, F, Ho, Wo)
+    _plate_int(name, "n_max", n_max, 1, 256)
+    if Ho * Wo * 4 >= 2 ** 31 - 1 or F * Ho * Wo >= 2 ** 31 - 1:
+        raise RuntimeError("%s: Ho*Wo*4 and F*Ho*Wo must stay below 2^31 - 1, got %s" % (name, (F, Ho, Wo)))
+    dev = _plate_on(name, plate, ((plate, "plate"), (frames, "frames"), (block, "block")))
+    with torch.cuda.device(dev):
+        check(lib.mdqe_plate_update_u8(ptr(frames), int(frames.dtype == torch.uint8), stride, h0, w0, ptr(block), F, Ho, Wo, n_max, ptr(plate),
+                                       cur_stream(dev)), name)
+    return plate
+
+
+def plate_update_yuv(plate_y, plate_c, yuv, block, n_max=64):
+    """`plate_update` on decoder surfaces: plate_y (int32 [H, W, 2], cells (P, n)) learns the luma samples where block (uint8 [F, H, W])
+    is 0, plate_c (int32 [ceil(H/2), ceil(W/2), 4], cells (P_U, P_V, n, 0)) the chroma pairs whose whole 2 x 2 block (its in-picture
+    pixels) is 0; a P010 sample's value is word >> 6: include/mdqe_hip.h, mdqe_plate_update_yuv420sp.  yuv: a preprocess.YuvFrames of F
+    surfaces on the device.  One launch, in place.  -> (plate_y, plate_c)."""
+    from .preprocess import YUV_FORMATS, YuvFrames, _pitch_stride
+    name = "plate_update_yuv"
+    if not isinstance(yuv, YuvFrames):
+        raise RuntimeError("%s: yuv must be a preprocess.YuvFrames, got %s" % (name, type(yuv).__name__))
+    F, H, W = len(yuv), yuv.height, yuv.width
+    _plate_state(name, "plate_y", plate_y, (H, W, 2))
+    _plate_state(name, "plate_c", plate_c, ((H + 1) // 2, (W + 1) // 2, 4))
+    _plate_block(name, block, F, H, W)
+    _plate_int(name, "n_max", n_max, 1, 256)
+    if H * W * 4 >= 2 ** 31 - 1 or F * H * W >= 2 ** 31 - 1:
+        raise RuntimeError("%s: H*W*4 and F*H*W must stay below 2^31 - 1, got %s" % (name, (F, H, W)))
+    dev = _plate_on(name, plate_y, ((plate_y, "plate_y"), (plate_c, "plate_c"), (yuv.y, "yuv"), (yuv.uv, "yuv"), (block, "block")))
+    (yp, ys), (cp, cs) = _pitch_stride(yuv.y), _pitch_stride(yuv.uv)
+    with torch.cuda.device(dev):
+        check(lib.mdqe_plate_update_yuv420sp(ptr(yuv.y), yp, ys, ptr(yuv.uv), cp, cs, F, H, W, YUV_FORMATS.index(yuv.fmt), ptr(block), n_max,
+                                             ptr(plate_y), ptr(plate_c), cur_stream(dev)), name)
+    return plate_y, plate_c
+
+
+def plate_picture(plate, fill, reach=16, out=None):
+    """The background plate's picture, the backdrop ops.render_replace takes: out (uint8 [Ho, Wo, 3], CUDA, contiguous; None:
+    allocated) from plate (int32 [Ho, Wo, 4], `plate_update`'s state).  A seen pixel (n > 0) shows (P + 128) >> 8, a never-seen one the
+    seen pixel with the smallest (d2, Y', X') within `reach` pixels (Euclidean; an int in 0..32), else `fill` (uint8 [3] on the device):
+    the integer rule of include/mdqe_hip.h, mdqe_plate_picture_u8.  One launch on the current stream.  -> out."""
+    name = "plate_picture"
+    Ho, Wo = _plate_rgb(name, plate)
+    if not torch.is_tensor(fill) or fill.dtype != torch.uint8 or tuple(fill.shape) != (3,) or not fill.is_contiguous():
+        raise RuntimeError("%s: fill must be contiguous uint8 [3] in the frames' channel order (render.Style.plate_fill_on)" % name)
+    _plate_int(name, "reach", reach, 0, 32)
+    if Ho * Wo * 4 >= 2 ** 31 - 1:
+        raise RuntimeError("%s: Ho*Wo*4 must stay below 2^31 - 1, got %s" % (name, (Ho, Wo)))
+    if out is None:
+        out = torch.empty((Ho, Wo, 3), dtype=torch.uint8, device=plate.device)
+    if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (Ho, Wo, 3) or not out.is_contiguous():
+        raise RuntimeError("%s: out must be contiguous uint8 %s" % (name, [Ho, Wo, 3]))
+    dev = _plate_on(name, plate, ((plate, "plate"), (fill, "fill"), (out, "out")))
+    with torch.cuda.device(dev):
+        check(lib.mdqe_plate_picture_u8(ptr(plate), Ho, Wo, reach, ptr(fill), ptr(out), cur_stream(dev)), name)
+    return out
+
+
+def plate_picture_yuv(plate_y, plate_c, fill_yuv, out, reach=16):
+    """`plate_picture` as one decoder surface, the backdrop ops.render_replace_yuv takes: out (a preprocess.YuvFrames of ONE surface on
+    the device; its height, width and fmt say the planes' sizes and samples) from plate_y and plate_c (`plate_update_yuv`'s state).  The
+    chroma plane is filled on its own grid with reach (reach + 1) // 2; fill_yuv: uint16 [3], (Y, U, V) in sample units
+    (render.backdrop_yuv); P010 words are value << 6: include/mdqe_hip.h, mdqe_plate_picture_yuv420sp.  One launch.  -> out."""
+    from .preprocess import YUV_FORMATS, YuvFrames, _pitch_stride
+    name = "plate_picture_yuv"
+    if not isinstance(out, YuvFrames) or len(out) != 1:
+        raise RuntimeError("%s: out must be a preprocess.YuvFrames of ONE surface" % name)
+    H, W = out.height, out.width
+    _plate_state(name, "plate_y", plate_y, (H, W, 2))
+    _plate_state(name, "plate_c", plate_c, ((H + 1) // 2, (W + 1) // 2, 4))
+    if (not torch.is_tensor(fill_yuv) or fill_yuv.dtype not in (torch.uint16, torch.int16) or tuple(fill_yuv.shape) != (3,)
+            or not fill_yuv.is_contiguous()):
+        raise RuntimeError("%s: fill_yuv must be contiguous uint16 [3], (Y, U, V) in sample units (render.backdrop_yuv)" % name)
+    _plate_int(name, "reach", reach, 0, 32)
+    if H * W * 4 >= 2 ** 31 - 1:
+        raise RuntimeError("%s: H*W*4 must stay below 2^31 - 1, got %s" % (name, (H, W)))
+    dev = _plate_on(name, plate_y, ((plate_y, "plate_y"), (plate_c, "plate_c"), (fill_yuv, "fill_yuv"), (out.y, "out"), (out.uv, "out")))
+    with torch.cuda.device(dev):
+        check(lib.mdqe_plate_picture_yuv420sp(ptr(plate_y), ptr(plate_c), H, W, YUV_FORMATS.index(out.fmt), reach, ptr(fill_yuv),
+                                              ptr(out.y), _pitch_stride(out.y)[0], ptr(out.uv), _pitch_stride(out.uv)[0], cur_stream(dev)), name)
+    return out
+
+
 def _trail_args(name, pts, n, palette, F, f_off, p_off, trail, width, table_dtypes):
     """The checks render_trails and render_trails_yuv share.  -> the point table's row stride."""
     # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)

@@ -82,6 +82,8 @@ def backdrop_yuv(colour, fmt="nv12", matrix="bt709", full_range=False, order="rg
     if torch.is_tensor(c):
         raise ValueError("backdrop_yuv: colour must be three ints 0..255, got a tensor (a picture backdrop of a surface session is a "
                          "YuvFrames of one surface)")
+    if not isinstance(c, tuple):
+        raise ValueError("backdrop_yuv: colour must be three ints 0..255, got %r" % (colour,))
     pal = torch.zeros(256, 3, dtype=torch.uint8)
     pal[0] = torch.tensor(c, dtype=torch.uint8)
     return palette_yuv(pal, fmt, matrix, full_range, order)[0].contiguous()
@@ -231,6 +233,8 @@ def blur_taps(radius):
 def _backdrop(v, who):
     """A backdrop as the painters take it: a tuple of three ints 0..255, or a contiguous uint8 tensor [Ho, Wo, 3] (kept as handed in)."""
     from .preprocess import YuvFrames
+    if isinstance(v, str) and v == "plate":        # the learned background plate (merge.Plate): the video makes the picture
+        return v
     if isinstance(v, YuvFrames):
         if len(v) != 1:
             raise ValueError("%s: a backdrop surface must be a YuvFrames of ONE surface, got %d -- slice one, frames[i:i + 1]" % (who, len(v)))
@@ -294,7 +298,17 @@ class Style:
     under-covers are redacted too; with mosaic="background", blur="background" or the plain overlay every track grows, so the objects
     keep a sharp margin, or the tint becomes wider (`grows`).  Contours and tints are those of the grown map.  Every other output --
     the label maps, boxes, captions, trails, crops, polygons, mattes, masks -- stays that of the map as the model made it.  Not with
-    `replace`: there the matte owns the edge."""
+    `replace`: there the matte owns the edge.
+    Object removal: backdrop="plate", only with replace="tracks" -- the backdrop is the scene itself, a background plate the video
+    learns on the device from the pixels no track covers (merge.Plate, ops.plate_update / ops.plate_picture, csrc/plate.hip; the rule
+    is in include/mdqe_hip.h), so the replaced tracks are gone from the picture.  plate_frames: the memory N of the plate's running
+    mean in observations, an int in 1..256 (the first N observations of a pixel form their mean, later ones weigh 1 / N).  plate_margin:
+    an int in 0..32; a pixel teaches the plate only where no labelled pixel lies within this many output pixels (Euclidean), so an
+    object's fringe, which masks under-cover, stays out of it.  plate_reach: an int in 0..32; a pixel that has never been seen free
+    takes the nearest seen pixel within this distance, else plate_fill (three ints 0..255 in the frames' channel order).  plate_init:
+    None, or an empty-scene shot the plate starts from -- a uint8 tensor [Ho, Wo, 3] of the output's size, or in a surface=True
+    session a preprocess.YuvFrames of one surface of the session's kind -- the remedy for a fixed camera whose objects never move
+    away.  The state belongs to the video, never to the style: sessions may share a style."""
     alpha: float = 0.5
     contour: int = 1
     palette: torch.Tensor = None
@@ -315,8 +329,19 @@ class Style:
     matte_gain: float = 1.0
     grow: int = 0
     blur_edge: str = "bleed"
+    plate_frames: int = 64
+    plate_margin: int = 4
+    plate_reach: int = 16
+    plate_fill: tuple = (128, 128, 128)
+    plate_init: object = None
 
     def __post_init__(self):
+        for k, lo, hi, what in (("plate_frames", 1, 256, "the memory of the plate's running mean in observations"),
+                                ("plate_margin", 0, 32, "how far from any label a pixel must lie to teach the plate, in output pixels"),
+                                ("plate_reach", 0, 32, "how far a never-seen pixel looks for a seen one, in output pixels")):
+            v = getattr(self, k)
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError("overlay style: %s is %s, an int in %d..%d; got %r" % (k, what, lo, hi, v))
         if isinstance(self.grow, bool) or not isinstance(self.grow, int) or not 0 <= self.grow <= 32:
             raise ValueError("overlay style: grow must be an int in 0..32, got %r" % (self.grow,))
         if isinstance(self.trail, bool) or not isinstance(self.trail, int) or not 0 <= self.trail <= 64:
@@ -373,6 +398,27 @@ class Style:
             raise ValueError("overlay style: grow is the margin of a mosaic, a blur or the tint; with replace=%r the matte owns the edge "
                              "-- lower matte_gain for a softer, wider edge, or use blur= or mosaic= with grow=%d" % (self.replace, self.grow))
         self.backdrop = _backdrop(self.backdrop, "overlay style")
+        if self.plate and self.replace != "tracks":
+            raise ValueError("overlay style: backdrop='plate' is the scene behind the tracks, learned where no track is: it goes with "
+                             "replace='tracks' only -- set replace='tracks', or give a colour or a picture as the backdrop; got replace=%r"
+                             % (self.replace,))
+        try:
+            fill = tuple(self.plate_fill) if not isinstance(self.plate_fill, (str, bytes)) and not torch.is_tensor(self.plate_fill) else None
+        except TypeError:
+            fill = None
+        if fill is None or len(fill) != 3 or any(isinstance(c, bool) or not isinstance(c, int) or not 0 <= c <= 255 for c in fill):
+            raise ValueError("overlay style: plate_fill must be three ints 0..255 in the frames' channel order, got %r" % (self.plate_fill,))
+        self.plate_fill = fill
+        if self.plate_init is not None:
+            if not self.plate:
+                raise ValueError("overlay style: plate_init is what a background plate starts from -- add replace='tracks', "
+                                 "backdrop='plate', or hand the picture in as the backdrop itself; got backdrop=%r"
+                                 % (self.backdrop if not torch.is_tensor(self.backdrop) else "a picture",))
+            from .preprocess import YuvFrames
+            if not torch.is_tensor(self.plate_init) and not isinstance(self.plate_init, YuvFrames):
+                raise ValueError("overlay style: plate_init must be None, a uint8 tensor [Ho, Wo, 3] of the output's size or a "
+                                 "preprocess.YuvFrames of one surface, got %r" % (self.plate_init,))
+            self.plate_init = _backdrop(self.plate_init, "overlay style: plate_init")
         if self.classes is not None:
             try:
                 cls = tuple(self.classes) if not isinstance(self.classes, (str, bytes)) else None
@@ -399,6 +445,27 @@ class Style:
         """Whether a trail pass runs between the painter and the annotations (with the defaults: no, and exactly the painter's launches
         are made)."""
         return self.trail > 0
+
+    @property
+    def plate(self):
+        """Whether the backdrop is the learned background plate (merge.Plate); with any other backdrop nothing of it is made or launched."""
+        return isinstance(self.backdrop, str) and self.backdrop == "plate"
+
+    def plate_fill_on(self, device):
+        """plate_fill on `device`, uint8 [3] (cached per device)."""
+        return self._cached_on("_plate_fill_on", (str(device),), lambda: torch.tensor(self.plate_fill, dtype=torch.uint8))
+
+    def plate_fill_yuv_on(self, device, fmt, matrix, full_range, order):
+        """`backdrop_yuv(plate_fill, ...)` on `device`, uint16 [3] (cached per device and kind of surface)."""
+        return self._cached_on("_plate_fill_yuv_on", (str(device), fmt, matrix, bool(full_range), order),
+                               lambda: backdrop_yuv(self.plate_fill, fmt, matrix, bool(full_range), order))
+
+    def plate_init_on(self, device):
+        """plate_init on `device` (cached per device): a contiguous uint8 [Ho, Wo, 3] picture, or a YuvFrames of one surface."""
+        from .preprocess import YuvFrames
+        if isinstance(self.plate_init, YuvFrames):
+            return self._cached_on("_plate_init_on", (str(device),), lambda: self.plate_init, YuvFrames.to)
+        return self._cached_on("_plate_init_on", (str(device),), lambda: self.plate_init)
 
     def _cached_on(self, slot, key, make, to=lambda t, device: t.contiguous().to(device)):
         """What `make()` gives on the host, on the device key[0]: made and moved there once per `key` -- one tiny upload per session, not
