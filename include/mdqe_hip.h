@@ -553,6 +553,28 @@ int mdqe_final_masks_overlap(const float* logits, int n_sel, const int* inst_idx
                              const uint32_t* gt_bits, int G, int f_off,
                              unsigned long long* inter, long inter_row_stride, int* area, void* stream);
 
+/* The same sweep with the masks counted against EACH OTHER: how much of each track is hidden, and by whom -- the relation between the
+ * tracks of a window, which neither the planes nor the label map says on its own.  logits .. Wo are the label map's.  At window frame f
+ * and output pixel (Y, X), with b_k the final-mask bit of selected row k (the expression of the entry points above: one definition) and
+ *   o = the owner: the smallest k among the rows with b_k set whose up-sampled logit equals the largest among them, none if no bit is
+ *       set -- exactly the choice mdqe_final_label_map_u8 makes (the same device expression), so inst_idx_dev[o] + 1 is its label,
+ *   occ[(k * Fw + f) * n_sel + j] = #{(Y, X) : b_k set and o == j}                  int32 [n_sel, Fw, n_sel].
+ * So occ[k, f, k] is the area of k's VISIBLE region (column 0 of the label map's geometry table), the sum of occ[k, f, :] the area of
+ * k's dense mask (column 0 of mdqe_final_masks_u8_geom's table), and for j != k occ[k, f, j] is the part of k's mask that track j
+ * hides.  A row listed twice in inst_idx_dev follows from the rule: the earlier position owns.  Only selected rows can be owners.
+ * occ is fully OVERWRITTEN on every call (the entry clears it itself).  Integer counters only (ballots, popcounts, integer LDS and
+ * global atomics): exact, identical from run to run.  n_sel <= 255, (long)Ho*Wo < 2^31, Hm*Wm < 2^31 and (long)n_sel*n_sel*Fw < 2^31
+ * are checked before any pointer is looked at (MDQE_EINVAL); n_sel == 0 or Fw == 0 returns OK and launches nothing.  Any n_sel <= 255:
+ * the k axis goes in chunks of at most 16384 / n_sel - 1 rows per block (one chunk up to 127 rows, five at 255; at most 64 KB of LDS),
+ * every chunk finding the owner over all rows.  Never allocates, never synchronises. */
+int mdqe_final_masks_occlusion(const float* logits, int n_sel, const int* inst_idx_dev, int Fw, int Hm, int Wm, int factor,
+                               int h, int w, int Ho, int Wo, int* occ, void* stream);
+/* That entry's launch plan for 1 <= n_sel <= 255 (else MDQE_EINVAL), on the host, nothing launched: *chunk rows of the k axis a block,
+ * *chunks of them (blockIdx.y), *lds_bytes of dynamic LDS a block asks for (ids[n_sel] | tab[chunk, n_sel]) and, where slots is not NULL
+ * (int [*chunks * n_sel], at most 5 * 255), slots[b * n_sel + k] = the row of block-chunk b's table that selected row k counts into, or
+ * -1 for a row of another chunk -- the kernel's own mapping (one definition), so every row >= 0 there lies below that chunk's rows. */
+int mdqe_final_masks_occlusion_plan(int n_sel, int* chunk, int* chunks, long* lds_bytes, int* slots);
+
 /* The picture a viewer paints from that map: out[f_off + f, Y, X, c] (uint8, pixel-interleaved, [>= f_off + F, Ho, Wo, 3]) from labels
  * (uint8 [F, Ho, Wo], what mdqe_final_label_map_u8 writes), the frames the caller handed in (frames: [F, 3, h0, w0] planar, uint8 if
  * is_u8 else float32, consecutive frames frame_stride ELEMENTS apart -- a view into a larger store works -- or NULL) and palette (uint8

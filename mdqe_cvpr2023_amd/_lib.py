@@ -77,6 +77,8 @@ SIGNATURES = {
     "mdqe_render_trails_u8": [p, i, i, i, i, p, l, i, i, i, i, p, p],
     "mdqe_render_trails_yuv420sp": [p, l, l, p, l, l, i, i, i, i, i, p, l, i, i, i, i, p, p],
     "mdqe_final_masks_overlap": [p, i, p, i, i, i, i, i, i, i, i, p, i, i, p, l, p, p],
+    "mdqe_final_masks_occlusion": [p, i, p, i, i, i, i, i, i, i, i, p, p],
+    "mdqe_final_masks_occlusion_plan": [i, p, p, p, p],
     "mdqe_set_gemm_precision": [i],
     "mdqe_set_gemm_precision_thread": [i],
     "mdqe_layernorm_post_f32": [p, p, p, p, p, l, i, f, p],

@@ -1,7 +1,7 @@
 // One output pixel of the final mask (mdqe/mdqe.py:357-358 + 458-462; the formula is stated above the entry points in final_mask.hip),
-// shared by every form built on it -- dense, RLE, geometry, label map (final_mask.hip) and the overlap counts (score_ops.hip): identical
-// arithmetic, identical bits.  Three steps: where the pixel reads (the same for every map of a window), the up-sampled logit there, and
-// the threshold on it.
+// shared by every form built on it -- dense, RLE, geometry, label map (final_mask.hip), the overlap counts (score_ops.hip) and the
+// occlusion table (occlusion.hip): identical arithmetic, identical bits.  Three steps: where the pixel reads (the same for every map
+// of a window), the up-sampled logit there, and the threshold on it.
 #pragma once
 #include "common.h"
 
@@ -35,6 +35,13 @@ __device__ __forceinline__ int final_mask_bit(float v) {
 __device__ __forceinline__ int final_mask_pixel(const float* __restrict__ m, int Hm, int Wm, int factor, int h, int w, float sy_scale,
                                                 float sx_scale, int Y, int X) {
   return final_mask_bit(final_mask_value(m, Hm, Wm, factor, h, w, sy_scale, sx_scale, Y, X));
+}
+
+// The owner of a pixel, one row at a time in the order of the selected rows: row k (bit: its final-mask bit, v: its up-sampled logit)
+// takes the pixel from `best` (-1: nobody yet; best_v: its logit) iff its bit is set and it is the first such row or v is strictly
+// larger.  So the owner is the first row with the largest logit among the set ones: the label map's choice and the occlusion table's.
+__device__ __forceinline__ bool final_owner_takes(int bit, float v, int best, float best_v) {
+  return bit && (best < 0 || v > best_v);
 }
 
 // The matte's level 0..255 from x = gain * (the largest up-sampled logit of the participating rows) and U = the OR of their final-mask

@@ -357,12 +357,12 @@ final_label_map_kernel(const float* __restrict__ lg, int n_sel, int Fw, int Hm, 
       const int slot = src_cap * Wm;
       for (int k = 0; k < n_sel; ++k) {
         const float v = final_mask_value_at(rows_lds + k * slot, Wm, t);
-        if (final_mask_bit(v) && (best < 0 || v > best_v)) { best = k; best_v = v; }
+        if (final_owner_takes(final_mask_bit(v), v, best, best_v)) { best = k; best_v = v; }
       }
     } else {
       for (int k = 0; k < n_sel; ++k) {
         const float v = final_mask_value_at(lg + ((long)ids[k] * Fw + f) * map_stride, Wm, t);
-        if (final_mask_bit(v) && (best < 0 || v > best_v)) { best = k; best_v = v; }
+        if (final_owner_takes(final_mask_bit(v), v, best, best_v)) { best = k; best_v = v; }
       }
     }
     o[i] = best < 0 ? (unsigned char)0 : (unsigned char)(ids[best] + 1);

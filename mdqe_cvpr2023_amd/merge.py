@@ -10,6 +10,8 @@ visible region, traced on the device and brought to the host per window: `polygo
 `build_window`; the three paths differ in the destination only: per window into per-video pinned memory (`_early_masks`), per window
 as a record (`_online_window`), or all windows into whole-video device buffers with one copy at the end (`video_result`).  Shared
 beside it: `to_host` (the hop on the copy stream), `rle.positions_to_rles`, `stitch`, `result_head` / `track_geometry` (a result's keys).
+The occlusion table (`occlusion_counts`, `occlusion_result`: per window how much of each track's mask every track owns) is a form of its
+own that needs none of the others.
 `OverlapTables` is not an output form but a score: with a ground truth handed in (vis_score.GroundTruth), every flushed window's final
 masks are counted against it where they are decided (ops.final_masks_overlap) -- "pred_gt", beside whatever form the masks take."""
 import contextlib
@@ -35,15 +37,16 @@ class Forms:
     crops: bool = False                   # per-track chips cut from the frames (render.Crops; the map and its table: a device scratch if not returned)
     paths: bool = False                   # per-track centroids and moments of the map's visible regions (PathTable; the map: a device scratch if not returned)
     polygons: bool = False                # per-track outline polygons of the map's visible regions (polygons.Polygons; the map: a device scratch if not returned)
+    occlusion: bool = False               # the occlusion table of the window's tracks, int32 [n, F, n] (ops.final_occlusion), beside any other form
     matte: bool = False                   # the soft matte of the window's tracks, one uint8 plane per frame (render.Matte), beside any other form
 
     @classmethod
     def _of(cls, model, geometry, planes, labels, overlay, early_always=False, surface=False, crops=False, paths=False, matte=False,
-            polygons=False):
+            polygons=False, occlusion=False):
         """geometry None: the model's flag.  It describes the planes where there are planes, and the labels' regions where the map is returned."""
         g = bool(getattr(model, "geometry_output", False) if geometry is None else geometry)
         return cls(planes, labels, overlay, g and planes is not None, g and labels, early_always, bool(overlay and surface), bool(crops),
-                   bool(paths), matte=bool(matte), polygons=bool(polygons))
+                   bool(paths), matte=bool(matte), polygons=bool(polygons), occlusion=bool(occlusion))
 
     @classmethod
     def of_model(cls, model, emit_masks=True, geometry=None):
@@ -54,15 +57,17 @@ class Forms:
         pic = getattr(model, "overlay_output", False)
         return cls._of(model, geometry, None if lab == "only" else "rle" if rle else "dense", bool(lab), bool(pic), rle, pic == "surface",
                        getattr(model, "crop_output", None) is not None, bool(getattr(model, "path_output", False)),
-                       getattr(model, "matte_output", None) is not None, getattr(model, "polygon_output", None) is not None)
+                       getattr(model, "matte_output", None) is not None, getattr(model, "polygon_output", None) is not None,
+                       occlusion=bool(getattr(model, "occlusion_output", False)))
 
     @classmethod
-    def of_emit(cls, emit, geometry=False, model=None, surface=False, crops=False, paths=False, matte=False, polygons=False):
+    def of_emit(cls, emit, geometry=False, model=None, surface=False, crops=False, paths=False, matte=False, polygons=False,
+                occlusion=False):
         """Online ("masks" | "rle" | "labels" | "overlay"; surface: the overlay onto the surfaces pushed; crops: chips beside it; paths:
-        centroids and moments beside it; polygons: outline polygons beside it)."""
+        centroids and moments beside it; polygons: outline polygons beside it; occlusion: the occlusion table beside it)."""
         lab = emit in ("labels", "overlay")
         return cls._of(model, geometry, None if lab else {"masks": "dense", "rle": "rle"}[emit], lab, emit == "overlay", surface=surface,
-                       crops=crops, paths=paths, matte=matte, polygons=polygons)
+                       crops=crops, paths=paths, matte=matte, polygons=polygons, occlusion=occlusion)
 
 
 def dense_masks(m, idx, stride, frame_hw, out_size, geometry, out, f_off):
@@ -677,8 +682,40 @@ def matte_planes(m, stride, frame_hw, out_size, spec, cls, out, f_off):
     ops.final_matte(m, idx, stride, fh, fw, Ho, Wo, out, f_off, None if take is None else take.to(m.device), spec.gain)
 
 
+def occlusion_counts(m, stride, frame_hw, out_size, out=None):
+    """The occlusion table of window logits m [n, F, Hm, Wm] on the device: int32 [n, F, n] over ALL n rows (idx = arange(n), as
+    `label_maps` does, so column j is the track whose label is j + 1 and every path agrees bit for bit): occ[k, f, j] = the pixels of
+    k's final mask that j owns (ops.final_occlusion: one more sweep of the logits; no label map is made or needed).  n = 0: an empty
+    table, nothing launched.  out: the buffer to write into."""
+    from . import ops
+    (fh, fw), (Ho, Wo) = frame_hw, out_size
+    idx = torch.arange(int(m.shape[0]), dtype=torch.int32, device=m.device)
+    return ops.final_occlusion(m, idx, stride, fh, fw, Ho, Wo, out)
+
+
+def occlusion_result(rows, n_frames, windows):
+    """{"pred_occlusion": int32 [n_out, L, n_out + 1]} of a whole video from its windows' tables, on the host (`windows`: (f_off, frames,
+    rows the window holds, table [n, F, n]) in video order): row a is tracker row rows[a], column b < n_out the pixels of a's mask that
+    tracker row rows[b] owns (0 where the window does not hold that row), the last column those owned by tracks that are not among
+    `rows`.  The frames before a row's first window are zero (`stitch`'s rule)."""
+    rows, L = [int(r) for r in rows], int(n_frames)
+    width = len(rows) + 1
+    wins = []
+    for f_off, nf, n, table in windows:
+        t = torch.as_tensor(table).to(torch.int64).reshape(int(n), int(nf), int(n))
+        piece = torch.zeros((int(n), int(nf), width), dtype=torch.int64)
+        for b, r in enumerate(rows):
+            if r < n:
+                piece[:, :, b] = t[:, :, r]
+        inside = sorted({r for r in rows if r < n})
+        piece[:, :, -1] = t.sum(-1) - t[:, :, inside].sum(-1)
+        wins.append((f_off, nf, n, piece.to(torch.int32)))
+    parts = stitch(rows, L, wins, lambda k: torch.zeros((k, width), dtype=torch.int32), torch.cat)
+    return {"pred_occlusion": torch.stack(parts) if parts else torch.zeros((0, L, 1), dtype=torch.int32)}
+
+
 def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels=None, picture=None, paint=None,
-                 hop=lambda stage, geom: geom, crops=None, paths=None, matte=None, polygons=None, plate=None):
+                 hop=lambda stage, geom: geom, crops=None, paths=None, matte=None, polygons=None, plate=None, occlusion=None):
     """What `forms` asks for of ONE flushed window (logits m [n, F, Hm, Wm]), on the current stream, for every path; the only caller
     of `overlay_frames`, `label_maps`, `dense_masks` and `rle_positions`.  First the label map of ALL n rows into labels = (device
     buffer, frame offset) and, with picture = (buffer, offset), its overlay, painted from paint = (FrameStore, first video frame,
@@ -694,6 +731,8 @@ def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels
     the map's visible regions (`polygon_rings`: they come to the host there), stage "polygons"; the map is then made whether or not it is
     returned.
     plate (a Plate): the video's background plate, which an overlay in a style with backdrop="plate" teaches and composites.
+    occlusion (int32 device buffer [n, F, n]): the window's occlusion table over ALL n rows (`occlusion_counts`), stage "occlusion",
+    behind "matte"; it needs no label map.
     -> (labels' geometry table [n, F, 5] or None, planes' table [len(rows), F, 5] or None, (pos, n_pos) of `rle_positions` or None,
     the window's TrackPolygons or None)."""
     lgeom = pgeom = runs = poly = None
@@ -719,6 +758,9 @@ def build_window(m, forms, rows, stride, frame_hw, out_size, planes=None, labels
     if matte is not None:
         matte_planes(m, stride, frame_hw, out_size, *matte)
         hop("matte", None)
+    if occlusion is not None:
+        occlusion_counts(m, stride, frame_hw, out_size, occlusion)
+        hop("occlusion", None)
     if rows is not None and int(rows.numel()):
         if planes is not None:
             pgeom = hop("planes", dense_masks(m, rows, stride, frame_hw, out_size, forms.plane_geometry, *planes))
@@ -812,6 +854,7 @@ class EarlyMasks:
     overlay: object = None                                            # overlay: ONE pinned uint8 [L, Ho, Wo, 3] per video (model.overlay_output)
     matte: object = None                                              # matte: ONE pinned uint8 [L, Ho, Wo] per video (model.matte_output)
     polygons: list = dataclasses.field(default_factory=list)          # per window, its TrackPolygons (k = tracker row; model.polygon_output)
+    occlusion: list = dataclasses.field(default_factory=list)         # per window (f_off, frames, tracks, int32 [tracks, frames, tracks] pinned host; model.occlusion_output)
 
 
 def result_head(model, cls_clips, out_size, n_frames, score=None, track_ids=True):
@@ -858,11 +901,11 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
         elif forms.planes:
             planes_res = {"pred_masks": [early.hosts[i].view(torch.bool)[:n_frames] for i in inst]}
         host = {"labels": early.labels, "overlay": early.overlay, "matte": early.matte}
-        polys = early.polygons
+        polys, occs = early.polygons, early.occlusion
     else:
         sel = sorted(set(inst))
         rows = [sel.index(i) for i in inst]                        # rows of the planes' buffer = positions in sel
-        plane_geoms, label_geoms, polys, u8 = [], [], [], dict(dtype=torch.uint8, device=model.device)
+        plane_geoms, label_geoms, polys, occs, u8 = [], [], [], [], dict(dtype=torch.uint8, device=model.device)
         # (the windows tile [0, n_frames): every row of the map and the picture is written; a track's planes start at its first window)
         d_lab = torch.empty(n_frames, Ho, Wo, **u8) if forms.labels or forms.overlay or forms.crops or forms.paths or forms.polygons else None
         if forms.crops:
@@ -881,12 +924,16 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
             at = [None if t is None else (t, f_off) for t in (d_planes, d_lab, d_pic)]
             if paths is not None:
                 paths.begin(n, nf)
+            occ = torch.empty((n, nf, n), dtype=torch.int32, device=model.device) if forms.occlusion else None
             lg, pg, _, poly = build_window(m, forms, sel_dev[:cnt] if forms.planes else None, model.cfg.match_stride, frame_hw, out_size, *at,
                                      paint=(frame_source, f_off, model.overlay_style, cls_clips[i]) if forms.overlay else None,
                                      crops=(crops.spec, frame_source, f_off, *crops.rows(n), crops.spec.count(f_off)) if forms.crops else None,
                                      paths=paths, matte=(model.matte_output, cls_clips[i], d_mat, f_off) if forms.matte else None,
                                      **({"plate": plate} if plate is not None else {}),
-                                     **({"polygons": (model.polygon_output, cls_clips[i], f_off)} if forms.polygons else {}))
+                                     **({"polygons": (model.polygon_output, cls_clips[i], f_off)} if forms.polygons else {}),
+                                     **({"occlusion": occ} if occ is not None else {}))
+            if occ is not None:
+                occs.append((f_off, nf, n, occ))
             if forms.polygons:
                 polys.append(poly)
             if paths is not None:
@@ -907,6 +954,7 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
         # (the tables' copies follow the buffers' sync)
         plane_geoms, label_geoms = ([(f, nf, n, g.cpu() if on else g) for f, nf, n, g in gs]
                                     for on, gs in ((forms.plane_geometry, plane_geoms), (forms.label_geometry, label_geoms)))
+        occs = [(f, nf, n, t.cpu()) for f, nf, n, t in occs]
         if forms.planes:
             planes = host["planes"].view(torch.bool)
             if forms.planes == "rle":                              # no early path (unknown length): encode on the host
@@ -914,10 +962,12 @@ def video_result(model, image_size, cls_clips, windows, frame_hw, n_frames, earl
                 planes_res = {"pred_rles": [enc[p] for p in rows]}
             else:
                 planes_res = {"pred_masks": [planes[p] for p in rows]}
-    if forms.labels or forms.overlay or forms.crops or forms.paths or forms.matte or forms.polygons:
+    if forms.labels or forms.overlay or forms.crops or forms.paths or forms.matte or forms.polygons or forms.occlusion:
         res.setdefault("pred_track_ids", list(inst))
     if forms.matte:
         res["pred_matte"] = host["matte"][:n_frames]
+    if forms.occlusion:
+        res.update(occlusion_result(inst, n_frames, occs))
     if forms.crops:
         res.update(crops.result(inst))
     if forms.paths:
@@ -945,7 +995,8 @@ class ClipMerger:
     EARLY_TRACKS = 48                       # tracks per video the early-mask path budgets pinned memory for
 
     def __init__(self, model, frame_hw, out_size, mask_hw, n_frames=None, emit_masks=True, online=None, geometry=None, frame_source=None,
-                 style=None, ground_truth=None, surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None, polygons=None):
+                 style=None, ground_truth=None, surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None, polygons=None,
+                 occlusion=False):
         self.model, self.frame_hw, self.out_size, self.mask_hw = model, frame_hw, out_size, mask_hw
         self.emit_masks = emit_masks                # False: scores / labels only (ranks > 0 of a sharded video)
         # online ("masks" | "rle" | "labels" | "overlay"; online.OnlineVideo, CUDA only): at each flush the window's final masks -- or their
@@ -962,7 +1013,7 @@ class ClipMerger:
         # polygons (polygons.Polygons): an online session's; offline the model's polygon_output
         self.polygon_spec = polygons if online else (getattr(model, "polygon_output", None) if emit_masks else None)
         self.forms = forms = (Forms.of_emit(online, geometry, model, surface, self.crop_spec is not None, bool(paths), matte is not None,
-                                            self.polygon_spec is not None) if online
+                                            self.polygon_spec is not None, occlusion=bool(occlusion)) if online
                               else Forms.of_model(model, emit_masks, geometry))
         self.crop_table = None                      # the early path's CropTable, from its first window
         self.path_table = None                      # the early and the online path's PathTable, from their first window
@@ -1101,7 +1152,11 @@ class ClipMerger:
         mat = torch.empty(nf, Ho, Wo, **u8) if forms.matte else None
         copies = {"labels": (pairs("labels", lab) if forms.labels else []) + (pairs("overlay", pic) if forms.overlay else []),
                   "planes": pairs("planes", planes) if planes is not None else [], "crops": [], "paths": [], "polygons": [],
-                  "matte": pairs("matte", mat) if mat is not None else []}
+                  "matte": pairs("matte", mat) if mat is not None else [], "occlusion": []}
+        occ = None
+        if forms.occlusion:                         # the window's table [n, F, n], sent to the host (offline: selected and stitched at the end)
+            occ = torch.empty((n, nf, n), dtype=torch.int32, device=self.dev)
+            copies["occlusion"] = pairs("occlusion", occ)
         crop = None
         if forms.crops:
             spec = self.crop_spec
@@ -1118,7 +1173,7 @@ class ClipMerger:
         # (the copy stream is created BEFORE the window's kernels are launched, and only by a window that copies, as ever: the order
         # streams are first used in decides their queues)
         sends_paths = bool(forms.paths and self.online and n)        # (offline the windows' tables wait on the device: PathTable.keep)
-        cs = copy_stream(self.model) if copies["labels"] or copies["planes"] or copies["crops"] or copies["matte"] or sends_paths else None
+        cs = copy_stream(self.model) if copies["labels"] or copies["planes"] or copies["crops"] or copies["matte"] or copies["occlusion"] or sends_paths else None
         if self.path_table is None:
             self.path_table = path_table(forms, self.style, self.dev, keep=forms.paths and not self.online)
         if self.plate is None:
@@ -1133,6 +1188,7 @@ class ClipMerger:
                            matte=(self.matte_spec, c, mat, 0) if mat is not None else None,
                            **({"plate": self.plate} if self.plate is not None else {}),
                            **({"polygons": (self.polygon_spec, c, self.f_off)} if forms.polygons else {}),
+                           **({"occlusion": occ} if occ is not None else {}),
                            hop=lambda stage, geom: (to_host(cs, self.side, copies[stage], geom, event())
                                                     if copies[stage] or geom is not None else None))   # (a scratch stage: nothing to send)
         if self.path_table is not None:
@@ -1153,6 +1209,9 @@ class ClipMerger:
         early = self.early
 
         def pairs(kind, buf):
+            if kind == "occlusion":                 # the window's own table: its shape changes with the tracks
+                early.occlusion.append((f0, nf, n, torch.empty(tuple(buf.shape), dtype=buf.dtype, pin_memory=bool(buf.numel()))))
+                return [(early.occlusion[-1][3], buf)] if buf.numel() else []
             if kind == "planes":
                 while len(early.hosts) < n:         # a new track: its own pinned buffer, zero before its first window (:442)
                     early.hosts.append(model.pinned_mask_buffer(shape))
@@ -1190,7 +1249,7 @@ class ClipMerger:
             if not torch.is_tensor(buf):            # a surface picture: pinned surfaces of the same pitch, both planes
                 host = rec["overlay"] = surface_picture(self.frame_source, nf, out_size, "cpu", self.surface_pitch_align, pin_memory=True)
                 return [(host.y, buf.y), (host.uv, buf.uv)]
-            if kind in ("crops", "crop_rects", "centroids", "moments"):     # (their shape changes with the tracks: not the mask pool's kind of buffer)
+            if kind in ("crops", "crop_rects", "centroids", "moments", "occlusion"):     # (their shape changes with the tracks: not the mask pool's kind of buffer)
                 rec[kind] = torch.empty(tuple(buf.shape), dtype=buf.dtype, pin_memory=bool(buf.numel()))
                 return [(rec[kind], buf)] if buf.numel() else []
             host = self.model.pinned_mask_buffer(tuple(buf.shape))

@@ -334,6 +334,9 @@ class MDQE(nn.Module):
         # A polygons.Polygons: forward() on a video adds "pred_polygons", the outlines of each output's visible regions as rings of
         # lattice corners, traced on the device from the label map (ops.label_polygons).  None: nothing changes.  (A property: see below.)
         self.polygon_output = None
+        # True: forward() on a video adds "pred_occlusion" (int32 [n_out, L, n_out + 1]: how much of each output's mask every output owns,
+        # counted on the device by ops.final_occlusion).  False: nothing changes.  (A property: see below.)
+        self.occlusion_output = False
         self.merge_on_cpu = None                 # None: cfg.merge_on_cpu (MODEL.MDQE.MERGE_ON_CPU); True / False override it
         # Final masks of a tracker window leave the device when the window is flushed (pinned host buffers, copied under the later
         # windows' compute) instead of in one pass + one 100-MB copy after the last window.  Independent of MERGE_ON_CPU, which in the
@@ -580,6 +583,25 @@ class MDQE(nn.Module):
         self.__dict__["_polygon_output"] = value
 
     @property
+    def occlusion_output(self):
+        """False or True: forward() on a video adds "pred_occlusion" (int32 [n_out, L, n_out + 1], host: entry [a, f, b] with b < n_out is
+        the number of pixels of output a's final mask in frame f that output b's track owns -- b == a: a's visible region, b != a: the
+        part of a that b hides -- and the last column the pixels owned by tracks that are not among the outputs, so a row sums to the
+        area of a's mask; the owner is the label map's, ops.final_occlusion; zero in the frames before the track's first window) and
+        "pred_track_ids", the order of its rows and columns.  Beside every other output form, on either mask path; no label map is made
+        for it and the bits of the other outputs are left alone.  Helpers on the table: occlusion.py.  Videos only, one device
+        (sharding.py refuses it)."""
+        return self.__dict__.get("_occlusion_output", False)
+
+    @occlusion_output.setter
+    def occlusion_output(self, value):
+        if not isinstance(value, bool):
+            raise ValueError("occlusion_output must be False or True, got %r" % (value,))
+        if value:
+            self.check_occlusion_capacity()
+        self.__dict__["_occlusion_output"] = value
+
+    @property
     def overlay_style(self):
         if "_overlay_style" not in self.__dict__:
             from .render import Style
@@ -598,6 +620,12 @@ class MDQE(nn.Module):
         if int(self.cfg.n_max_inst) > 255:
             raise ValueError("label maps are uint8 (label = track + 1): n_max_inst (MODEL.MDQE.MAX_NUM_INSTANCES) = %d exceeds 255"
                              % int(self.cfg.n_max_inst))
+
+    def check_occlusion_capacity(self):
+        """The occlusion sweep keeps a pixel's owner among at most 255 rows, as the label map does."""
+        if int(self.cfg.n_max_inst) > 255:
+            raise ValueError("the occlusion table takes at most 255 tracker rows: n_max_inst (MODEL.MDQE.MAX_NUM_INSTANCES) = %d exceeds "
+                             "255; lower it to 255 or less" % int(self.cfg.n_max_inst))
 
     PIN_POOL_GB = float(os.environ.get("MDQE_PIN_POOL_GB", "8"))       # pinned host memory the model keeps for mask read-back between calls
 
@@ -1025,7 +1053,7 @@ class MDQE(nn.Module):
             yield guarded(step)
 
     def online_video(self, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None,
-                     surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None, polygons=None):
+                     surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None, polygons=None, occlusion=False):
         """An online session over ONE video whose frames arrive in pushes (a camera, a stream, a video too long to hold): push()
         returns each tracker window as soon as it is final, close() the rest, result() the video-level scores / labels / tracks.
         height / width: output mask size (default: the frame size); emit: "masks" (bool [n, F, H, W] per window), "rle" or "labels" (one
@@ -1042,11 +1070,12 @@ class MDQE(nn.Module):
         "pred_moments" (`path_output`'s); matte (render.Matte, beside any emit): every window carries `matte`, uint8 [F, H, W], the soft
         matte of its tracks, and with keep result() "pred_matte" (`matte_output`'s); polygons (polygons.Polygons, beside any emit): every
         window carries `polygons`, a polygons.TrackPolygons of its tracks' outlines, and with keep result() "pred_polygons"
-        (`polygon_output`'s).  See online.py."""
+        (`polygon_output`'s); occlusion (a bool, beside any emit): every window carries `occlusion`, int32 [n, F, n], the pixels of each
+        track's mask that every track owns, and with keep result() "pred_occlusion" (`occlusion_output`'s).  See online.py."""
         from .online import OnlineVideo
         return OnlineVideo(self, height=height, width=width, emit=emit, keep=keep, geometry=geometry, style=style, ground_truth=ground_truth,
                            surface=surface, surface_pitch_align=surface_pitch_align, crops=crops, paths=paths, matte=matte,
-                           polygons=polygons)
+                           polygons=polygons, occlusion=occlusion)
 
     def inference_image(self, batched_inputs):
         """COCO single-image branch: MDQE.forward :213-236 -> mdqe.forward (models/mdqe.py:62-70) -> decoder
@@ -1075,6 +1104,9 @@ class MDQE(nn.Module):
         if getattr(self, "polygon_output", None) is not None:
             raise ValueError("polygon_output: the COCO image branch has no polygons (track outlines are a video output: use a video config, "
                              "or set polygon_output = None)")
+        if getattr(self, "occlusion_output", False):
+            raise ValueError("occlusion_output: the COCO image branch has no occlusion table (the relation between tracks is a video "
+                             "output: use a video config, or set occlusion_output = False)")
         from .preprocess import YuvFrames
         if isinstance(item["image"], YuvFrames):
             raise ValueError("YuvFrames: the COCO image branch takes RGB tensors (decoder surfaces are a video input; convert one with "

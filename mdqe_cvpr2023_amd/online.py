@@ -72,6 +72,11 @@ polygons=Polygons(...) (polygons.py), beside ANY emit: every window also carries
 of its tracks' visible regions of the label map -- rings of lattice corners, traced on the device (ops.label_polygons; the map is then
 made for every emit), a few KB per window; f counts video frames, k is the window's row.  keep=True adds "pred_polygons" to result(),
 equal to forward()'s with model.polygon_output.
+occlusion=True, beside ANY emit (surface=True sessions included): every window also carries `win.occlusion`, int32 [n, F, n] on pinned
+host -- occlusion[k, f, j] = the pixels of track k's final mask in frame f that track j owns (j == k: k's visible region; j != k: the
+part of k that j hides; the row's sum: the area of k's mask), rows and columns being the window's tracker rows -- counted on the device
+in one more sweep of the window's logits (ops.final_occlusion); no label map is made for it, so emit="rle" stays without one.  keep=True
+adds "pred_occlusion" int32 [n_out, L, n_out + 1] to result(), equal to forward()'s with model.occlusion_output; helpers: occlusion.py.
 """
 import contextlib
 import dataclasses
@@ -166,7 +171,8 @@ class Window:
     f1-f0, 3], its (pixels, sum of X, sum of Y) (pseudo-fields of the same kind).  In a session with matte=: `matte` uint8 [f1-f0, H, W]
     on pinned host, the soft matte of the window's tracks (render.Matte; a pseudo-field of the same kind).  In a session with
     polygons=: `polygons`, a polygons.TrackPolygons of the outlines of the window's tracks, f in video frames, k the window's row (a
-    pseudo-field of the same kind)."""
+    pseudo-field of the same kind).  In a session with occlusion=True: `occlusion` int32 [n, f1-f0, n] on pinned host, [k, f, j] = the
+    pixels of track k's mask that track j owns (a pseudo-field of the same kind)."""
     frames: tuple
     track_ids: list
     cls_probs: torch.Tensor
@@ -183,9 +189,11 @@ class Window:
     moments: dataclasses.InitVar[torch.Tensor] = None
     matte: dataclasses.InitVar[torch.Tensor] = None
     polygons: dataclasses.InitVar[object] = None
+    occlusion: dataclasses.InitVar[torch.Tensor] = None
 
-    def __post_init__(self, labels, overlay, crops, crop_rects, crop_frames, centroids, moments, matte, polygons=None):
+    def __post_init__(self, labels, overlay, crops, crop_rects, crop_frames, centroids, moments, matte, polygons=None, occlusion=None):
         self.matte = matte
+        self.occlusion = occlusion
         self.polygons = polygons
         self.labels = labels
         self.overlay = overlay
@@ -195,7 +203,7 @@ class Window:
 
 class OnlineVideo:
     def __init__(self, model, height=None, width=None, emit="masks", keep=False, geometry=False, style=None, ground_truth=None,
-                 surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None, polygons=None):
+                 surface=False, surface_pitch_align=1, crops=None, paths=False, matte=None, polygons=None, occlusion=False):
         if emit not in ("masks", "rle", "labels", "overlay"):
             raise ValueError("online_video: emit must be 'masks', 'rle', 'labels' or 'overlay'")
         if not isinstance(surface, bool):
@@ -234,6 +242,13 @@ class OnlineVideo:
             if model.cfg.is_coco:
                 raise ValueError("online_video: polygons with a COCO image config: track outlines are a video output (use a video config)")
         self.polygons = polygons
+        if not isinstance(occlusion, bool):
+            raise ValueError("online_video: occlusion must be a bool, got %r" % (occlusion,))
+        if occlusion and model.cfg.is_coco:
+            raise ValueError("online_video: occlusion with a COCO image config: the occlusion table is a video output (use a video config)")
+        if occlusion:
+            model.check_occlusion_capacity()
+        self.occlusion = occlusion
         if emit in ("labels", "overlay") or crops is not None or paths or matte is not None or polygons is not None:
             model.check_label_capacity()
         from .render import Style
@@ -302,7 +317,7 @@ class OnlineVideo:
         self.merger = ClipMerger(model, self.hw, self.out_size, self.mask_hw, n_frames=None, online=self.emit,
                                  geometry=self.geometry, frame_source=self.store, style=self.style, ground_truth=self.ground_truth,
                                  surface=self.surface, surface_pitch_align=self.surface_pitch_align, crops=self.crops, paths=self.paths,
-                                 matte=self.matte, polygons=self.polygons)
+                                 matte=self.matte, polygons=self.polygons, **({"occlusion": True} if self.occlusion else {}))
         shapes = model.engine.cache_shapes(self.geo)
         per_frame = 4 * sum(int(np.prod(sh)) for sh in shapes.values())
         budget = cache_budget_frames(per_frame, model.CACHE_GB)
@@ -335,7 +350,7 @@ class OnlineVideo:
                               masks=r.get("masks"), rles=r.get("rles"), boxes=boxes, areas=areas, labels=r.get("labels"),
                               overlay=r.get("overlay"), crops=r.get("crops"), crop_rects=r.get("crop_rects"),
                               crop_frames=r.get("crop_frames"), centroids=r.get("centroids"), moments=r.get("moments"),
-                              matte=r.get("matte"), polygons=r.get("polygons")))
+                              matte=r.get("matte"), polygons=r.get("polygons"), occlusion=r.get("occlusion")))
         del self.merger.emitted[:]
         if self.store is not None:
             # the chunks that lie wholly before the first frame no window has emitted are done with; what stays and may be the caller's
@@ -455,5 +470,8 @@ class OnlineVideo:
                                                                for w in self.kept]))
         if self.keep and forms.polygons:          # (the windows' rings in a row, their rows renumbered to the outputs)
             res.update(merge.polygon_result(inst, self.out_size, [w.polygons for w in self.kept]))
+        if self.keep and forms.occlusion:         # (per output the track's rows of the windows' tables; zero before its first window)
+            res.update(merge.occlusion_result(inst, self.received, [(w.frames[0], w.frames[1] - w.frames[0], len(w.track_ids), w.occlusion)
+                                                                    for w in self.kept]))
         self._result = res
         return res

@@ -691,6 +691,32 @@ def final_masks_overlap(logits, inst_idx, factor, h, w, Ho, Wo, gt_bits, G, f_of
     return inter, area
 
 
+def final_occlusion(logits, inst_idx, factor, h, w, Ho, Wo, out=None):
+    """A window's final masks counted against each other on the device: for the rows `inst_idx` (int32 CUDA [n_sel], n_sel <= 255) of
+    logits [n, Fw, Hm, Wm], with b_k the final-mask bit of row k (ops.final_masks' own bit) and o the pixel's owner (ops.final_label_map's
+    own choice among those rows), occ[k, f, j] = the number of pixels of window frame f with b_k set and o == j.  So occ[k, f, k] is the
+    area of k's visible region, occ[k, f].sum() the area of its dense mask and, for j != k, occ[k, f, j] the part of k that j hides
+    (the rule of include/mdqe_hip.h, mdqe_final_masks_occlusion; helpers on the table: occlusion.py).  `out`: a contiguous int32 CUDA
+    [n_sel, Fw, n_sel] buffer to write into (fully overwritten, whatever it held).  Integers only: exact, identical from run to run.
+    -> occ int32 CUDA [n_sel, Fw, n_sel]."""
+    # (shapes and dtypes first, devices after: what a host without a GPU can check is checked the same way there)
+    if not torch.is_tensor(logits) or logits.dim() != 4:
+        raise RuntimeError("final_occlusion: logits must be [n, Fw, Hm, Wm], got %s" % (tuple(getattr(logits, "shape", ())),))
+    if not torch.is_tensor(inst_idx) or inst_idx.dtype != torch.int32 or inst_idx.dim() != 1 or int(inst_idx.numel()) > 255:
+        raise RuntimeError("final_occlusion: inst_idx must be int32 [n_sel <= 255]")
+    k, Fw = int(inst_idx.numel()), int(logits.shape[1])
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.int32 or tuple(out.shape) != (k, Fw, k) or not out.is_contiguous()):
+        raise RuntimeError("final_occlusion: out must be contiguous int32 [n_sel = %d, Fw = %d, n_sel]" % (k, Fw))
+    if out is not None and (not out.is_cuda or out.device != logits.device):
+        raise RuntimeError("final_occlusion: out must be a CUDA tensor on the logits' device, got %s" % (out.device,))
+    k, Fw, Hm, Wm = _final_mask_args(logits, inst_idx, True)
+    if out is None:
+        out = torch.empty((k, Fw, k), dtype=torch.int32, device=logits.device)
+    check(lib.mdqe_final_masks_occlusion(ptr(logits), k, ptr(inst_idx), Fw, Hm, Wm, factor, h, w, Ho, Wo, ptr(out), cur_stream()),
+          "final_occlusion")
+    return out
+
+
 def _action_arg(name, action):
     """The per-label action table of the painters that take one."""
     if not torch.is_tensor(action) or action.dtype != torch.uint8 or tuple(action.shape) != (256,) or not action.is_contiguous():

@@ -572,6 +572,10 @@ class _Job:
         if getattr(model, "path_output", False):
             raise ValueError("path_output is not offered by the sharded driver: the centroids are summed from the label map where it is made, "
                              "window by window on one device (sum them from pred_label_map on the host, or run the video on one device)")
+        if getattr(model, "occlusion_output", False):
+            raise ValueError("occlusion_output is not offered by the sharded driver: the table is counted from every window's logits where "
+                             "the window is flushed, on one device (count it from pred_masks and pred_label_map on the host, or run the "
+                             "video on one device)")
         if getattr(model, "polygon_output", None) is not None:
             raise ValueError("polygon_output is not offered by the sharded driver: the outlines are traced from the label map where it is "
                              "made, window by window on one device (trace them from pred_label_map on the host with "
